@@ -12,6 +12,12 @@ evaluated by ONE launch of the fused kernel (default B = 4096: 256 blocks of 16 
 per-state tables, 221 MB, stay in the 256 MB Infinity Cache between launches, beyond that they stream from HBM; `batch_sweep`
 in the output line).  Everything (feature block, group ids, probability tables, weights) is
 resident in HBM before the timed region; the B scalars are fetched to the host inside it.
+
+A plain run (no --full) does only what the headline figure needs: set up the B states, warm up (--warmup steps, then more
+until WARMUP_MIN_S have run), time exactly --steps steps once, write the last step's B results if --dump-outputs is given,
+print the line (metric, value, unit, ms_per_step, dtype, results_sha1, ...).  Everything below -- the repeated timed loop and its median, the parity gate,
+the kernel time and roofline, the secondary figures, the two legs, the CPU baselines, the per-rank figures of N > 1 --
+runs only with --full.
 `single_chain` in the output line is what ONE chain sees (B = 1, host-synchronous), `per_config`
 covers every 1-GPU BASELINE config (cfg1, south_america, headline, stress) at B = 1 / 8 / 64.
 
@@ -36,7 +42,8 @@ Two further legs beside the headline figure (rank 0, N = 1): `hbm_regime` -- 2 x
 -- every step first moves one object of EVERY state to another cluster (count delta, the two touched clusters' tables rebuilt:
 sbayes/sampling/counts.py:55-95, conditionals.py:171-188) and then evaluates all of them: no launch re-reads frozen tables.
 
-  python bench.py                       # 1 GPU, defaults finish in about a minute
+  python bench.py                       # 1 GPU, the headline figure alone: a few seconds
+  python bench.py --full                # every figure and check: about a minute
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -66,6 +73,7 @@ HEADLINE_BATCH = 4096      # resident states per launch (tools/summarize_profile
 NOMINAL_CLOCK_GHZ = 2.4    # MI355X_MICROARCH.md "Max clock"
 I8_MFMA_PEAK_TOPS = 5000.0 # MI355X_MICROARCH.md: dense i8 MFMA = 2 x the bf16 rate (~2.5 PF): ~5 POP/s
 FP4_MFMA_PEAK_TOPS = 10000.0   # MI355X_MICROARCH.md: dense FP4 (v_mfma_f32_32x32x64_f8f6f4) = 4 x the bf16 rate: ~10 PF
+WARMUP_MIN_S = 0.25        # the warm-up runs at least this long (the clocks settle within ~0.1-0.2 s of launches)
 PMC_FILE = "profiles/r6/pmc_summary.json"
 TRAFFIC_FILE = "profiles/traffic_latest.json"
 
@@ -78,7 +86,8 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=20,
+                    help=f"warm-up steps before the timed ones; more follow, 16 at a time, until the warm-up has run {WARMUP_MIN_S} s")
     ap.add_argument("--workload", default="headline", choices=["cfg1", "south_america", "headline", "stress"])
     ap.add_argument("--batch", type=int, default=None,
                     help="resident sample states (chains x candidate states) evaluated per step "
@@ -100,11 +109,20 @@ def parse():
     ap.add_argument("--no-legs", action="store_true", help="skip the hbm_regime and changing_tables legs (and their extra slots)")
     ap.add_argument("--legs", action="store_true", help="run the two legs even with --no-secondary (tests)")
     ap.add_argument("--min-time", type=float, default=0.05,
-                    help="the K-step timed loop is repeated (each repetition bracketed by barrier + sync on both sides) "
+                    help="with --full, the K-step timed loop is repeated (each repetition bracketed by barrier + sync on both sides) "
                          "until the repetitions together cover this many seconds; the MEDIAN repetition is reported")
-    ap.add_argument("--reps", type=int, default=0, help="force the number of repetitions of the K-step loop (0: from --min-time)")
+    ap.add_argument("--reps", type=int, default=0,
+                    help="with --full, force the number of repetitions of the K-step loop (0: from --min-time)")
     ap.add_argument("--explore", action="store_true", help="also print the batch sweep to stderr")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (latency, sweep, per_config, a1/a7 rates)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the repeated K-step loop (--min-time / "
+                         "--reps, median reported), the oracle parity gate, the roofline and kernel-time figures, the secondary "
+                         "figures, the two legs, the CPU baselines and the per-rank figures of N > 1.  The options above that "
+                         "name these act only with --full.  Without it: set up, warm up, time the K steps once, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the B log-likelihoods (float64) of the last one to DIR/mixture_loglik.npy "
+                         "(rank r > 0: DIR/mixture_loglik_rank<r>.npy)")
     return ap.parse_args()
 
 
@@ -225,6 +243,15 @@ def verify_results(eng, wl, slots, values, what, want0=None, tol=1e-10):
         if not err <= tol:
             raise RuntimeError(f"parity gate failed ({what}): slot {int(slot)} device {float(got)!r} oracle {want!r} rel.err {err:.3e} > {tol}")
     return worst, [int(s) for s in slots]
+
+
+def dump_outputs(out_dir, rank, results):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the B float64 log-likelihoods of
+    fetch_results -- as .npy, so that two builds run with the same arguments (hence the same seeded states) can be compared."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    name = "mixture_loglik.npy" if rank == 0 else f"mixture_loglik_rank{rank}.npy"
+    np.save(out / name, np.ascontiguousarray(results, dtype=np.float64))
 
 
 def _median_rep(times):
@@ -839,9 +866,11 @@ def main():
     wl = load_workload(args.workload)
     n_obj, n_feat, n_states = wl.shape
     B = args.batch if args.batch else (64 if args.workload == "stress" else HEADLINE_BATCH)
+    full = args.full
     # the two legs beside the headline figure need a second set of B slots (candidates of the changing-tables leg, then the
     # upper half of the 2 B states of the HBM-regime launch): rank 0 of a 1-GPU run only
-    legs = rank == 0 and n_gpus == 1 and not args.no_legs and (args.legs or not args.no_secondary) and args.kernel == "packed" and 2 * B <= 16384
+    legs = (full and rank == 0 and n_gpus == 1 and not args.no_legs and (args.legs or not args.no_secondary)
+            and args.kernel == "packed" and 2 * B <= 16384)
     t_setup = time.perf_counter()
     eng = setup_engine(wl, B, device, args.kernel, args.log_mode, n_slots=2 * B if legs else B)
     t_setup = time.perf_counter() - t_setup
@@ -853,9 +882,12 @@ def main():
     # ---- oracle value of the workload's own state (slot 0); the gate itself runs on the TIMED results, below ------
     want = None
     if rank == 0:
-        orc, oargs = oracle_eval(wl)
-        want = float(orc.mixture_loglik(*oargs))
-        log(f"[bench] {B} states ready in {t_setup:.1f} s; oracle value of slot 0: {want!r}")
+        if full:
+            orc, oargs = oracle_eval(wl)
+            want = float(orc.mixture_loglik(*oargs))
+            log(f"[bench] {B} states ready in {t_setup:.1f} s; oracle value of slot 0: {want!r}")
+        else:
+            log(f"[bench] {B} states ready in {t_setup:.1f} s")
 
     def barrier():
         eng.sync()
@@ -865,23 +897,31 @@ def main():
     def step():
         eng.mixture_loglik_batch_async(0, B)
 
-    for _ in range(args.warmup):
-        step()
-    eng.fetch_results(0, B)
+    # warm-up: --warmup steps, then more in synchronised chunks until WARMUP_MIN_S of them have run -- the clocks take about
+    # that long to settle, and the K steps are timed once in a plain run
+    warmup_steps = 0
+    t_warm = time.perf_counter()
+    while warmup_steps < args.warmup or time.perf_counter() - t_warm < WARMUP_MIN_S:
+        for _ in range(max(args.warmup - warmup_steps, 16)):
+            step()
+            warmup_steps += 1
+        eng.fetch_results(0, B)
 
-    stride = args.event_stride
-    eng.profile_mixture(0, B, 64)                  # (grows the engine's event pool outside the timed region)
-    eng.kernel_timing_start()                      # (events are bracketing nothing until resumed inside the loop)
-    eng.kernel_timing_pause()
+    stride = args.event_stride if full else 0
+    if full:
+        eng.profile_mixture(0, B, 64)              # (grows the engine's event pool outside the timed region)
+        eng.kernel_timing_start()                  # (events are bracketing nothing until resumed inside the loop)
+        eng.kernel_timing_pause()
 
     own_times, spans = [], []
 
     def timed_rep():
-        """EXACTLY K steps, barrier + stream sync on both sides, max over ranks.  One event pair on the engine's stream
-        spans the K launches (first event before launch 1, second behind launch K, read after the fetch)."""
+        """EXACTLY K steps, barrier + stream sync on both sides, max over ranks.  With --full, one event pair on the engine's
+        stream spans the K launches (first event before launch 1, second behind launch K, read after the fetch)."""
         barrier()
         t0 = time.perf_counter()
-        eng.timer_start()
+        if full:
+            eng.timer_start()
         for i in range(args.steps):
             if stride > 0 and i % stride == 0:
                 eng.kernel_timing_resume()         # (secondary figure: event pair around the dominant kernel of this launch)
@@ -889,84 +929,94 @@ def main():
                 eng.kernel_timing_pause()
             else:
                 step()
-        eng.timer_mark()
+        if full:
+            eng.timer_mark()
         res = eng.fetch_results(0, B)              # D2H of the B scalars + stream sync, inside the timed region
         own = time.perf_counter() - t0             # this rank's own K steps (before it waits for the others)
         barrier()
         dt = time.perf_counter() - t0
-        spans.append(eng.timer_elapsed() * 1e-3)   # seconds; the second event is long done
+        if full:
+            spans.append(eng.timer_elapsed() * 1e-3)   # seconds; the second event is long done
         own_times.append(own)
         return chains.max_over_ranks(dt, dist), res
 
-    # A K-step loop is ~1 ms at the driver's K = 20: one stray interrupt moves it by percents.  The loop is therefore
-    # repeated -- every repetition is the contract's region (exactly K steps, barrier + sync both sides, max over
-    # ranks; the repetition count follows from the first one's all-reduced time, so every rank runs the same number)
-    # -- and the MEDIAN repetition is reported: value, ms_per_step and the kernel span all come from that ONE repetition.
+    # A plain run times the K steps ONCE: --steps is the number of timed steps.  With --full, a K-step loop of ~1 ms at the
+    # driver's K = 20 is moved by percents by one stray interrupt, so the loop is repeated -- every repetition is the
+    # contract's region (exactly K steps, barrier + sync both sides, max over ranks; the repetition count follows from the
+    # first one's all-reduced time, so every rank runs the same number) -- and the MEDIAN repetition is reported: value,
+    # ms_per_step and the kernel span all come from that ONE repetition.
     first, results = timed_rep()
-    n_reps = args.reps if args.reps > 0 else int(min(200, max(5, np.ceil(args.min_time / max(first, 1e-9)))))
-    n_reps += 1 - n_reps % 2                           # an odd count: the median is ONE repetition, not the upper of two middle ones
+    n_reps = 1
+    if full:
+        n_reps = args.reps if args.reps > 0 else int(min(200, max(5, np.ceil(args.min_time / max(first, 1e-9)))))
+        n_reps += 1 - n_reps % 2                       # an odd count: the median is ONE repetition, not the upper of two middle ones
     rep_times = [first]
     for _ in range(n_reps - 1):
         dt, results = timed_rep()
         rep_times.append(dt)
     k_med = _median_rep(rep_times)
     elapsed = float(rep_times[k_med])
-    kern_ms = spans[k_med] / args.steps * 1e3      # this rank's span of the median repetition / K
-    pair_n, pair_ms = 0, None
-    if stride <= 0 and rank == 0:                  # the same launches again, each bracketed by an event pair (secondary figure)
-        eng.kernel_timing_start()
-        for _ in range(max(args.steps, 20)):
-            step()
-        eng.fetch_results(0, B)
-    pair_n, pair_ms = eng.kernel_timing_stop()
     assert np.all(np.isfinite(results))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, results)
 
     evals = args.steps * B * n_gpus
     value = evals / elapsed
     ms_per_step = elapsed / args.steps * 1e3
-    # a kernel cannot take longer than the step that contains it; the span lies inside this rank's own
-    # host-timed region, which is at most the max over ranks
-    assert kern_ms <= ms_per_step * 1.0005, (kern_ms, ms_per_step)
+    if full:
+        kern_ms = spans[k_med] / args.steps * 1e3  # this rank's span of the median repetition / K
+        if stride <= 0 and rank == 0:              # the same launches again, each bracketed by an event pair (secondary figure)
+            eng.kernel_timing_start()
+            for _ in range(max(args.steps, 20)):
+                step()
+            eng.fetch_results(0, B)
+        pair_n, pair_ms = eng.kernel_timing_stop()
+        # a kernel cannot take longer than the step that contains it; the span lies inside this rank's own
+        # host-timed region, which is at most the max over ranks
+        assert kern_ms <= ms_per_step * 1.0005, (kern_ms, ms_per_step)
 
     # ---- parity gate ON THE TIMED RESULTS (rank 0; outside the timed region): the last repetition's B values -------------------
     parity = parity_slots = None
-    if rank == 0:
+    if rank == 0 and full:
         rng = np.random.default_rng(2025)
         slots = np.unique(np.concatenate([[0, B - 1], rng.integers(0, B, size=15)])) if B > 1 else np.array([0])
         parity, parity_slots = verify_results(eng, wl, slots, results[slots], "timed launches", want0=want)
         log(f"[bench] parity of the timed kernel ({eng.last_mixture_kernel()}): {len(parity_slots)} slots incl. slot 0 = the workload's state, "
             f"oracle from device readback, max rel.err {parity:.3e}")
 
-    # ---- roofline of the dominant kernel ---------------------------------------------------------------------------
-    has_comp = np.stack([g.any(axis=0) for g in wl.groups], axis=1)
-    n_pat = len(np.unique(has_comp, axis=0))          # distinct has_components rows (likelihood.py:183)
-    packed = not args.kernel.startswith("onehot")
-    groups_per_comp = [g.shape[0] for g in wl.groups]
-    b_eval = algorithmic_bytes(n_obj, n_feat, n_states, groups_per_comp, n_pat, packed=packed)
     results_digest = __import__("hashlib").sha1(np.ascontiguousarray(results).tobytes()).hexdigest()[:16]
-    timed_kernel = eng.last_mixture_kernel()
-    traffic, valu, stale = static_profile_figures(args.workload, args.kernel, B, kern_ms * 1e3, timed_kernel, results_digest)
 
-    def unique_fn(n):
-        return unique_bytes_per_launch(n_obj, n_feat, n_states, groups_per_comp, n_pat, n, packed=packed)
-    roofline = roofline_block(b_eval, unique_fn(B), B, kern_ms, traffic, valu, timed_kernel, packed,
-                              f"one HIP event pair on the engine's stream around the {args.steps} back-to-back launches of the median "
-                              f"repetition / {args.steps}: the kernel plus the dispatch gap to the next one; it lies inside the "
-                              "host-timed region, so kernel_avg_us <= ms_per_step x 1000 (asserted); rocprofv3's kernel trace of the same "
-                              "command (profiles/) reads the kernel alone",
-                              shape=(n_obj, n_feat, n_states))
-    if pair_n:
-        roofline["kernel_event_pairs_us"] = round(pair_ms * 1e3, 3)
-        roofline["kernel_event_pairs_note"] = (f"secondary: HIP event pairs around {pair_n} single launches "
-                                               + ("issued right after the timed loops" if stride <= 0 else f"(every {stride}-th of the timed loops)")
-                                               + "; a pair also holds the dispatch gap behind the PREVIOUS kernel")
+    # ---- roofline of the dominant kernel ---------------------------------------------------------------------------
+    roofline = valu = stale = None
+    if full:
+        timed_kernel = eng.last_mixture_kernel()
+        has_comp = np.stack([g.any(axis=0) for g in wl.groups], axis=1)
+        n_pat = len(np.unique(has_comp, axis=0))      # distinct has_components rows (likelihood.py:183)
+        packed = not args.kernel.startswith("onehot")
+        groups_per_comp = [g.shape[0] for g in wl.groups]
+        b_eval = algorithmic_bytes(n_obj, n_feat, n_states, groups_per_comp, n_pat, packed=packed)
+        traffic, valu, stale = static_profile_figures(args.workload, args.kernel, B, kern_ms * 1e3, timed_kernel, results_digest)
+
+        def unique_fn(n):
+            return unique_bytes_per_launch(n_obj, n_feat, n_states, groups_per_comp, n_pat, n, packed=packed)
+        roofline = roofline_block(b_eval, unique_fn(B), B, kern_ms, traffic, valu, timed_kernel, packed,
+                                  f"one HIP event pair on the engine's stream around the {args.steps} back-to-back launches of the "
+                                  f"median repetition / {args.steps}: the kernel plus the dispatch gap to the next one; it lies inside "
+                                  "the host-timed region, so kernel_avg_us <= ms_per_step x 1000 (asserted); rocprofv3's kernel trace "
+                                  "of the same command (profiles/) reads the kernel alone",
+                                  shape=(n_obj, n_feat, n_states))
+        if pair_n:
+            roofline["kernel_event_pairs_us"] = round(pair_ms * 1e3, 3)
+            roofline["kernel_event_pairs_note"] = (f"secondary: HIP event pairs around {pair_n} single launches "
+                                                   + ("issued right after the timed loops" if stride <= 0 else f"(every {stride}-th of the timed loops)")
+                                                   + "; a pair also holds the dispatch gap behind the PREVIOUS kernel")
 
     # ---- what every rank (= every GPU's chains) saw by itself: north_star asks for PER-CHAIN throughput at each N ------
     # (chains are independent in the reference: sbayes/sampling/mcmc.py:239-241, one OS process per chain in MC3:
     #  sbayes/mcmc_setup.py:271-299).  Each rank reports its own batched rate (its own K steps, not the max over ranks),
     #  its own kernel time and what ONE host-synchronous chain gets on its GPU while the other ranks do the same.
     per_rank = None
-    if n_gpus > 1:
+    if n_gpus > 1 and full:
         own_rate = args.steps * B / float(np.median(own_times))
         barrier()
         for _ in range(10):
@@ -980,7 +1030,7 @@ def main():
                     for r in range(world)]
 
     extra = {}
-    if rank == 0 and n_gpus == 1 and not args.no_secondary:
+    if full and rank == 0 and n_gpus == 1 and not args.no_secondary:
         extra.update(secondary_figures(eng, wl, B, args))
         extra["per_config"] = per_config_block(device, eng if args.workload == "headline" and B >= 64 else None,
                                                0.0 if args.no_cpu_baseline else args.cpu_seconds)
@@ -1004,7 +1054,7 @@ def main():
             extra["value_changing_tables"] = extra["changing_tables"]["evals_per_s"]
 
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         ll_cpu, cpu_rate, n_cpu, cpu_el = cpu_baseline(wl, args.cpu_seconds)
         cpu = {"value": round(cpu_rate, 3), "unit": "evals/s", "cores": 1, "kind": "port",
                "sample": f"{n_cpu} uncached mixture-LL evals of the {args.workload} workload in {cpu_el:.1f} s, "
@@ -1033,9 +1083,11 @@ def main():
         line = {
             "metric": "log-likelihood evals/sec at 1000 sites x 200 feats x 10 states; 1/2/4/8-GPU chains",
             "value": round(value, 2), "unit": "evals/s", "n_gpus": n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5), "n_reps": n_reps,
-            "timed_region": {"what": f"{n_reps} repetitions of the {args.steps}-step loop, each bracketed by barrier + stream sync "
-                                     "on both sides and max-reduced over ranks; value / ms_per_step are the MEDIAN repetition",
+            "warmup": args.warmup, "warmup_steps_run": warmup_steps, "ms_per_step": round(ms_per_step, 5), "n_reps": n_reps,
+            "timed_region": {"what": (f"{n_reps} repetitions of the {args.steps}-step loop, each bracketed by barrier + stream sync "
+                                      "on both sides and max-reduced over ranks; value / ms_per_step are the MEDIAN repetition"
+                                      if full else f"the {args.steps}-step loop once, bracketed by barrier + stream sync on both "
+                                      "sides and max-reduced over ranks"),
                              "rep_ms_per_step_min": round(min(rep_times) / args.steps * 1e3, 5),
                              "rep_ms_per_step_median": round(ms_per_step, 5),
                              "rep_ms_per_step_max": round(max(rep_times) / args.steps * 1e3, 5),
@@ -1049,19 +1101,24 @@ def main():
                        "evals_per_step": B, "chains_per_gpu": B, "kernel": args.kernel, "log_mode": args.log_mode,
                        "single_chain_evals_per_s": extra.get("single_chain", {}).get("evals_per_s"),
                        "parallelism": f"{n_gpus} independent engine(s), one per GPU, no collectives"},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "parity_timed_kernel_max_rel_err": parity,
-            "parity_timed_kernel": {"slots": parity_slots, "tolerance": 1e-10, "kernel": timed_kernel,
-                                    "what": "the B results of the last timed repetition; slot 0 = the workload's own state (its oracle value "
-                                            "from the host arrays and from the device readback agree), the others random: group ids, source "
-                                            "rows and weights read back from the device, counts recounted by the oracle and compared bit for "
-                                            "bit with the device's, then oracle/sbayes_oracle.py mixture_loglik"},
+        }
+        if full:
+            line.update({
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "parity_timed_kernel_max_rel_err": parity,
+                "parity_timed_kernel": {"slots": parity_slots, "tolerance": 1e-10, "kernel": timed_kernel,
+                                        "what": "the B results of the last timed repetition; slot 0 = the workload's own state (its oracle "
+                                                "value from the host arrays and from the device readback agree), the others random: group "
+                                                "ids, source rows and weights read back from the device, counts recounted by the oracle and "
+                                                "compared bit for bit with the device's, then oracle/sbayes_oracle.py mixture_loglik"},
+            })
+        line.update({
             "results_sha1": results_digest,   # (rank 0's B results of the last repetition: A/B runs of engine builds must agree on it)
             "device": info["device_name"],
             "dist_backend": chains.backend_name(dist),
             "setup_s": round(t_setup, 2),
-        }
+        })
         if per_rank:
             line["per_rank"] = per_rank
             line["per_rank_evals_per_s_min"] = min(r["evals_per_s"] for r in per_rank)

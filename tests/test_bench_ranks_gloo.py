@@ -10,29 +10,39 @@ import sys
 import textwrap
 from pathlib import Path
 
+import numpy as np
+
 REPO = Path(__file__).resolve().parent.parent
 
 STUB_RUNNER = textwrap.dedent('''
-    import os, sys, time
+    import json, os, sys, time
     import numpy as np
     sys.path.insert(0, %(repo)r)
     import bench
     import sbayes_amd.engine as engine_mod
 
+    ENGINES = []
+
     class StubEngine:
-        """Stands in for sbayes_amd.engine.Engine: remembers its device, returns the oracle-free constant results."""
+        """Stands in for sbayes_amd.engine.Engine: remembers its device, counts its launches, returns oracle-free results
+        (slot i: i + the number of launches so far)."""
         def __init__(self, wl, batch, device):
             self.device, self.batch = device, batch
-            self.n_timed = 0
+            self.n_timed = self.n_launches = self.n_profiled = 0
+            ENGINES.append(self)
         def info(self):
             return {"device": self.device, "device_name": "stub"}
         def sync(self): pass
         def mixture_loglik(self, slot):
             time.sleep(0.0008 if self.device == 5 else 0.0002)
             return -1.0
-        def mixture_loglik_batch_async(self, first, n): time.sleep(0.004 if self.device == 5 else 0.001)      # rank 5 is slow
-        def fetch_results(self, first, n): return np.full(n, -1.0)
-        def profile_mixture(self, first, n, iters): return 0.0, 0.0
+        def mixture_loglik_batch_async(self, first, n):
+            self.n_launches += 1
+            time.sleep(0.004 if self.device == 5 else 0.001)      # rank 5 is slow
+        def fetch_results(self, first, n): return np.arange(first, first + n, dtype=np.float64) + self.n_launches
+        def profile_mixture(self, first, n, iters):
+            self.n_profiled += 1
+            return 0.0, 0.0
         def timer_start(self): pass
         def timer_mark(self): pass
         def timer_elapsed(self): return 6 * 0.05                   # ms: span of the K = 6 launches of a repetition
@@ -50,14 +60,16 @@ STUB_RUNNER = textwrap.dedent('''
     _orig = chains.init_process_group
     chains.init_process_group = lambda backend=None: _orig("gloo")
     bench.oracle_eval = lambda wl: (type("O", (), {"mixture_loglik": staticmethod(lambda *a: -1.0)}), ())
-    sys.argv = ["bench.py", "--gpus", "8", "--steps", "6", "--warmup", "2", "--workload", "cfg1", "--batch", "4"]
+    sys.argv = ["bench.py"] + %(argv)r
     bench.main()
+    print("STUB " + json.dumps({"launches": sum(e.n_launches for e in ENGINES), "profiled": sum(e.n_profiled for e in ENGINES)}))
 ''')
 
 
 def test_bench_rank_logic_world_size_8(tmp_path):
     runner = tmp_path / "runner.py"
-    runner.write_text(STUB_RUNNER % {"repo": str(REPO)})
+    runner.write_text(STUB_RUNNER % {"repo": str(REPO), "argv": ["--gpus", "8", "--steps", "6", "--warmup", "2", "--workload", "cfg1",
+                                                                  "--batch", "4", "--full"]})
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -95,3 +107,30 @@ def test_bench_rank_logic_world_size_8(tmp_path):
     # the kernel time is the span of a repetition's K launches / K and fits inside the step
     assert rf["kernel_avg_us"] == 50.0 and rf["kernel_avg_us"] <= line["ms_per_step"] * 1e3
     assert line["parity_timed_kernel_max_rel_err"] == 0.0 and 0 in line["parity_timed_kernel"]["slots"]
+
+
+def test_plain_bench_times_exactly_the_steps_and_dumps_the_last_results(tmp_path):
+    """Without --full (one process, no process group): the warm-up (at least --warmup steps, at least WARMUP_MIN_S) and EXACTLY
+    --steps launches -- one repetition, no other launch --, the headline keys only, and --dump-outputs writes the B float64
+    results the last timed step returned."""
+    runner = tmp_path / "runner.py"
+    out = tmp_path / "out"
+    runner.write_text(STUB_RUNNER % {"repo": str(REPO), "argv": ["--steps", "7", "--warmup", "3", "--workload", "cfg1", "--batch", "4",
+                                                                  "--dump-outputs", str(out)]})
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SBAYES_AMD_FORCE_DIST")}
+    res = subprocess.run([sys.executable, str(runner)], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 7 and line["warmup"] == 3 and line["n_reps"] == 1
+    assert line["unit"] == "evals/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and "metric" in line
+    assert abs(line["value"] - 7 * 4 / (line["ms_per_step"] * 7 / 1e3)) <= 1e-3 * line["value"]
+    for key in ("roofline", "cpu_baseline", "parity_timed_kernel", "per_config", "sampler_replay", "hbm_regime", "per_rank"):
+        assert key not in line, key
+    stub = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("STUB ")][-1][5:])
+    warm = line["warmup_steps_run"]
+    assert warm >= 3 + 16                      # (3 stub launches take far less than WARMUP_MIN_S: chunks of 16 followed)
+    assert stub == {"launches": warm + 7, "profiled": 0}
+    dumped = np.load(out / "mixture_loglik.npy")
+    assert dumped.dtype == np.float64 and np.array_equal(dumped, np.arange(4) + warm + 7.0)

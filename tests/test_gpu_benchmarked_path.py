@@ -114,8 +114,8 @@ def test_bench_line_is_self_consistent_and_self_proving():
     the TIMED results and both legs' results passed the oracle gate (the run fails otherwise), the legs report their figures."""
     import json
     import subprocess
-    res = subprocess.run([sys.executable, str(REPO / "bench.py"), "--batch", "512", "--steps", "5", "--warmup", "2", "--no-secondary",
-                          "--no-cpu-baseline", "--legs"], capture_output=True, text=True, timeout=600, cwd=str(REPO))
+    res = subprocess.run([sys.executable, str(REPO / "bench.py"), "--batch", "512", "--steps", "5", "--warmup", "2", "--full",
+                          "--no-secondary", "--no-cpu-baseline", "--legs"], capture_output=True, text=True, timeout=600, cwd=str(REPO))
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     rf = line["roofline"]
@@ -128,3 +128,23 @@ def test_bench_line_is_self_consistent_and_self_proving():
     assert hbm["kernel_avg_us"] <= hbm["ms_per_step"] * 1000.0 * 1.0005
     assert chg["states"] == 512 and chg["parity_max_rel_err"] <= 1e-10 and chg["evals_per_s"] > 0
     assert line["value_hbm_regime"] == hbm["evals_per_s"] and line["value_changing_tables"] == chg["evals_per_s"]
+
+
+def test_plain_bench_dumps_what_the_gated_run_computed(tmp_path):
+    """bench.py without --full times the steps once and checks nothing; --dump-outputs of such a run must hold, bit for bit, the
+    B results that a --full run of the same arguments passed through the oracle parity gate."""
+    import json
+    import subprocess
+    common = ["--batch", "512", "--steps", "5", "--warmup", "2"]
+    lines = {}
+    for mode, extra in (("full", ["--full", "--no-secondary", "--no-cpu-baseline", "--no-legs"]), ("plain", [])):
+        res = subprocess.run([sys.executable, str(REPO / "bench.py"), *common, *extra, "--dump-outputs", str(tmp_path / mode)],
+                             capture_output=True, text=True, timeout=600, cwd=str(REPO))
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines[mode] = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    full, plain = lines["full"], lines["plain"]
+    assert full["parity_timed_kernel_max_rel_err"] <= 1e-10
+    assert plain["n_reps"] == 1 and plain["steps"] == 5 and plain["value"] > 0 and "roofline" not in plain
+    got, want = np.load(tmp_path / "plain" / "mixture_loglik.npy"), np.load(tmp_path / "full" / "mixture_loglik.npy")
+    assert got.dtype == np.float64 and got.shape == (512,) and np.array_equal(got, want)
+    assert plain["results_sha1"] == full["results_sha1"]

@@ -23,7 +23,7 @@ def test_bench_under_a_forced_process_group(backend):
     env = dict(os.environ, SBAYES_AMD_DIST_BACKEND=backend, SBAYES_AMD_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), str(REPO / "bench.py"), "--gpus", "1",
-                          "--steps", "3", "--warmup", "1", "--batch", "64", "--no-secondary", "--no-cpu-baseline"],
+                          "--steps", "3", "--warmup", "1", "--batch", "64", "--full", "--no-secondary", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=str(REPO))
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
-BENCH="python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
+BENCH="python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA --kernel-trace --output-format csv -d $OUT/sq1 -- $BENCH > /dev/null 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/sq2 -- $BENCH > /dev/null 2>&1

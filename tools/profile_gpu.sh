@@ -9,7 +9,7 @@ ONLY=${2:-all}            # "headline": the headline passes only (the stress sha
 OUT=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
-BENCH="python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
+BENCH="python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
 for kern in packed packed_tuple packed_tuple_lds packed_general packed_v2 onehot onehot_general; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$kern -- $BENCH --kernel $kern > $OUT/bench_$kern.json 2> $OUT/bench_$kern.err
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch_$kern -- $BENCH --kernel $kern > /dev/null 2>&1
@@ -34,13 +34,13 @@ fi
 # stress shape (HBM/MALL streaming regime): rows kernel (default at B >= 2), the older general kernel, one-hot stream
 for kern in packed packed_v2 onehot; do
   for B in 8 64; do
-    SB="python3 bench.py --workload stress --batch $B --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --kernel $kern"
+    SB="python3 bench.py --full --workload stress --batch $B --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --kernel $kern"
     rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_stress_${kern}_b$B -- $SB > $OUT/bench_stress_${kern}_b$B.json 2> $OUT/bench_stress_${kern}_b$B.err
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch_stress_${kern}_b$B -- $SB > /dev/null 2>&1
     echo "done stress $kern B=$B"
   done
 done
-SB="python3 bench.py --workload stress --batch 64 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --kernel packed"
+SB="python3 bench.py --full --workload stress --batch 64 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --kernel packed"
 # (control: the rows kernel with the objects in their own order -- what ran before round 5)
 SBE_ROWS_SORTED=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_stress_packed_unsorted_b64 -- $SB > $OUT/bench_stress_packed_unsorted_b64.json 2> $OUT/bench_stress_packed_unsorted_b64.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA --kernel-trace --output-format csv -d $OUT/pmc_sq1_stress_packed_b64 -- $SB > /dev/null 2>&1

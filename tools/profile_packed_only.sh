@@ -4,7 +4,7 @@ TAG=${1:-r1b}
 OUT=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
-BENCH="python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
+BENCH="python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-secondary"
 kern=packed
 rm -rf $OUT/trace_$kern $OUT/pmc_fetch_$kern $OUT/pmc_write_$kern $OUT/pmc_sq1_$kern $OUT/pmc_sq2_$kern
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$kern -- $BENCH --kernel $kern > $OUT/bench_$kern.json 2> $OUT/bench_$kern.err
