@@ -757,30 +757,11 @@ int sbe_collapsed_and_source_prior(sbe_engine* e, int slot, double* per_group_ou
 
 int sbe_observation_lh_exact(sbe_engine* e, int slot, double* out) {
     CHECK_ENGINE(e); CHECK_SLOT(e, slot); CHECK_PTR(e, out);
-    Slot& s = e->slots[slot];
-    if (!s.groups_set || !s.source_set || !s.weights_set) return fail(e, SBE_ERR_STATE, "slot %d: groups / source / weights not set", slot);
-    { int orc = reject_overlap(e, slot, "sbe_observation_lh_exact"); if (orc) return orc; }
-    for (int c = 0; c < e->C; ++c)
-        if (!s.counts_set[c] || !e->conc_set[c]) return fail(e, SBE_ERR_STATE, "slot %d: counts / concentration of component %d not set", slot, c);
-    HIPCHK(e, hipSetDevice(e->device));
-    int rc = SBE_OK;
-    if (s.patterns_dirty) { rc = upload_patterns_and_weights(e, slot); if (rc) return rc; }
-    const int64_t n = (int64_t)e->N * e->F;
-    rc = ensure_scratch(e, n * sizeof(double));
+    int rc = enqueue_lh_exact(e, slot, "sbe_observation_lh_exact");
     if (rc) return rc;
-    rc = clear_status_word(e, ST_BAD_NORMALIZE);
+    rc = d2h(e, out, e->d_scratch, (size_t)e->N * e->F * sizeof(double));
     if (rc) return rc;
-    k_lh_exact<<<div_up(n, 256), 256, 0, e->stream>>>(
-        e->d_state, e->d_src + (int64_t)slot * e->N * e->Fp, e->d_gid + (int64_t)slot * e->C * e->Np,
-        e->d_counts + (int64_t)slot * e->table_elems(), e->d_conc, (double*)e->d_scratch, e->N, e->Np, e->F, e->S, e->C,
-        e->Fp, e->d_status, e->d_wpat + (int64_t)slot * e->Pmax * e->F * e->C, e->d_pid + (int64_t)slot * e->Np);
-    HIPCHK(e, hipGetLastError());
-    rc = d2h(e, out, e->d_scratch, n * sizeof(double));
-    if (rc) return rc;
-    rc = read_status(e);
-    if (rc) return rc;
-    if (e->h_status[ST_BAD_NORMALIZE]) return fail(e, SBE_ERR_DATA, "normalize: non-positive row sum in leave-one-out tables (sbayes/util.py:1006 assert)");
-    return SBE_OK;
+    return lh_exact_report(e);
 }
 
 }  // extern "C"

@@ -1,0 +1,105 @@
+"""CPU checks of the ELPD boundary (include/sbe_elpd.h, sbayes_amd/elpd.py): the symbols are exported and bound by the
+module's own prototype table, and bad arguments are refused before the device is touched."""
+import ast
+import ctypes as ct
+import inspect
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from sbayes_amd import _lib, elpd
+
+REPO = Path(__file__).resolve().parent.parent
+
+
+def _declared():
+    text = re.sub(r"/\*.*?\*/", "", (REPO / "include" / "sbe_elpd.h").read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_symbol_of_the_header_is_exported_and_bound():
+    lib = elpd.load()
+    names = _declared()
+    assert len(names) == 12
+    for name in names:
+        assert hasattr(lib, name), f"{name} declared in include/sbe_elpd.h but not exported"
+    assert sorted(elpd.PROTOTYPES) == names
+    assert lib.sbe_elpd_abi_version() == elpd.ABI_VERSION
+    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+
+
+def test_every_array_handed_to_the_library_is_bound_to_a_name():
+    """elpd.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
+    tree = ast.parse(inspect.getsource(elpd))
+    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
+           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
+           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
+    assert not bad, bad
+
+
+def test_lds_threshold_is_within_the_budget():
+    s = elpd.lds_max_samples()
+    assert 30_000 < s < 40_960                     # 160 KiB of LDS at 4 bytes per sample, less the tail buffers
+
+
+@pytest.fixture
+def no_store(monkeypatch):
+    def refuse(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(elpd, "_Store", refuse)
+
+
+@pytest.mark.parametrize("lh,err", [
+    (np.ones((10, 3), dtype=np.float64), TypeError),
+    (np.ones(10, dtype=np.float32), ValueError),
+    (np.ones((10, 0), dtype=np.float32), ValueError),
+    (np.ones((1, 4), dtype=np.float32), ValueError),           # one sample: PSIS needs two
+])
+def test_bad_matrix_is_refused_before_the_device(no_store, lh, err):
+    with pytest.raises(err):
+        elpd.psis_loo(lh, burnin=0.0)
+
+
+@pytest.mark.parametrize("burnin", [1.0, 1.5, -0.1, 0.95])
+def test_bad_burnin_is_refused_before_the_device(no_store, burnin):
+    with pytest.raises(ValueError):
+        elpd.waic(np.ones((10, 3), dtype=np.float32), burnin=burnin)
+
+
+def test_bad_na_mask_is_refused_before_the_device(no_store):
+    lh = np.full((10, 3), 0.5, dtype=np.float32)
+    with pytest.raises(ValueError, match="na_values has 2 entries"):
+        elpd.psis_loo(lh, na_values=np.zeros(2, bool))
+    with pytest.raises(TypeError):
+        elpd.psis_loo(lh, na_values=np.zeros(3, np.int8))
+
+
+def test_too_many_samples_are_refused_with_the_limit(no_store):
+    with pytest.raises(ValueError, match=r"2\^20"):
+        elpd.psis_loo(np.ones((elpd.MAX_SAMPLES + 1, 1), dtype=np.float32), burnin=0.0)
+
+
+def test_c_abi_validates_before_the_device():
+    lib = elpd.load()
+    h = ct.c_void_p()
+    assert lib.sbe_elpd_create(ct.byref(h), 0, 0, 10) == 1 and not h
+    assert b"n_columns=0" in lib.sbe_elpd_last_error(None)
+    assert lib.sbe_elpd_create(ct.byref(h), 0, 5, 0) == 1
+    assert b"capacity=0" in lib.sbe_elpd_last_error(None)
+    assert lib.sbe_elpd_append_rows(None, None, 1) == 1
+    assert b"null store" in lib.sbe_elpd_last_error(None)
+    out = ct.c_int64()
+    assert lib.sbe_elpd_compute(None, 0, None, 0, None, None, None, None, ct.byref(out)) == 1
+
+
+def test_log_capacity_must_be_positive():
+    with pytest.raises(ValueError):
+        elpd.LikelihoodLog(object(), capacity=0)
+
+
+def test_handles_are_not_picklable():
+    import pickle
+    with pytest.raises(TypeError):
+        pickle.dumps(elpd.LikelihoodLog(object(), capacity=3))
