@@ -47,6 +47,7 @@ struct Slot {
     std::vector<uint32_t> h_toff;         // [Np] tid * (S+1) * 512                  } tables (valid when n_tuples > 0;
     std::vector<uint16_t> h_tuple_g;      // [kMaxTuples][kMaxComponents]            } the one-call step ships them in
     std::vector<uint8_t> h_tuple_p;       // [kMaxTuples]                            } its payload)
+    bool share_ok = false;                // the tuple tables fit the shared-operand epilogue (tuples_share_operands); kept with them
     bool groups_set = false, weights_set = false, source_set = false;
     std::vector<uint8_t> probs_set, counts_set;   // per component
     bool patterns_dirty = true;
@@ -677,6 +678,26 @@ void derive_patterns(sbe_engine* e, Slot& s) {
     for (int n = 0; n < N; ++n) s.h_pid[n] = index_of[bits[n]];
 }
 
+// Whether the slot's present tuples have ONE component-1 group and at most two weight patterns: the slots the matrix-pipe
+// kernel's shared-operand epilogue can evaluate (C = 2).  Recomputed wherever h_tuple_g / h_tuple_p change; the kernel checks
+// the same property again and reports NaN for a block whose slot does not have it.
+bool tuples_share_operands(const sbe_engine* e, const Slot& s) {
+    if (e->C != 2 || s.n_tuples == 0 || (int)s.h_tuple_p.size() != kMaxTuples) return false;
+    int first = -1, pb = -1;
+    for (int t = 0; t < kMaxTuples; ++t) {
+        const int pat = s.h_tuple_p[t];
+        if (pat == 0xFF) continue;
+        if (first < 0) { first = t; continue; }
+        if (s.h_tuple_g[(size_t)t * kMaxComponents + 1] != s.h_tuple_g[(size_t)first * kMaxComponents + 1]) return false;
+        const int pa = s.h_tuple_p[first];
+        if (pat != pa) {
+            if (pb < 0) pb = pat;
+            else if (pat != pb) return false;
+        }
+    }
+    return first >= 0;
+}
+
 // distinct group tuples (g_0..g_{C-1}) of the objects, for the group-tuple kernels (host mirrors only)
 void derive_tuples(sbe_engine* e, Slot& s) {
     const int N = e->N, C = e->C;
@@ -716,6 +737,7 @@ void derive_tuples(sbe_engine* e, Slot& s) {
     }
     s.n_tuples = ok ? n_tup : 0;
     s.inc_ok = ok;                                    // (derive_patterns ran just before: both count tables are current)
+    s.share_ok = tuples_share_operands(e, s);
 }
 
 // The same tables after a few objects changed their component-0 group (a cluster move), in O(moved): `s` holds the
@@ -777,6 +799,7 @@ bool update_patterns_and_tuples(sbe_engine* e, Slot& s, const int32_t* moved, co
     // table made the two step forms pick different kernels at N = 18).  Vacated indices at the end are dropped; one in
     // the middle sends the step to the full derivation.
     while (s.n_tuples > 0 && s.tup_cnt[s.n_tuples - 1] == 0) --s.n_tuples;
+    s.share_ok = tuples_share_operands(e, s);
     for (int t = 0; t < s.n_tuples; ++t)
         if (s.tup_cnt[t] == 0) return false;
     return s.n_tuples > 0;
@@ -945,7 +968,7 @@ int ensure_xt(sbe_engine* e) {
 }
 
 // geometry of a matrix-pipe launch over n slots with at most KT tuples each; n_split = 0: the form does not apply
-struct MfmaGeom { int n_split, nt_per_split, MT, SL; size_t lds; bool ws; };      // SL: slots per block (16 / 4 / 2)
+struct MfmaGeom { int n_split, nt_per_split, MT, SL; size_t lds; bool ws, shared; };      // SL: slots per block (16 / 4 / 2)
 // the wave-specialised kernel (sbe_mixture_mfma_ws.hip): OPT-IN (SBE_MFMA_WS=1).  Measured on hardware it loses to the
 // unspecialised kernel at the headline shape (72.0 against 64.5 us per 4096 states, profiles/r6/ws_experiment.log); kept, tested
 // (tests/test_gpu_shapes.py::test_mfma_wave_specialised_form) and selectable for same-box comparisons.
@@ -1013,7 +1036,7 @@ int launch_mfma_form(sbe_engine* e, int first_slot, int n, int KT, const MfmaGeo
     if (rc) return rc;
     MfmaMixParams p{};
     p.F = e->F; p.S = e->S; p.FS = e->F * e->S; p.Gtot = e->Gtot; p.Np = e->Np;
-    p.NT = e->xt_NT; p.KBp = e->xt_KBp; p.KT = KT; p.SL = mg.SL;
+    p.NT = e->xt_NT; p.KBp = e->xt_KBp; p.KT = KT; p.SL = mg.SL; p.shared = mg.shared ? 1 : 0;
     p.n_batch = n; p.n_split = mg.n_split; p.nt_per_split = mg.nt_per_split;
     p.first_slot = first_slot; p.slot_list = d_slots;
     p.xt = e->d_xt; p.xt_bytes = (uint32_t)e->xt_bytes;
@@ -1093,6 +1116,12 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         if (!force_mfma && mg.n_split > 0 && KT > 8 && e->N < e->mfma_wide_min_share * mg.MT * (32 / mg.SL)) mg = MfmaGeom{};
     }
     const bool mfma = mg.n_split > 0;
+    // the shared-operand epilogue: C = 2, 16 FP4 slots per block, at most 3 M tiles (6 tuples; 4 tiles spill), every slot of
+    // the launch fitting it (per-slot flag)
+    if (mfma && e->C == 2 && mg.SL == 16 && mg.MT <= 3 && !mg.ws && tuple_mfma_fp4() && tuple_mfma_shared()) {
+        mg.shared = true;
+        for (int i = 0; i < n && mg.shared; ++i) mg.shared = e->slots[slot_at(i)].share_ok;
+    }
     if (force_mfma && !mfma)
         return fail(e, SBE_ERR_ARG, "matrix-pipe group-tuple kernel forced but not applicable (tuples=%d, C=%d, LDS %zu bytes)", KT, e->C, mg.lds);
     if (mfma) combo = false;
@@ -1226,7 +1255,7 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         if (done_out) *done_out = done_k;
     }
     if (mfma) {
-        snprintf(e->last_kernel, sizeof e->last_kernel, "k_mixture_tuple_mfma%s<packed stream, group-tuple form, matrix pipe %s, %d slots x M tiles %d, C=%d>", mg.ws ? "_ws" : "", tuple_mfma_fp4() ? "fp4" : "i8", mg.SL, mg.MT, e->C);
+        snprintf(e->last_kernel, sizeof e->last_kernel, "k_mixture_tuple_mfma%s<packed stream, group-tuple form, matrix pipe %s, %d slots x M tiles %d, C=%d%s>", mg.ws ? "_ws" : "", tuple_mfma_fp4() ? "fp4" : "i8", mg.SL, mg.MT, e->C, mg.shared ? ", shared operands" : "");
         int rc = launch_mfma_form(e, first_slot, n, KT, mg, d_slots, mfma_reduce, done_k);
         if (rc) return rc;
     } else {

@@ -666,6 +666,7 @@ int prepare_step_delta(sbe_engine* e, uint8_t* h_base, const uint8_t* d_base, co
     }
     cd.patterns = cur.patterns; cd.n_tuples = cur.n_tuples;
     cd.h_tuple_g = cur.h_tuple_g; cd.h_tuple_p = cur.h_tuple_p; cd.pat_cnt = cur.pat_cnt; cd.tup_cnt = cur.tup_cnt;
+    cd.share_ok = cur.share_ok;
     cd.inc_ok = cur.inc_ok; cd.patterns_dirty = false;
     cd.groups_set = cur.groups_set; cd.weights_set = true; cd.source_set = cur.source_set;
     cd.counts_set = cur.counts_set;

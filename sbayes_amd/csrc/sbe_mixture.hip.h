@@ -65,6 +65,7 @@ struct MfmaMixParams {
     int NT, KBp;                                   // 32-column tiles of the (feature, state) axis; k-blocks of 64 (FP4 operands) / 32 (i8) objects, padded to a multiple of 4
     int KT;                                        // tuples used by the slots of this launch (max; <= 64)
     int SL;                                        // slots per block: 16 (KT <= 8), 4 (<= 32) or 2 (<= 64) -- the widest whose A image fits LDS
+    int shared;                                    // 1: the shared-operand epilogue (C = 2, 16 slots, FP4; every slot fits it: host flag)
     int n_batch, n_split, nt_per_split;            // slots of the launch; column splits (blocks per group of 16 slots); column tiles per split
     int first_slot;
     const int32_t* slot_list;                      // slots of this launch (n_batch entries), or null: first_slot + i
@@ -119,6 +120,7 @@ size_t tuple_mfma_lds_bytes(int MT, int C, int KBp);
 void fine_log_table(double* tab);                 // [2 * 1024] {1/c, log c} of k_mixture_tuple_mfma's log (sbe_mixture_mfma.hip)
 // false (nothing launched): an instance of the kernel carries static LDS, so its dynamic block does not start at address 0
 bool launch_tuple_mfma(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st);
+bool tuple_mfma_shared();                        // the shared-operand epilogue where it applies (SBE_MFMA_SHARED=0: never); fixed for the process
 constexpr int kTupleMfmaColsPerPass = 2;          // column tiles a wave of k_mixture_tuple_mfma owns per pass (= columns per lane)
 
 }  // namespace sbe

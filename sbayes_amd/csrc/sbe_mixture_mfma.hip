@@ -136,7 +136,8 @@ void fine_log_table(double* tab /* [2 * kFineLogEntries] */) {
 // SLB = log2(slots per block): 4 (16 slots x <= 8 tuples: the form of round 5), 2 (4 slots x <= 32 tuples), 1 (2 slots x <= 64 tuples:
 // the whole tuple table) -- an M tile's 32 rows are 32 / SL tuples x SL slots (row = (tuple in tile) * SL + slot), so a block of
 // MT <= 4 tiles holds MT * 32 / SL tuples.  The wide forms (round 6) put datasets with several confounders on the matrix pipe.
-template <int MT, int CT, int GT = 4, bool FP4 = true, int SLB = 4>
+// SHARE: the shared-operand epilogue (16 slots, C = 2, FP4; see the epilogue below).
+template <int MT, int CT, int GT = 4, bool FP4 = true, int SLB = 4, bool SHARE = false>
 __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixParams p) {
     typedef typename std::conditional<FP4, v16f_t, v16i_t>::type acc_t;      // counts: exact integers either way
     constexpr int SL = 1 << SLB, TPT = 32 / SL, TPB = MT * TPT;              // slots per block; tuples per M tile / per block
@@ -198,8 +199,16 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         return;
     }
     // ---- phase 0: tuple metadata, log table, A fragments (sbe_mixture_mfma.hip.h) -----------------------------------------
-    mfma_phase0<MT, CT, FP4, kMfmaThreads, decltype(slot_of), SL>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp);
+    mfma_phase0<MT, CT, FP4, kMfmaThreads, decltype(slot_of), SL, !SHARE>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp);
+    // shared-operand form: the slot and step descriptors take the place of the per-tuple metadata (256 + 256 MT <= 512 MT bytes)
+    static_assert(!SHARE || (SL == 16 && CT == 2 && FP4 && MT <= 3), "the shared-operand epilogue: 16 slots, C = 2, FP4 operands, <= 6 tuples");
+    const uint4* sdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off);
+    const uint4* tdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off + SL * 16);
+    if constexpr (SHARE) mfma_shared_desc<MT, SL>(p, slot_of, const_cast<uint4*>(sdesc), const_cast<uint4*>(tdesc));
     __syncthreads();
+    // a slot of the block that does not fit the shared form: the block's results are NaN (block-uniform)
+    bool bad = false;
+    if constexpr (SHARE) bad = __builtin_amdgcn_ballot_w64(sdesc[lane & (SL - 1)].w != 0u) != 0ull;
 
     // ---- phase 1: counts on the matrix pipe, table entries + log + dot product on the vector pipe ----------------------
     const int h = lane >> 5, cl = lane & 31;
@@ -367,6 +376,102 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         }
     };
 
+    // ---- shared-operand epilogue (SHARE) --------------------------------------------------------------------------------
+    // At C = 2 with one component-1 group per slot (a universal confounder) and at most two weight patterns per slot, the
+    // table entry of (slot, tuple t, column) is
+    //     v = w0(pat t) p0[g0(t)] + w1(pat t) p1        -- p1 and the two weight pairs the same for all of the slot's tuples.
+    // A step = (slot k of the lane, M tile m): the four entries (t0, r0), (t0, r1), (t1, r0), (t1, r1) of tuples t0 = 2m,
+    // t1 = 2m + 1 and the lane's two column tiles r -- exactly the order in which slot k's terms reach lsum[k] in the per-entry
+    // epilogue (m, tuple in tile, r), so every fp64 chain takes the same terms in the same order.  Per (slot, column tile) the
+    // epilogue loads p1 and the pairs (w0, w1) of patterns a and b once and forms u = w1 p1 in fp64 for both; an entry then
+    // needs its p0 load and
+    //     v = fma(w0, p0, u)     (pattern a; pattern b: the same FMA again on the lanes whose tuple has pattern b).
+    // Bits: the product of two float32 values is exact in fp64 (48 significant bits; exponents far inside fp64's range, also
+    // for float32 subnormals), so fma(w0, p0, w1 p1) and the per-entry form's fma(w1, p1, w0 p0) are both ONE rounding of
+    // the same exact sum, and round-to-nearest addition is commutative, signed zeros included ((+0) + (-0) = +0 either way).
+    // Infinities and NaNs: the exact products are the same values (0 x inf = NaN in both forms), so a non-finite entry stays
+    // non-finite and takes the rare path below in both; only the payload of a NaN may differ, and a NaN result is NaN.  The
+    // rows of ones (a tuple without a cluster, a tuple that is not there) and zero probabilities are ordinary values here.
+    // Tuples that are not there have no counts: whatever their entry is, it adds nothing (the rare path zeroes a non-normal
+    // one exactly as before).
+    // Pipeline: step descriptors (LDS) two steps ahead, p0 one step ahead, the next slot's shared operands during the
+    // current slot's steps (loaded at m = 1, converted at the next slot's first step).
+    constexpr int NSS = 8 * MT;                                       // steps: slot k major, M tile m minor
+    uint32_t sh_col4[kMfmaRN], sh_fw4[kMfmaRN], col4u = 0;
+    uint4 sdq, tdq[2];
+    float p0q[2][4], p1r[kMfmaRN];
+    uint32_t wr[kMfmaRN][4];                                          // raw (w0 a, w1 a, w0 b, w1 b) of the next slot
+    uint64_t selm[2][2];                                              // lanes whose tuple t0 / t1 has pattern b, per step parity
+    double w0a[kMfmaRN], ua[kMfmaRN], w0b[kMfmaRN], ub[kMfmaRN];      // the current slot's shared operands
+    auto k_slot = [&](int k) -> int { return (k & 3) + 8 * (k >> 2) + 4 * h; };     // slot of the block held in lsum[k]
+    auto sh_desc = [&](int k) { sdq = sdesc[k_slot(k)]; };
+    auto sh_load = [&]() {
+#pragma unroll
+        for (int r = 0; r < kMfmaRN; ++r) {
+            p1r[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr_rsrc, (int)(sdq.x + sh_col4[r]), 0, 0));
+            const u32x2_t va = __builtin_amdgcn_raw_buffer_load_b64(w_rsrc, (int)(sdq.y + sh_fw4[r]), 0, 0);
+            const u32x2_t vb = __builtin_amdgcn_raw_buffer_load_b64(w_rsrc, (int)(sdq.z + sh_fw4[r]), 0, 0);
+            const uint32_t a0 = va.x, a1 = va.y, b0 = vb.x, b1 = vb.y;              // (copies: see st_load)
+            wr[r][0] = a0; wr[r][1] = a1; wr[r][2] = b0; wr[r][3] = b1;
+        }
+    };
+    auto sh_conv = [&]() {
+#pragma unroll
+        for (int r = 0; r < kMfmaRN; ++r) {
+            const double p1 = (double)p1r[r];
+            w0a[r] = (double)__uint_as_float(wr[r][0]); ua[r] = (double)__uint_as_float(wr[r][1]) * p1;      // (exact)
+            w0b[r] = (double)__uint_as_float(wr[r][2]); ub[r] = (double)__uint_as_float(wr[r][3]) * p1;
+        }
+    };
+    auto td_read = [&](int q) { tdq[q & 1] = tdesc[k_slot(q / MT) * MT + q % MT]; };
+    // p0 of step q: columns of tile r = 1 are those of tile 0 plus 32, unclamped -- a column beyond F*S has no counts, and the
+    // buffer's range check makes any offset a valid read
+    auto p0_load = [&](int q) {
+        const uint4 d = tdq[q & 1];
+        const uint32_t o0 = d.x + col4u, o1 = d.y + col4u;
+        p0q[q & 1][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr_rsrc, (int)o0, 0, 0));
+        p0q[q & 1][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr_rsrc, (int)(o0 + 128u), 0, 0));
+        p0q[q & 1][2] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr_rsrc, (int)o1, 0, 0));
+        p0q[q & 1][3] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(pr_rsrc, (int)(o1 + 128u), 0, 0));
+        selm[q & 1][0] = __builtin_amdgcn_ballot_w64(d.z != 0u);
+        selm[q & 1][1] = __builtin_amdgcn_ballot_w64(d.w != 0u);
+    };
+    auto sh_comp = [&](int q, const acc_t (&acc)[MT][kMfmaRN]) __attribute__((always_inline)) {
+        const int k = q / MT, m = q % MT;
+        double vv[4], lg[4], cntd[4];
+        int cnt[4];
+        bool special = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int tt = i >> 1, r = i & 1;
+            const float c = acc[m][r][4 * ((k >> 2) + 2 * tt) + (k & 3)];      // an exact integer <= N
+            cnt[i] = (int)c; cntd[i] = (double)c;
+            const double p0 = (double)p0q[q & 1][i];
+            double v = fma(w0a[r], p0, ua[r]);
+            // pattern b: the same FMA with b's operands, under an EXEC mask of its lanes (restored in the same statement; SCC
+            // is clobbered by s_and_saveexec)
+            uint64_t keep;
+            asm("s_and_saveexec_b64 %1, %2\n\tv_fma_f64 %0, %3, %4, %5\n\ts_mov_b64 exec, %1"
+                : "+v"(v), "=&s"(keep) : "s"(selm[q & 1][tt]), "v"(w0b[r]), "v"(p0), "v"(ub[r]) : "scc");
+            vv[i] = v;
+            special |= __builtin_amdgcn_class(v, 0x2FF);
+        }
+        int kx[4];
+        tab_log4_n<4>(vv, lg, kx, tab_off, one_hi);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(special) != 0ull, 0)) {     // (the rare path of st_comp)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (__builtin_amdgcn_class(vv[i], 0x2FF)) { lg[i] = cnt[i] != 0 ? lib_log(vv[i]) : 0.0; kx[i] = kFineLogBias; }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            lsum[k] = fma(cntd[i], lg[i], lsum[k]);
+            ksum[k] = __mul24(cnt[i], kx[i]) + ksum[k];
+            asm volatile("" : "+v"(ksum[k]));
+            asm volatile("" : "+v"(lsum[k]));
+        }
+    };
+
     for (int nt0 = nt_lo + w * kMfmaRN; nt0 < nt_hi; nt0 += kMfmaWaves * kMfmaRN) {
         int toff[kMfmaRN];
 #pragma unroll
@@ -387,6 +492,32 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         counts_pass(acc, toff);
 #pragma unroll
         for (int r = 0; r < kMfmaRN; ++r) csum += ccnt[r];
+        if constexpr (SHARE) {
+#pragma unroll
+            for (int r = 0; r < kMfmaRN; ++r) {
+                const uint32_t colc = (uint32_t)min((nt0 + r) * 32 + cl, p.FS - 1);
+                sh_col4[r] = colc * 4u; sh_fw4[r] = colc / (uint32_t)p.S * (uint32_t)(CT * 4);
+            }
+            col4u = (uint32_t)(nt0 * 32 + cl) * 4u;
+            sh_desc(0); td_read(0); td_read(1);
+            sh_load();
+            p0_load(0);
+#pragma unroll
+            for (int q = 0; q < NSS; ++q) {
+                const int k = q / MT, m = q % MT;
+                if (m == 0) {
+                    sh_conv();                                        // slot k's operands (loaded during slot k - 1)
+                    if (k + 1 < 8) sh_desc(k + 1);
+                }
+                if (m == (MT > 1 ? 1 : 0) && k + 1 < 8) sh_load();    // slot k + 1's
+                if (q + 1 < NSS) {
+                    p0_load(q + 1);
+                    if (q + 2 < NSS) td_read(q + 2);
+                }
+                sh_comp(q, acc);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
         st_cols(nt0);
         // the single metadata buffer is refilled as soon as the loads of its last step (r = RN - 1) are out
         st_meta(0);
@@ -399,6 +530,7 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
             }
             st_comp(q, acc);
             __builtin_amdgcn_sched_barrier(0);
+        }
         }
     }
 
@@ -441,6 +573,7 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
 #pragma unroll
         for (int ww = 0; ww < kMfmaWaves; ++ww) { total += red[(ww * 2 + 0) * 16 + lane]; total += red[(ww * 2 + 1) * 16 + lane]; }
     }
+    if (bad) total = __longlong_as_double(0x7FF8000000000000ll);          // (a slot that does not fit the shared form)
     double* const my_partials = p.partials + (int64_t)max(my_slot, 0) * p.partials_stride;
     if (!p.results) {
         if (my_slot >= 0) my_partials[split] = total;
@@ -488,7 +621,12 @@ template <int MT, bool FP4, int SLB>
 static void launch_mfma_mt(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
     switch (C) {
         case 1: k_mixture_tuple_mfma<MT, 1, mfma_gt<MT, 1>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
-        case 2: k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
+        case 2:
+            if constexpr (FP4 && SLB == 4 && MT <= 3) {          // (MT = 4 spills: 37 VGPRs over 256)
+                if (p.shared) { k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), FP4, SLB, true><<<grid, kMfmaThreads, lds, st>>>(p); break; }
+            }
+            k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p);
+            break;
         case 3: k_mixture_tuple_mfma<MT, 3, mfma_gt<MT, 3>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
         default: k_mixture_tuple_mfma<MT, 4, mfma_gt<MT, 4>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
     }
@@ -497,9 +635,9 @@ static void launch_mfma_mt(int C, const MfmaMixParams& p, dim3 grid, size_t lds,
 // one-time: the kernels ask for up to the whole 160 KB of a CU's LDS.  The log table's index is its whole LDS address
 // (tab_off = 0), which holds only while the kernel has NO static LDS: checked here, once, on the host -- the guard inside the
 // kernel would store NaNs but not take its completion tickets, and a host-synchronous caller would wait for them.
-template <int MT, int CT, bool FP4, int SLB>
+template <int MT, int CT, bool FP4, int SLB, bool SHARE = false>
 static bool allow_lds() {
-    const void* fn = reinterpret_cast<const void*>(&k_mixture_tuple_mfma<MT, CT, mfma_gt<MT, CT>(), FP4, SLB>);
+    const void* fn = reinterpret_cast<const void*>(&k_mixture_tuple_mfma<MT, CT, mfma_gt<MT, CT>(), FP4, SLB, SHARE>);
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncAttributes attr{};
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) { (void)hipGetLastError(); return true; }   // (not answerable: the kernel's own guard stays)
@@ -513,12 +651,22 @@ static bool allow_lds_all() {
     ok &= allow_lds<2, 1, FP4, SLB>(); ok &= allow_lds<2, 2, FP4, SLB>(); ok &= allow_lds<2, 3, FP4, SLB>(); ok &= allow_lds<2, 4, FP4, SLB>();
     ok &= allow_lds<3, 1, FP4, SLB>(); ok &= allow_lds<3, 2, FP4, SLB>(); ok &= allow_lds<3, 3, FP4, SLB>(); ok &= allow_lds<3, 4, FP4, SLB>();
     ok &= allow_lds<4, 1, FP4, SLB>(); ok &= allow_lds<4, 2, FP4, SLB>(); ok &= allow_lds<4, 3, FP4, SLB>(); ok &= allow_lds<4, 4, FP4, SLB>();
+    if constexpr (FP4 && SLB == 4) {
+        ok &= allow_lds<1, 2, FP4, SLB, true>(); ok &= allow_lds<2, 2, FP4, SLB, true>(); ok &= allow_lds<3, 2, FP4, SLB, true>();
+    }
     return ok;
 }
 
 // operand format of the count contraction: FP4 (default) or i8 (SBE_MFMA_FP4=0: same-box comparisons); fixed for the process
 bool tuple_mfma_fp4() {
     static const bool on = [] { const char* v = getenv("SBE_MFMA_FP4"); return !(v && atoi(v) == 0); }();
+    return on;
+}
+
+// the shared-operand epilogue where the host finds that it applies (default), or never (SBE_MFMA_SHARED=0: same-box comparisons
+// and the bit-identity tests); fixed for the process
+bool tuple_mfma_shared() {
+    static const bool on = [] { const char* v = getenv("SBE_MFMA_SHARED"); return !(v && atoi(v) == 0); }();
     return on;
 }
 

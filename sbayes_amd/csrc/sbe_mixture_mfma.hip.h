@@ -82,7 +82,8 @@ struct __attribute__((aligned(CT <= 1 ? 8 : (CT <= 3 ? 16 : 32)))) TupleMeta {
 // metadata at `meta`.
 // SL = slots per block (16 / 4 / 2): an M tile's 32 rows are 32 / SL tuples x SL slots, row = (tuple in tile) * SL + slot; the
 // block holds TPB = MT * 32 / SL tuples.
-template <int MT, int CT, bool FP4, int NTHR, typename SlotOf, int SL = kMfmaSlots>
+// META = false: no per-tuple metadata (the shared-operand epilogue reads its own descriptors: mfma_shared_desc).
+template <int MT, int CT, bool FP4, int NTHR, typename SlotOf, int SL = kMfmaSlots, bool META = true>
 __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMixParams& p, const SlotOf& slot_of, uint32_t tab_off,
                                             uint32_t a_off, TupleMeta<CT>* meta, int KBp) {
     typedef TupleMeta<CT> Meta;
@@ -167,7 +168,7 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
             const int i = (int)threadIdx.x + k * kMfmaThreads;
             lt[k] = i < 2 * kFineLogEntries ? reinterpret_cast<const double*>(p.logtab)[i] : 0.0;
         }
-        const bool has_meta = (int)threadIdx.x < SL * TPB;
+        const bool has_meta = META && (int)threadIdx.x < SL * TPB;
         const int m_sl = (int)threadIdx.x / TPB, m_t = (int)threadIdx.x % TPB;
         const int m_slot = has_meta ? slot_of(m_sl) : -1;
         uint32_t m_pat = 0xFFu, m_g[CT];
@@ -179,6 +180,7 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
             for (int c = 0; c < CT; ++c) m_g[c] = p.tuple_g[(int64_t)m_slot * p.tuple_g_stride + m_t * kMaxComponents + c];
         }
         if (has_meta) meta[m_sl * TPB + m_t] = meta_of(m_slot, m_t, m_pat, m_g);
+        (void)meta;
 #pragma unroll
         for (int k = 0; k < LT; ++k) {
             const int i = (int)threadIdx.x + k * kMfmaThreads;
@@ -245,6 +247,55 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
             }
         }
     }
+}
+
+// Descriptors of the shared-operand epilogue (k_mixture_tuple_mfma, SHARE: 16 slots, C = 2).  A slot of that form has, over
+// its present tuples, ONE component-1 group and at most two weight patterns a, b; a tuple differs from its neighbours only in
+// its component-0 group and in which of the two patterns it has.  Per slot sl of the block (thread sl builds it):
+//     sdesc[sl]          = {goff1, woff_a, woff_b, bad}                          (byte offsets into probs / wpat)
+//     tdesc[sl * MT + m] = {goff0(2m), goff0(2m + 1), sel(2m), sel(2m + 1)}      (one ds_read_b128 per epilogue step)
+// sel = 1: the tuple has pattern b.  A tuple that is not there (pattern 0xFF, t >= KT, a slot beyond the batch) has no counts;
+// it keeps its component-0 row on the ones row, as in the per-tuple metadata, and selector 0.  bad != 0: the slot does not
+// fit the form (the host's per-slot flag was wrong) -- the block then reports NaN for its slots instead of a wrong number.
+template <int MT, int SL, typename SlotOf>
+__device__ __forceinline__ void mfma_shared_desc(const MfmaMixParams& p, const SlotOf& slot_of, uint4* sdesc, uint4* tdesc) {
+    constexpr int TPB = MT * 32 / SL;
+    static_assert(SL == 16 && TPB <= kMaxTuples, "the shared-operand form has 16 slots of <= 8 tuples");
+    if ((int)threadIdx.x >= SL) return;
+    const int sl = (int)threadIdx.x, slot = slot_of(sl);
+    uint32_t pat[TPB], g0[TPB], g1[TPB];
+#pragma unroll
+    for (int t = 0; t < TPB; ++t) {                       // (asked for together: one round trip)
+        pat[t] = 0xFFu; g0[t] = g1[t] = 0xFFFFFFFFu;
+        if (slot >= 0 && t < p.KT) {
+            pat[t] = p.tuple_p[(int64_t)slot * p.tuple_p_stride + t];
+            g0[t] = p.tuple_g[(int64_t)slot * p.tuple_g_stride + t * kMaxComponents + 0];
+            g1[t] = p.tuple_g[(int64_t)slot * p.tuple_g_stride + t * kMaxComponents + 1];
+        }
+    }
+    auto goff = [&](uint32_t g) -> uint32_t {
+        return (int)g < p.Gtot ? (uint32_t)(((int64_t)slot * p.probs_stride + (int64_t)g * p.FS) * 4) : p.probs_ones_off;
+    };
+    uint32_t goff1 = p.probs_ones_off, wa = p.wpat_ones_off, wb = p.wpat_ones_off, bad = 0u;
+    uint32_t go0[TPB], sel[TPB];
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < TPB; ++t) {
+        go0[t] = p.probs_ones_off; sel[t] = 0u;
+        if (pat[t] == 0xFFu) continue;
+        go0[t] = goff(g0[t]);
+        const uint32_t wo = (uint32_t)(((int64_t)slot * p.wpat_stride + (int64_t)pat[t] * p.F * 2) * 4), g1o = goff(g1[t]);
+        if (!any) { any = true; goff1 = g1o; wa = wb = wo; }
+        if (g1o != goff1) bad = 1u;
+        if (wo != wa) {
+            if (wb == wa) wb = wo;
+            else if (wo != wb) bad = 1u;
+            sel[t] = 1u;
+        }
+    }
+    sdesc[sl] = make_uint4(goff1, wa, wb, bad);
+#pragma unroll
+    for (int m = 0; m < MT; ++m) tdesc[sl * MT + m] = make_uint4(go0[2 * m], go0[2 * m + 1], sel[2 * m], sel[2 * m + 1]);
 }
 
 }  // namespace sbe
