@@ -901,7 +901,6 @@ MixGeom mix_geometry_v2(const sbe_engine* e, int P, int n_batch, int blocks_per_
         const size_t image = (size_t)e->tile_tab_elems() * sizeof(float) + (size_t)P * e->C * e->ft * sizeof(double);
         blocks_per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)blocks_per_cu, (160 * 1024) / (image + 4096)));
     }
-    if (const char* env = getenv("SBE_BLOCKS_PER_CU")) { if (atoi(env) > 0) blocks_per_cu = atoi(env); }   // experiments
     const int64_t target_blocks = (int64_t)blocks_per_cu * e->compute_units;
     int64_t chunks = std::max<int64_t>(1, target_blocks / ((int64_t)g.n_ftiles * std::max(1, n_batch)));
     const int min_quads = 4 * (kWave / e->ft);            // one step for each of the 4 waves
@@ -934,7 +933,7 @@ int check_slot_ready(sbe_engine* e, int slot, bool need_weights) {
 // 1 KB (tile NT and the PF fragments behind it are zero: what the kernel reads instead of branching on bounds).
 int ensure_xt(sbe_engine* e) {
     if (e->d_xt) return SBE_OK;
-    const int NT = div_up((int64_t)e->F * e->S, 32), KBp = round_up(div_up(e->N, tuple_mfma_kblock_objects()), 4);
+    const int NT = div_up((int64_t)e->F * e->S, 32), KBp = round_up(div_up(e->N, kTupleMfmaKBlockObjects), 4);
     const size_t bytes = ((size_t)(NT + 1) * KBp + 4) * 1024;
     // built into locals and published only when every step has succeeded: a caller that catches the first
     // error and retries gets the same error again, never a launch with half of this in place
@@ -950,7 +949,7 @@ int ensure_xt(sbe_engine* e) {
         HIPCHK(e, hipMemcpy(logtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
         launch_column_tables(e->d_state, reinterpret_cast<int32_t*>(logtab + 1024), e->N, e->F, e->S, e->Fp, NT, e->stream);
         HIPCHK(e, hipGetLastError());
-        launch_xt_frags(e->d_state, xt, e->N, e->F, e->S, e->Fp, NT, KBp, tuple_mfma_fp4(), e->stream);
+        launch_xt_frags(e->d_state, xt, e->N, e->F, e->S, e->Fp, NT, KBp, e->stream);
         HIPCHK(e, hipGetLastError());
         return SBE_OK;
     };
@@ -968,19 +967,12 @@ int ensure_xt(sbe_engine* e) {
 }
 
 // geometry of a matrix-pipe launch over n slots with at most KT tuples each; n_split = 0: the form does not apply
-struct MfmaGeom { int n_split, nt_per_split, MT, SL; size_t lds; bool ws, shared; };      // SL: slots per block (16 / 4 / 2)
-// the wave-specialised kernel (sbe_mixture_mfma_ws.hip): OPT-IN (SBE_MFMA_WS=1).  Measured on hardware it loses to the
-// unspecialised kernel at the headline shape (72.0 against 64.5 us per 4096 states, profiles/r6/ws_experiment.log); kept, tested
-// (tests/test_gpu_shapes.py::test_mfma_wave_specialised_form) and selectable for same-box comparisons.
-static bool mfma_ws_wanted() {
-    static const bool on = [] { const char* v = getenv("SBE_MFMA_WS"); return v && atoi(v) == 1; }();
-    return on;
-}
+struct MfmaGeom { int n_split, nt_per_split, MT, SL; size_t lds; bool shared; };      // SL: slots per block (16 / 4 / 2)
 MfmaGeom mfma_geometry(const sbe_engine* e, int n, int KT) {
     MfmaGeom g{};
     g.SL = tuple_mfma_slots_per_block(KT);           // 16 slots x <= 8 tuples, 4 x <= 32, 2 x <= 64 per block: the most KT allows
     if (g.SL == 0 || e->C > 4) return g;
-    const int NT = div_up((int64_t)e->F * e->S, 32), KBp = round_up(div_up(e->N, tuple_mfma_kblock_objects()), 4);
+    const int NT = div_up((int64_t)e->F * e->S, 32), KBp = round_up(div_up(e->N, kTupleMfmaKBlockObjects), 4);
     // Few states per launch: with 16 slots per block a launch of n states is ceil(n / 16) x (at most 4 column splits) blocks -- at
     // 512 states half the CUs idle and every block still walks a whole pass of MT M tiles (24.6 us at 256..1024 headline states).
     // Four slots per block (ONE M tile of <= 8 tuples x 4 slots) make four times the blocks of a third of the work per pass.  The
@@ -988,7 +980,7 @@ MfmaGeom mfma_geometry(const sbe_engine* e, int n, int KT) {
     // shape): 14.6 / 16.1 / 17.9 / 21.4 us at 32 / 256 / 320 / 512 states (1 / 1 / 2 / 2 units against 3) where k_mixture_tuple64
     // takes 16.0 / 21.1 / 26.5 / 35.1 us; at 576 states the four-slot form needs 4 units (30.6 us) and the 16-slot form stays
     // (24.6 us): profiles/r6/mfma_threshold.log
-    if (g.SL == 16 && tuple_mfma_fp4() && e->mfma_small_sl4) {
+    if (g.SL == 16 && e->mfma_small_sl4) {
         auto units = [&](int SL, int MT) -> int64_t {
             const int groups = div_up(n, SL);
             const int split = std::max(1, std::min(div_up(NT, 16), e->compute_units / std::max(1, groups)));
@@ -997,18 +989,13 @@ MfmaGeom mfma_geometry(const sbe_engine* e, int n, int KT) {
         };
         if (units(4, 1) < units(16, div_up(KT, 2))) g.SL = 4;
     }
-    if (const char* env = getenv("SBE_MFMA_SL")) { const int v = atoi(env); if ((v == 4 || v == 2) && v < g.SL && tuple_mfma_fp4()) g.SL = v; }   // experiments
-    // ... and fewer slots per block (FP4 operands) while the A image -- MT x KBp KB, MT = tuples x slots / 32 -- does not fit a
+    // ... and fewer slots per block while the A image -- MT x KBp KB, MT = tuples x slots / 32 -- does not fit a
     // CU's LDS: many objects with few tuples (5000 objects x 6 tuples: 16 slots need 3 x 80 KB, 4 slots 1 x 80 KB)
     for (;;) {
         g.MT = div_up(KT, 32 / g.SL);
         g.lds = tuple_mfma_lds_bytes(g.MT, e->C, KBp);
-        if (g.lds <= 160 * 1024 || g.SL == 2 || !tuple_mfma_fp4()) break;
+        if (g.lds <= 160 * 1024 || g.SL == 2) break;
         g.SL = g.SL == 16 ? 4 : 2;
-    }
-    if (g.SL == 16 && tuple_mfma_fp4() && mfma_ws_wanted() && tuple_mfma_ws_lds_bytes(g.MT, e->C, KBp) <= 160 * 1024) {
-        g.ws = true;
-        g.lds = tuple_mfma_ws_lds_bytes(g.MT, e->C, KBp);
     }
     if (g.lds > 160 * 1024) return g;
     // the tables are addressed through 32-bit buffer offsets
@@ -1056,7 +1043,7 @@ int launch_mfma_form(sbe_engine* e, int first_slot, int n, int KT, const MfmaGeo
     p.partials = e->d_partials; p.partials_stride = e->partials_stride;
     if (reduce_in_kernel) { p.results = e->d_results; p.arrive = e->d_arrive; p.done = done; }
     const dim3 grid((unsigned)(div_up(n, mg.SL) * mg.n_split));
-    if (!(mg.ws ? launch_tuple_mfma_ws(e->C, p, grid, mg.lds, e->stream) : launch_tuple_mfma(e->C, p, grid, mg.lds, e->stream)))
+    if (!launch_tuple_mfma(e->C, p, grid, mg.lds, e->stream))
         return fail(e, SBE_ERR_STATE, "k_mixture_tuple_mfma was built with static LDS: its log table must sit at LDS address 0 "
                                       "(toolchain change; rebuild without static __shared__ in sbe_mixture_mfma.hip)");
     return SBE_OK;
@@ -1104,10 +1091,10 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
     }
     // large batches: the per-observation gather as an integer contraction on the matrix pipe (k_mixture_tuple_mfma)
     MfmaGeom mg{};
-    // (default: from mfma_min_batch states per launch on whatever the shape, and -- FP4 operands, four slots per block -- from 32
-    //  states on when the launch holds enough observations for the kernel's fixed costs: 32 headline states = 6.4 M)
+    // (default: from mfma_min_batch states per launch on whatever the shape, and -- four slots per block -- from 32 states on
+    //  when the launch holds enough observations for the kernel's fixed costs: 32 headline states = 6.4 M)
     const bool mfma_default = e->opt_kernel == SBE_MIXTURE_PACKED &&
-                              (n >= e->mfma_min_batch || (tuple_mfma_fp4() && e->mfma_small_sl4 && n >= 32 && (int64_t)n * e->N * e->F >= e->mfma_min_obs));
+                              (n >= e->mfma_min_batch || (e->mfma_small_sl4 && n >= 32 && (int64_t)n * e->N * e->F >= e->mfma_min_obs));
     if (combo && (force_mfma || mfma_default)) {
         mg = mfma_geometry(e, n, KT);
         // The wide forms (more than 8 tuples: 4 / 2 slots per block) pay one log per (padded tuple, feature, state) where the
@@ -1116,9 +1103,9 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         if (!force_mfma && mg.n_split > 0 && KT > 8 && e->N < e->mfma_wide_min_share * mg.MT * (32 / mg.SL)) mg = MfmaGeom{};
     }
     const bool mfma = mg.n_split > 0;
-    // the shared-operand epilogue: C = 2, 16 FP4 slots per block, at most 3 M tiles (6 tuples; 4 tiles spill), every slot of
-    // the launch fitting it (per-slot flag)
-    if (mfma && e->C == 2 && mg.SL == 16 && mg.MT <= 3 && !mg.ws && tuple_mfma_fp4() && tuple_mfma_shared()) {
+    // the shared-operand epilogue: C = 2, 16 slots per block, at most 3 M tiles (6 tuples; 4 tiles spill), every slot of the
+    // launch fitting it (per-slot flag)
+    if (mfma && e->C == 2 && mg.SL == 16 && mg.MT <= 3 && tuple_mfma_shared()) {
         mg.shared = true;
         for (int i = 0; i < n && mg.shared; ++i) mg.shared = e->slots[slot_at(i)].share_ok;
     }
@@ -1201,8 +1188,7 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         // the chip; small images take two generations of blocks
         // (a block that stages a large image wants at least ~8 block steps of work behind it)
         const int64_t target = (int64_t)e->compute_units * (image > 72 * 1024 ? 1 : 2);
-        int min_steps = image > 72 * 1024 ? 8 : image > 24 * 1024 ? 4 : 1;
-        if (const char* env = getenv("SBE_ROWS_MIN_STEPS")) { if (atoi(env) > 0) min_steps = atoi(env); }   // experiments
+        const int min_steps = image > 72 * 1024 ? 8 : image > 24 * 1024 ? 4 : 1;
         int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(div_up(NQ_geo, (int64_t)gran * min_steps), div_up(target, (int64_t)n_t * n)));
         const int qpc = round_up(div_up(NQ_geo, chunks), gran);
         g.ft = rft; g.n_ftiles = n_t; g.objs_per_chunk = qpc; g.n_chunks = div_up(NQ_geo, qpc);
@@ -1255,7 +1241,7 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         if (done_out) *done_out = done_k;
     }
     if (mfma) {
-        snprintf(e->last_kernel, sizeof e->last_kernel, "k_mixture_tuple_mfma%s<packed stream, group-tuple form, matrix pipe %s, %d slots x M tiles %d, C=%d%s>", mg.ws ? "_ws" : "", tuple_mfma_fp4() ? "fp4" : "i8", mg.SL, mg.MT, e->C, mg.shared ? ", shared operands" : "");
+        snprintf(e->last_kernel, sizeof e->last_kernel, "k_mixture_tuple_mfma<packed stream, group-tuple form, matrix pipe fp4, %d slots x M tiles %d, C=%d%s>", mg.SL, mg.MT, e->C, mg.shared ? ", shared operands" : "");
         int rc = launch_mfma_form(e, first_slot, n, KT, mg, d_slots, mfma_reduce, done_k);
         if (rc) return rc;
     } else {
@@ -1287,7 +1273,6 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         p.ragged_w = (tuple64 && e->F % 64 != 0 && e->F % 64 <= 32) ? e->F % 64 : 0;
         if (combo && tuple64) {   // own block order (slots dealt to XCDs, generations, heavy work items first; see the kernel)
             p.gen_slots = std::max(1, (4 * e->compute_units / 8) / g.n_blocks);
-            if (const char* env = getenv("SBE_T64_GEN_SLOTS")) { if (atoi(env) > 0) p.gen_slots = atoi(env); }      // experiments: block order
             const int gens = div_up(div_up(n, 8), p.gen_slots);
             grid = n >= 8 ? dim3(8 * gens * p.gen_slots * g.n_blocks, 1) : dim3(n * g.n_blocks, 1);
         }
@@ -1300,18 +1285,8 @@ int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev
         p.rowoff = e->d_rowoff; p.rowoff_stride = (int64_t)(e->C + 1) * e->Np;
         p.rowoff_s = e->d_rowoff_s; p.rowoff_s_stride = (int64_t)e->rs_nq_max * (e->C + 1) * 4;
         p.rs_nq = e->d_rs_nq; p.state_s = e->d_state_s; p.state_s_pitch = e->Fq;
-        {   // shares of a rows block's steps by wave age class (see k_mixture_rows); SBE_ROWS_SPLIT="a,b,c,d" per mille
-            static int split[4] = {450, 270, 170, 110};
-            static bool parsed = false;
-            if (!parsed) {
-                parsed = true;
-                if (const char* env = getenv("SBE_ROWS_SPLIT")) {
-                    int v[4];
-                    if (sscanf(env, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] + v[1] + v[2] + v[3] == 1000 &&
-                        v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[3] >= 0)
-                        for (int i = 0; i < 4; ++i) split[i] = v[i];
-                }
-            }
+        {   // shares of a rows block's steps by wave age class (see k_mixture_rows), per mille
+            constexpr int split[4] = {450, 270, 170, 110};
             p.rows_cum[0] = 0;
             for (int i = 0; i < 4; ++i) p.rows_cum[i + 1] = p.rows_cum[i] + split[i];
         }

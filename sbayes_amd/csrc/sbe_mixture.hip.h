@@ -62,10 +62,10 @@ struct Mix2Params {
 // batched group-tuple form on the matrix pipe (sbe_mixture_mfma.hip: k_mixture_tuple_mfma)
 struct MfmaMixParams {
     int F, S, FS, Gtot, Np;
-    int NT, KBp;                                   // 32-column tiles of the (feature, state) axis; k-blocks of 64 (FP4 operands) / 32 (i8) objects, padded to a multiple of 4
+    int NT, KBp;                                   // 32-column tiles of the (feature, state) axis; k-blocks of 64 objects, padded to a multiple of 4
     int KT;                                        // tuples used by the slots of this launch (max; <= 64)
     int SL;                                        // slots per block: 16 (KT <= 8), 4 (<= 32) or 2 (<= 64) -- the widest whose A image fits LDS
-    int shared;                                    // 1: the shared-operand epilogue (C = 2, 16 slots, FP4; every slot fits it: host flag)
+    int shared;                                    // 1: the shared-operand epilogue (C = 2, 16 slots; every slot fits it: host flag)
     int n_batch, n_split, nt_per_split;            // slots of the launch; column splits (blocks per group of 16 slots); column tiles per split
     int first_slot;
     const int32_t* slot_list;                      // slots of this launch (n_batch entries), or null: first_slot + i
@@ -107,15 +107,11 @@ void launch_rowsort(const uint16_t* gid, const uint8_t* pid, uint32_t* out, int3
                     uint32_t row_bytes, uint32_t state_pitch, int step_objects, hipStream_t st);
 void launch_state_s(const uint8_t* state, uint8_t* state_s, int N, int F, int Fp, int pitch, int S, hipStream_t st);
 // sbe_mixture_mfma.hip
-bool tuple_mfma_fp4();                            // operand format of the count contraction: FP4 (default; a k-block = 64 objects) or i8 (32)
-inline int tuple_mfma_kblock_objects() { return tuple_mfma_fp4() ? 64 : 32; }
+constexpr int kTupleMfmaKBlockObjects = 64;       // objects per k-block of the FP4 count contraction
 int tuple_mfma_slots_per_block(int KT);           // 16 (KT <= 8) / 4 (<= 32) / 2 (<= 64): the MOST slots per block KT tuples allow; 0: the form does not apply
-void launch_xt_frags(const uint8_t* state, uint8_t* xt, int N, int F, int S, int Fp, int NT, int KBp, bool fp4, hipStream_t st);
+void launch_xt_frags(const uint8_t* state, uint8_t* xt, int N, int F, int S, int Fp, int NT, int KBp, hipStream_t st);
 size_t column_tables_bytes(int NT);               // colcount | colfeat | tile_prefix (MfmaMixParams), one allocation
 void launch_column_tables(const uint8_t* state, int32_t* out, int N, int F, int S, int Fp, int NT, hipStream_t st);
-// sbe_mixture_mfma_ws.hip: the wave-specialised form (producer waves count, consumer waves evaluate); FP4 operands only
-size_t tuple_mfma_ws_lds_bytes(int MT, int C, int KBp);
-bool launch_tuple_mfma_ws(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st);
 size_t tuple_mfma_lds_bytes(int MT, int C, int KBp);
 void fine_log_table(double* tab);                 // [2 * 1024] {1/c, log c} of k_mixture_tuple_mfma's log (sbe_mixture_mfma.hip)
 // false (nothing launched): an instance of the kernel carries static LDS, so its dynamic block does not start at address 0

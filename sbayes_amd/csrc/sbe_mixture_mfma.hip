@@ -10,8 +10,8 @@
 // belongs to.  Hence
 //     LL[b] = sum_{t, f, s} cnt_b[t][f][s] * T_b[t][f][s],      cnt_b[t][(f, s)] = sum_n [tid_b(n) = t] * X[n][(f, s)]
 // and cnt is a product of two 0/1 byte matrices: A[(b, t)][n] = [tid_b(n) = t] (built in LDS from the slots' tuple ids)
-// and X (the one-hot block, transposed once into MFMA fragment order: k_xt_frags).  v_mfma_i32_32x32x32_i8 accumulates it
-// exactly (counts <= N fit i32), the table entry is computed ONCE per (slot, tuple, feature, state) in the lane that holds
+// and X (the one-hot block, transposed once into MFMA fragment order: k_xt_frags).  The matrix pipe accumulates it
+// exactly (see the operand format below), the table entry is computed ONCE per (slot, tuple, feature, state) in the lane that holds
 // its count -- same products, same NumPy order of the component sum, same table-driven fp64 log as the other forms -- and
 // never goes through LDS.  NA observations have an all-zero one-hot row and are counted nowhere.
 //
@@ -22,14 +22,15 @@
 // 1 KB fully coalesced pieces (fragment order in memory), four k-blocks ahead.  Both operands take their k index from the
 // same (lane half, byte) position, so the product does not depend on the instruction's internal k order.
 //
-// Operand format (round 6): FP4.  0 and 1.0 are exact in e2m1 (0x0, 0x2) and a count <= N < 2^24 is exact in an f32 accumulator, so
-// v_mfma_f32_32x32x64_f8f6f4 (cbsz = blgp = 4, scale operands 0: the unscaled form) computes the SAME integers at twice the i8
-// instruction's depth for the same issue time (tools/probe/mfma_fp4_probe.hip: 35.1 against 35.1 counter ticks per instruction,
-// all 1024 outputs of an asymmetric 0/1 contraction exact): half the MFMAs, half the A image in LDS (48 KB instead of 96 KB at the
-// headline shape: N up to ~2 900 fits), half the X-fragment bytes from L2.  A k-block is then 64 objects; a lane's 16 bytes hold
+// Operand format: FP4.  0 and 1.0 are exact in e2m1 (0x0, 0x2) and a count <= N < 2^24 is exact in an f32 accumulator, so
+// v_mfma_f32_32x32x64_f8f6f4 (cbsz = blgp = 4, scale operands 0: the unscaled form) computes the counts exactly at twice the depth
+// of round 5's v_mfma_i32_32x32x32_i8 for the same issue time (tools/probe/mfma_fp4_probe.hip: 35.1 against 35.1 counter ticks
+// per instruction, all 1024 outputs of an asymmetric 0/1 contraction exact): half the MFMAs, half the A image in LDS (48 KB
+// instead of 96 KB at the headline shape: N up to ~2 900 fits), half the X-fragment bytes from L2 (76.3 -> 66.5 us:
+// profiles/r6/ab_fp4_and_epilogue.log; the i8 form has since been removed).  A k-block is 64 objects; a lane's 16 bytes hold
 // 32 nibbles, byte b of dword w: low nibble = object 8 w + b, high nibble = object 8 w + 4 + b of the lane half's 32 objects --
 // the order in which the A build gets them out of the tuple-id bytes with two shifts; the X fragments (k_xt_frags) use the same
-// one.  The i8 form stays selectable (SBE_MFMA_FP4=0) for same-box comparisons; both are oracle-checked.
+// one.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -42,39 +43,27 @@
 
 namespace sbe {
 
-constexpr int kMfmaWaves = 8;
-constexpr int kMfmaThreads = kMfmaWaves * kWave;
 constexpr int kMfmaRN = kTupleMfmaColsPerPass;   // column tiles per wave pass (2; the host's overflow bound uses the same constant)
 // (Other block shapes were measured in round 5 and lost: 16 waves x 1 column tile at 128 registers, +9 %; 8 waves x 1 tile with
 //  the next tile's MFMAs issued inside the epilogue, +7 %: profiles/r5/mfma_kernel_experiments_session2.log.)
 
-// One-hot block -> fragment order.  i8 operands: fragment (nt, kb): lane l holds bytes j = 0..15 = X[n = 32 kb + 16 (l >> 5) + j]
-// [col = 32 nt + (l & 31)] with col = f * S + s.  FP4 operands: a k-block is 64 objects; lane l holds 32 nibbles (1.0 = 0x2) of
-// the objects n0 = 64 kb + 32 (l >> 5) + ..: byte b of dword w, low nibble = object n0 + 8 w + b, high nibble = n0 + 8 w + 4 + b.
-// Zero for n >= N, col >= F * S and NA observations.
+// One-hot block -> fragment order.  Fragment (nt, kb) covers the columns col = 32 nt + (l & 31) = f * S + s and the 64 objects of
+// k-block kb: lane l holds 32 nibbles (1.0 = 0x2) of the objects n0 = 64 kb + 32 (l >> 5) + ..: byte b of dword w, low nibble =
+// object n0 + 8 w + b, high nibble = n0 + 8 w + 4 + b.  Zero for n >= N, col >= F * S and NA observations.
 __global__ void k_xt_frags(const uint8_t* __restrict__ state /* [N][Fp], 0xFF = NA */, uint8_t* __restrict__ xt,
-                           int N, int F, int S, int Fp, int NT, int KBp, int fp4) {
+                           int N, int F, int S, int Fp, int NT, int KBp) {
     const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= (int64_t)NT * KBp * 64) return;
     const int l = (int)(u & 63), kb = (int)((u >> 6) % KBp), nt = (int)((u >> 6) / KBp);
     const int col = nt * 32 + (l & 31), f = col / S, s = col - f * S;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (col < F * S) {
-        if (fp4) {
-            const int n0 = kb * 64 + 32 * (l >> 5);
+        const int n0 = kb * 64 + 32 * (l >> 5);
 #pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                const int n = n0 + 8 * (j >> 3) + (j & 7);                     // object j of the lane half, in order
-                const int b = j & 3, hi = (j >> 2) & 1;                       // -> byte b of dword j >> 3, low / high nibble
-                if (n < N && state[(int64_t)n * Fp + f] == (uint8_t)s) w[j >> 3] |= 0x2u << (8 * b + 4 * hi);
-            }
-        } else {
-            const int n0 = kb * 32 + 16 * (l >> 5);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int n = n0 + j;
-                if (n < N && state[(int64_t)n * Fp + f] == (uint8_t)s) w[j >> 2] |= 1u << (8 * (j & 3));
-            }
+        for (int j = 0; j < 32; ++j) {
+            const int n = n0 + 8 * (j >> 3) + (j & 7);                         // object j of the lane half, in order
+            const int b = j & 3, hi = (j >> 2) & 1;                           // -> byte b of dword j >> 3, low / high nibble
+            if (n < N && state[(int64_t)n * Fp + f] == (uint8_t)s) w[j >> 3] |= 0x2u << (8 * b + 4 * hi);
         }
     }
     reinterpret_cast<uint4*>(xt)[u] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -116,9 +105,9 @@ void launch_column_tables(const uint8_t* state, int32_t* out, int N, int F, int 
     k_tile_prefix<<<1, 64, 0, st>>>(colcount, tile_prefix, NT);
 }
 
-void launch_xt_frags(const uint8_t* state, uint8_t* xt, int N, int F, int S, int Fp, int NT, int KBp, bool fp4, hipStream_t st) {
+void launch_xt_frags(const uint8_t* state, uint8_t* xt, int N, int F, int S, int Fp, int NT, int KBp, hipStream_t st) {
     const int64_t units = (int64_t)NT * KBp * 64;
-    k_xt_frags<<<(unsigned)((units + 255) / 256), 256, 0, st>>>(state, xt, N, F, S, Fp, NT, KBp, fp4 ? 1 : 0);
+    k_xt_frags<<<(unsigned)((units + 255) / 256), 256, 0, st>>>(state, xt, N, F, S, Fp, NT, KBp);
 }
 
 // the table of tab_log4_n (host side: ensure_xt uploads it)
@@ -136,10 +125,10 @@ void fine_log_table(double* tab /* [2 * kFineLogEntries] */) {
 // SLB = log2(slots per block): 4 (16 slots x <= 8 tuples: the form of round 5), 2 (4 slots x <= 32 tuples), 1 (2 slots x <= 64 tuples:
 // the whole tuple table) -- an M tile's 32 rows are 32 / SL tuples x SL slots (row = (tuple in tile) * SL + slot), so a block of
 // MT <= 4 tiles holds MT * 32 / SL tuples.  The wide forms (round 6) put datasets with several confounders on the matrix pipe.
-// SHARE: the shared-operand epilogue (16 slots, C = 2, FP4; see the epilogue below).
-template <int MT, int CT, int GT = 4, bool FP4 = true, int SLB = 4, bool SHARE = false>
+// SHARE: the shared-operand epilogue (16 slots, C = 2; see the epilogue below).
+template <int MT, int CT, int GT = 4, int SLB = 4, bool SHARE = false>
 __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixParams p) {
-    typedef typename std::conditional<FP4, v16f_t, v16i_t>::type acc_t;      // counts: exact integers either way
+    typedef v16f_t acc_t;                                                    // counts: exact integers in f32
     constexpr int SL = 1 << SLB, TPT = 32 / SL, TPB = MT * TPT;              // slots per block; tuples per M tile / per block
     constexpr int NK = SL == 16 ? 8 : SL;                                    // slots a lane sums for
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -199,9 +188,9 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         return;
     }
     // ---- phase 0: tuple metadata, log table, A fragments (sbe_mixture_mfma.hip.h) -----------------------------------------
-    mfma_phase0<MT, CT, FP4, kMfmaThreads, decltype(slot_of), SL, !SHARE>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp);
+    mfma_phase0<MT, CT, decltype(slot_of), SL, !SHARE>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp);
     // shared-operand form: the slot and step descriptors take the place of the per-tuple metadata (256 + 256 MT <= 512 MT bytes)
-    static_assert(!SHARE || (SL == 16 && CT == 2 && FP4 && MT <= 3), "the shared-operand epilogue: 16 slots, C = 2, FP4 operands, <= 6 tuples");
+    static_assert(!SHARE || (SL == 16 && CT == 2 && MT <= 3), "the shared-operand epilogue: 16 slots, C = 2, <= 6 tuples");
     const uint4* sdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off);
     const uint4* tdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off + SL * 16);
     if constexpr (SHARE) mfma_shared_desc<MT, SL>(p, slot_of, const_cast<uint4*>(sdesc), const_cast<uint4*>(tdesc));
@@ -259,15 +248,12 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
-                    for (int r = 0; r < kMfmaRN; ++r)
-                        if constexpr (FP4) {
-                            // (an FP4 operand is the first four registers of the eight-register operand)
-                            const v8i_t a8 = {a_cur[m].x, a_cur[m].y, a_cur[m].z, a_cur[m].w, 0, 0, 0, 0};
-                            const v8i_t b8 = {b[r].x, b[r].y, b[r].z, b[r].w, 0, 0, 0, 0};
-                            acc[m][r] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[m][r], 4, 4, 0, 0, 0, 0);
-                        } else {
-                            acc[m][r] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a_cur[m], b[r], acc[m][r], 0, 0, 0);
-                        }
+                    for (int r = 0; r < kMfmaRN; ++r) {
+                        // (an FP4 operand is the first four registers of the eight-register operand)
+                        const v8i_t a8 = {a_cur[m].x, a_cur[m].y, a_cur[m].z, a_cur[m].w, 0, 0, 0, 0};
+                        const v8i_t b8 = {b[r].x, b[r].y, b[r].z, b[r].w, 0, 0, 0, 0};
+                        acc[m][r] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[m][r], 4, 4, 0, 0, 0, 0);
+                    }
 #pragma unroll
                 for (int m = 0; m < MT; ++m) a_cur[m] = a_nxt[m];
                 __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);                 // the next k-block's A fragments
@@ -337,12 +323,8 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         bool special = false;
 #pragma unroll
         for (int i = 0; i < G; ++i) {
-            if constexpr (FP4) {
-                const float c = acc[m][r][4 * j + half * G + i];          // an exact integer <= N
-                cnt[i] = (int)c; cntd[i] = (double)c;
-            } else {
-                cnt[i] = acc[m][r][4 * j + half * G + i]; cntd[i] = (double)cnt[i];
-            }
+            const float c = acc[m][r][4 * j + half * G + i];              // an exact integer <= N
+            cnt[i] = (int)c; cntd[i] = (double)c;
             // sum_c w_c * p_c in NumPy's order.  The product of two float32 values is exact in fp64, so fma(w, p, v)
             // rounds exactly like the reference's multiply-then-add: the same bits as the other kernel forms
             double v = 0.0;
@@ -617,50 +599,44 @@ size_t tuple_mfma_lds_bytes(int MT, int C, int KBp) {     // log table | A fragm
 // entries per epilogue step: a whole register quad where the registers allow it, half a quad for the widest instances
 template <int MT, int CT> constexpr int mfma_gt() { return (MT >= 4 || (MT == 3 && CT >= 3)) ? 2 : 4; }
 
-template <int MT, bool FP4, int SLB>
+template <int MT, int SLB>
 static void launch_mfma_mt(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
     switch (C) {
-        case 1: k_mixture_tuple_mfma<MT, 1, mfma_gt<MT, 1>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
+        case 1: k_mixture_tuple_mfma<MT, 1, mfma_gt<MT, 1>(), SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
         case 2:
-            if constexpr (FP4 && SLB == 4 && MT <= 3) {          // (MT = 4 spills: 37 VGPRs over 256)
-                if (p.shared) { k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), FP4, SLB, true><<<grid, kMfmaThreads, lds, st>>>(p); break; }
+            if constexpr (SLB == 4 && MT <= 3) {                 // (MT = 4 spills: 37 VGPRs over 256)
+                if (p.shared) { k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), SLB, true><<<grid, kMfmaThreads, lds, st>>>(p); break; }
             }
-            k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p);
+            k_mixture_tuple_mfma<MT, 2, mfma_gt<MT, 2>(), SLB><<<grid, kMfmaThreads, lds, st>>>(p);
             break;
-        case 3: k_mixture_tuple_mfma<MT, 3, mfma_gt<MT, 3>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
-        default: k_mixture_tuple_mfma<MT, 4, mfma_gt<MT, 4>(), FP4, SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
+        case 3: k_mixture_tuple_mfma<MT, 3, mfma_gt<MT, 3>(), SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
+        default: k_mixture_tuple_mfma<MT, 4, mfma_gt<MT, 4>(), SLB><<<grid, kMfmaThreads, lds, st>>>(p); break;
     }
 }
 
 // one-time: the kernels ask for up to the whole 160 KB of a CU's LDS.  The log table's index is its whole LDS address
 // (tab_off = 0), which holds only while the kernel has NO static LDS: checked here, once, on the host -- the guard inside the
 // kernel would store NaNs but not take its completion tickets, and a host-synchronous caller would wait for them.
-template <int MT, int CT, bool FP4, int SLB, bool SHARE = false>
+template <int MT, int CT, int SLB, bool SHARE = false>
 static bool allow_lds() {
-    const void* fn = reinterpret_cast<const void*>(&k_mixture_tuple_mfma<MT, CT, mfma_gt<MT, CT>(), FP4, SLB, SHARE>);
+    const void* fn = reinterpret_cast<const void*>(&k_mixture_tuple_mfma<MT, CT, mfma_gt<MT, CT>(), SLB, SHARE>);
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncAttributes attr{};
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) { (void)hipGetLastError(); return true; }   // (not answerable: the kernel's own guard stays)
     return attr.sharedSizeBytes == 0;
 }
 
-template <bool FP4, int SLB>
+template <int SLB>
 static bool allow_lds_all() {
     bool ok = true;
-    ok &= allow_lds<1, 1, FP4, SLB>(); ok &= allow_lds<1, 2, FP4, SLB>(); ok &= allow_lds<1, 3, FP4, SLB>(); ok &= allow_lds<1, 4, FP4, SLB>();
-    ok &= allow_lds<2, 1, FP4, SLB>(); ok &= allow_lds<2, 2, FP4, SLB>(); ok &= allow_lds<2, 3, FP4, SLB>(); ok &= allow_lds<2, 4, FP4, SLB>();
-    ok &= allow_lds<3, 1, FP4, SLB>(); ok &= allow_lds<3, 2, FP4, SLB>(); ok &= allow_lds<3, 3, FP4, SLB>(); ok &= allow_lds<3, 4, FP4, SLB>();
-    ok &= allow_lds<4, 1, FP4, SLB>(); ok &= allow_lds<4, 2, FP4, SLB>(); ok &= allow_lds<4, 3, FP4, SLB>(); ok &= allow_lds<4, 4, FP4, SLB>();
-    if constexpr (FP4 && SLB == 4) {
-        ok &= allow_lds<1, 2, FP4, SLB, true>(); ok &= allow_lds<2, 2, FP4, SLB, true>(); ok &= allow_lds<3, 2, FP4, SLB, true>();
+    ok &= allow_lds<1, 1, SLB>(); ok &= allow_lds<1, 2, SLB>(); ok &= allow_lds<1, 3, SLB>(); ok &= allow_lds<1, 4, SLB>();
+    ok &= allow_lds<2, 1, SLB>(); ok &= allow_lds<2, 2, SLB>(); ok &= allow_lds<2, 3, SLB>(); ok &= allow_lds<2, 4, SLB>();
+    ok &= allow_lds<3, 1, SLB>(); ok &= allow_lds<3, 2, SLB>(); ok &= allow_lds<3, 3, SLB>(); ok &= allow_lds<3, 4, SLB>();
+    ok &= allow_lds<4, 1, SLB>(); ok &= allow_lds<4, 2, SLB>(); ok &= allow_lds<4, 3, SLB>(); ok &= allow_lds<4, 4, SLB>();
+    if constexpr (SLB == 4) {
+        ok &= allow_lds<1, 2, SLB, true>(); ok &= allow_lds<2, 2, SLB, true>(); ok &= allow_lds<3, 2, SLB, true>();
     }
     return ok;
-}
-
-// operand format of the count contraction: FP4 (default) or i8 (SBE_MFMA_FP4=0: same-box comparisons); fixed for the process
-bool tuple_mfma_fp4() {
-    static const bool on = [] { const char* v = getenv("SBE_MFMA_FP4"); return !(v && atoi(v) == 0); }();
-    return on;
 }
 
 // the shared-operand epilogue where the host finds that it applies (default), or never (SBE_MFMA_SHARED=0: same-box comparisons
@@ -670,36 +646,30 @@ bool tuple_mfma_shared() {
     return on;
 }
 
-// slots per block for KT tuples (0: the form does not apply): 16 up to 8 tuples, 4 up to 32, 2 up to 64 -- the wide forms with FP4
-// operands only
+// slots per block for KT tuples (0: the form does not apply): 16 up to 8 tuples, 4 up to 32, 2 up to 64
 int tuple_mfma_slots_per_block(int KT) {
     if (KT < 1 || KT > 64) return 0;
-    if (KT <= 8) return 16;
-    if (!tuple_mfma_fp4()) return 0;
-    return KT <= 32 ? 4 : 2;
+    return KT <= 8 ? 16 : KT <= 32 ? 4 : 2;
 }
 
-template <bool FP4, int SLB>
+template <int SLB>
 static void launch_mfma_slb(int MT, int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
     switch (MT) {
-        case 1: launch_mfma_mt<1, FP4, SLB>(C, p, grid, lds, st); break;
-        case 2: launch_mfma_mt<2, FP4, SLB>(C, p, grid, lds, st); break;
-        case 3: launch_mfma_mt<3, FP4, SLB>(C, p, grid, lds, st); break;
-        default: launch_mfma_mt<4, FP4, SLB>(C, p, grid, lds, st); break;
+        case 1: launch_mfma_mt<1, SLB>(C, p, grid, lds, st); break;
+        case 2: launch_mfma_mt<2, SLB>(C, p, grid, lds, st); break;
+        case 3: launch_mfma_mt<3, SLB>(C, p, grid, lds, st); break;
+        default: launch_mfma_mt<4, SLB>(C, p, grid, lds, st); break;
     }
 }
 
 bool launch_tuple_mfma(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
-    const bool fp4 = tuple_mfma_fp4();
-    static const bool no_static_lds = tuple_mfma_fp4() ? (allow_lds_all<true, 4>() & allow_lds_all<true, 2>() & allow_lds_all<true, 1>())
-                                                       : allow_lds_all<false, 4>();
+    static const bool no_static_lds = [] { bool ok = allow_lds_all<4>(); ok &= allow_lds_all<2>(); ok &= allow_lds_all<1>(); return ok; }();
     if (!no_static_lds) return false;
     const int SL = p.SL;                                 // (chosen by the host: mfma_geometry)
     const int MT = (p.KT + 32 / SL - 1) / (32 / SL);
-    if (!fp4) launch_mfma_slb<false, 4>(MT, C, p, grid, lds, st);
-    else if (SL == 16) launch_mfma_slb<true, 4>(MT, C, p, grid, lds, st);
-    else if (SL == 4) launch_mfma_slb<true, 2>(MT, C, p, grid, lds, st);
-    else launch_mfma_slb<true, 1>(MT, C, p, grid, lds, st);
+    if (SL == 16) launch_mfma_slb<4>(MT, C, p, grid, lds, st);
+    else if (SL == 4) launch_mfma_slb<2>(MT, C, p, grid, lds, st);
+    else launch_mfma_slb<1>(MT, C, p, grid, lds, st);
     return true;
 }
 

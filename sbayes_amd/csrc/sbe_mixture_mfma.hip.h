@@ -1,21 +1,20 @@
-// sbe_mixture_mfma.hip.h -- what the two matrix-pipe kernels of the batched group-tuple form share (sbe_mixture_mfma.hip:
-// k_mixture_tuple_mfma, every wave counts and evaluates; sbe_mixture_mfma_ws.hip: k_mixture_tuple_mfma_ws, producer waves count,
-// consumer waves evaluate): fragment types, the table-driven log, the tuple metadata and phase 0 of a block (metadata, log
-// table and the A fragments -- the indicator image [tid == t] of the block's 16 slots -- into LDS).
+// sbe_mixture_mfma.hip.h -- pieces of the matrix-pipe kernel of the batched group-tuple form (sbe_mixture_mfma.hip:
+// k_mixture_tuple_mfma): fragment types, the block shape, the table-driven log, the tuple metadata, phase 0 of a block (metadata,
+// log table and the A fragments -- the indicator image [tid == t] of the block's slots -- into LDS) and the descriptors of the
+// shared-operand epilogue.
 #pragma once
-#include <type_traits>
-
 #include "sbe_mixture.hip.h"
 
 namespace sbe {
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v8i_t __attribute__((ext_vector_type(8)));
-typedef int v16i_t __attribute__((ext_vector_type(16)));
 typedef float v16f_t __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const v4i_t lds_cv4i_t;
 
 constexpr int kMfmaSlots = 16;          // slots per block in the narrow form (<= 8 tuples); wide forms: 4 (<= 32 tuples), 2 (<= 64)
+constexpr int kMfmaWaves = 8;
+constexpr int kMfmaThreads = kMfmaWaves * kWave;
 
 // Table-driven log for this kernel's epilogue, G chains interleaved: log v = k ln2 + log c_i + log1p(r), r = m / c_i - 1, with
 // its own FINER table (kFineLogEntries = 1024 intervals of the mantissa m in [1, 2): {RN(1/c_i) / 2, log c_i}, built by ensure_xt) so
@@ -77,20 +76,18 @@ struct __attribute__((aligned(CT <= 1 ? 8 : (CT <= 3 ? 16 : 32)))) TupleMeta {
     uint32_t goff[CT];
 };
 
-// Phase 0 of a block of NTHR threads (all of them call it; the caller's barrier follows): tuple metadata, log table, A fragments.
+// Phase 0 of a block (all kMfmaThreads threads call it; the caller's barrier follows): tuple metadata, log table, A fragments.
 // `slot_of(sl)`: absolute slot of the block's sl-th slot, or -1.  LDS: log table at tab_off (= 0), A fragments from a_off,
 // metadata at `meta`.
 // SL = slots per block (16 / 4 / 2): an M tile's 32 rows are 32 / SL tuples x SL slots, row = (tuple in tile) * SL + slot; the
 // block holds TPB = MT * 32 / SL tuples.
 // META = false: no per-tuple metadata (the shared-operand epilogue reads its own descriptors: mfma_shared_desc).
-template <int MT, int CT, bool FP4, int NTHR, typename SlotOf, int SL = kMfmaSlots, bool META = true>
+template <int MT, int CT, typename SlotOf, int SL = kMfmaSlots, bool META = true>
 __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMixParams& p, const SlotOf& slot_of, uint32_t tab_off,
                                             uint32_t a_off, TupleMeta<CT>* meta, int KBp) {
     typedef TupleMeta<CT> Meta;
-    constexpr int kMfmaThreads = NTHR;
     constexpr int TPT = 32 / SL, TPB = MT * TPT;                  // tuples per M tile / per block
     static_assert(SL == 16 || SL == 4 || SL == 2, "slots per block");
-    static_assert(!(SL != 16 && !FP4), "the wide forms exist with FP4 operands only");
     // ---- phase 0: tuple metadata, log table, A fragments ------------------------------------------------------------
     // Offsets of a tuple that is not there (another slot's tuple, the padding tuple of an odd KT, a slot beyond the batch)
     // and of a component the tuple has no group in point at the rows of ONES behind the two arrays: no observation is
@@ -111,141 +108,83 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
         }
         return md;
     };
-    if constexpr (FP4) {
-        // one unit = the 32 tuple ids of (slot sl, lane half h of k-block kb: 32 objects) -> the 2 MT indicator pieces (16 bytes =
-        // 32 nibbles each).  UB units' ids are asked for together.
-        const int n_units = SL * KBp * 2;
-        constexpr int UB = 2;
-        uint32_t d[UB][8];
-        auto load_ids = [&](int u0) {
+    // one unit = the 32 tuple ids of (slot sl, lane half h of k-block kb: 32 objects) -> the 2 MT indicator pieces (16 bytes =
+    // 32 nibbles each).  UB units' ids are asked for together.
+    const int n_units = SL * KBp * 2;
+    constexpr int UB = 2;
+    uint32_t d[UB][8];
+    auto load_ids = [&](int u0) {
 #pragma unroll
-            for (int k = 0; k < UB; ++k) {
-                const int u = u0 + k * kMfmaThreads;
-                const int sl = u % SL, n0 = (u / SL) * 32;     // (u / SL) = kb * 2 + h
-                const int slot = u < n_units ? slot_of(sl) : -1;
+        for (int k = 0; k < UB; ++k) {
+            const int u = u0 + k * kMfmaThreads;
+            const int sl = u % SL, n0 = (u / SL) * 32;     // (u / SL) = kb * 2 + h
+            const int slot = u < n_units ? slot_of(sl) : -1;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    d[k][i] = 0xFFFFFFFFu;                                        // matches no tuple
-                    if (slot >= 0 && n0 + 4 * i + 4 <= p.Np)
-                        d[k][i] = *reinterpret_cast<const uint32_t*>(p.tid + (int64_t)slot * p.tid_stride + n0 + 4 * i);
-                }
+            for (int i = 0; i < 8; ++i) {
+                d[k][i] = 0xFFFFFFFFu;                                        // matches no tuple
+                if (slot >= 0 && n0 + 4 * i + 4 <= p.Np)
+                    d[k][i] = *reinterpret_cast<const uint32_t*>(p.tid + (int64_t)slot * p.tid_stride + n0 + 4 * i);
             }
-        };
-        auto emit = [&](int u0) {
+        }
+    };
+    auto emit = [&](int u0) {
 #pragma unroll
-            for (int k = 0; k < UB; ++k) {
-                const int u = u0 + k * kMfmaThreads;
-                if (u >= n_units) break;
-                const int sl = u % SL, hk = u / SL;
-                const int kb = hk >> 1, h = hk & 1;
+        for (int k = 0; k < UB; ++k) {
+            const int u = u0 + k * kMfmaThreads;
+            if (u >= n_units) break;
+            const int sl = u % SL, hk = u / SL;
+            const int kb = hk >> 1, h = hk & 1;
 #pragma unroll 8
-                for (int t = 0; t < TPB; ++t) {
-                    uint4 o;
-                    uint32_t* ov = reinterpret_cast<uint32_t*>(&o);
+            for (int t = 0; t < TPB; ++t) {
+                uint4 o;
+                uint32_t* ov = reinterpret_cast<uint32_t*>(&o);
 #pragma unroll
-                    for (int wv = 0; wv < 4; ++wv) {
-                        uint32_t eq[2];
+                for (int wv = 0; wv < 4; ++wv) {
+                    uint32_t eq[2];
 #pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const uint32_t x = d[k][2 * wv + q] ^ ((uint32_t)t * 0x01010101u);
-                            const uint32_t nz = ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;      // bit 7 of a byte: byte != 0
-                            eq[q] = (~nz >> 7) & 0x01010101u;
-                        }
-                        ov[wv] = (eq[0] << 1) | (eq[1] << 5);       // 1.0 = 0x2: low nibbles = objects 8 wv + b, high = 8 wv + 4 + b
-                    }
-                    // fragment (m = t / TPT, kb): lane = h * 32 + row, row = (t % TPT) * SL + sl
-                    const uint32_t fl = (uint32_t)(h * 32 + (t % TPT) * SL + sl);
-                    *reinterpret_cast<uint4*>(lds_raw + a_off + (((uint32_t)(t / TPT) * (uint32_t)KBp + (uint32_t)kb) * 64u + fl) * 16u) = o;
-                }
-            }
-        };
-        const int u_first = (int)threadIdx.x;
-        load_ids(u_first);
-        constexpr int LT = (2 * kFineLogEntries + kMfmaThreads - 1) / kMfmaThreads;
-        double lt[LT];
-#pragma unroll
-        for (int k = 0; k < LT; ++k) {
-            const int i = (int)threadIdx.x + k * kMfmaThreads;
-            lt[k] = i < 2 * kFineLogEntries ? reinterpret_cast<const double*>(p.logtab)[i] : 0.0;
-        }
-        const bool has_meta = META && (int)threadIdx.x < SL * TPB;
-        const int m_sl = (int)threadIdx.x / TPB, m_t = (int)threadIdx.x % TPB;
-        const int m_slot = has_meta ? slot_of(m_sl) : -1;
-        uint32_t m_pat = 0xFFu, m_g[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) m_g[c] = 0xFFFFFFFFu;
-        if (m_slot >= 0) {                                   // (m_t < TPB <= kMaxTuples: the rows exist whatever KT is)
-            m_pat = p.tuple_p[(int64_t)m_slot * p.tuple_p_stride + m_t];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) m_g[c] = p.tuple_g[(int64_t)m_slot * p.tuple_g_stride + m_t * kMaxComponents + c];
-        }
-        if (has_meta) meta[m_sl * TPB + m_t] = meta_of(m_slot, m_t, m_pat, m_g);
-        (void)meta;
-#pragma unroll
-        for (int k = 0; k < LT; ++k) {
-            const int i = (int)threadIdx.x + k * kMfmaThreads;
-            if (i < 2 * kFineLogEntries) reinterpret_cast<double*>(lds_raw + tab_off)[i] = lt[k];
-        }
-        for (int u0 = u_first; u0 < n_units; u0 += UB * kMfmaThreads) {
-            if (u0 != u_first) load_ids(u0);
-            emit(u0);
-        }
-    } else {
-        if ((int)threadIdx.x < kMfmaSlots * 2 * MT) {
-            const int sl = (int)threadIdx.x / (2 * MT), t = (int)threadIdx.x % (2 * MT);
-            const int slot = slot_of(sl);
-            uint32_t pat = 0xFFu, g[CT];
-#pragma unroll
-            for (int c = 0; c < CT; ++c) g[c] = 0xFFFFFFFFu;
-            if (slot >= 0) {
-                pat = p.tuple_p[(int64_t)slot * p.tuple_p_stride + t];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) g[c] = p.tuple_g[(int64_t)slot * p.tuple_g_stride + t * kMaxComponents + c];
-            }
-            meta[sl * 2 * MT + t] = meta_of(slot, t, pat, g);
-        }
-        for (int i = (int)threadIdx.x; i < 2 * kFineLogEntries; i += kMfmaThreads)
-            reinterpret_cast<double*>(lds_raw + tab_off)[i] = reinterpret_cast<const double*>(p.logtab)[i];
-        // one unit = the 16 tuple ids of (slot sl, 16 objects) -> the 2 MT indicator pieces of those objects.  The ids of
-        // UB units are asked for together (a unit at a time the block's start is four dependent trips to L2 / HBM)
-        const int n_units = kMfmaSlots * KBp * 2;
-        constexpr int UB = 4;
-        for (int u0 = (int)threadIdx.x; u0 < n_units; u0 += UB * kMfmaThreads) {
-            uint32_t d[UB][4];
-#pragma unroll
-            for (int k = 0; k < UB; ++k) {
-                const int u = u0 + k * kMfmaThreads;
-                const int sl = u & 15, n0 = (u >> 4) * 16;     // (u >> 4) = kb * 2 + h
-                const int slot = u < n_units ? slot_of(sl) : -1;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    d[k][i] = 0xFFFFFFFFu;                                        // matches no tuple
-                    if (slot >= 0 && n0 + 4 * i + 4 <= p.Np)
-                        d[k][i] = *reinterpret_cast<const uint32_t*>(p.tid + (int64_t)slot * p.tid_stride + n0 + 4 * i);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < UB; ++k) {
-                const int u = u0 + k * kMfmaThreads;
-                if (u >= n_units) break;
-                const int sl = u & 15, hk = u >> 4;
-                const int kb = hk >> 1, h = hk & 1;
-#pragma unroll
-                for (int t = 0; t < 2 * MT; ++t) {
-                    uint4 o;
-                    uint32_t* ov = reinterpret_cast<uint32_t*>(&o);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const uint32_t x = d[k][i] ^ ((uint32_t)t * 0x01010101u);
+                    for (int q = 0; q < 2; ++q) {
+                        const uint32_t x = d[k][2 * wv + q] ^ ((uint32_t)t * 0x01010101u);
                         const uint32_t nz = ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;      // bit 7 of a byte: byte != 0
-                        ov[i] = (~nz >> 7) & 0x01010101u;
+                        eq[q] = (~nz >> 7) & 0x01010101u;
                     }
-                    // fragment (m = t >> 1, kb): lane = h * 32 + (t & 1) * 16 + sl
-                    const uint32_t fl = (uint32_t)(h * 32 + (t & 1) * 16 + sl);
-                    *reinterpret_cast<uint4*>(lds_raw + a_off + (((uint32_t)(t >> 1) * (uint32_t)KBp + (uint32_t)kb) * 64u + fl) * 16u) = o;
+                    ov[wv] = (eq[0] << 1) | (eq[1] << 5);       // 1.0 = 0x2: low nibbles = objects 8 wv + b, high = 8 wv + 4 + b
                 }
+                // fragment (m = t / TPT, kb): lane = h * 32 + row, row = (t % TPT) * SL + sl
+                const uint32_t fl = (uint32_t)(h * 32 + (t % TPT) * SL + sl);
+                *reinterpret_cast<uint4*>(lds_raw + a_off + (((uint32_t)(t / TPT) * (uint32_t)KBp + (uint32_t)kb) * 64u + fl) * 16u) = o;
             }
         }
+    };
+    const int u_first = (int)threadIdx.x;
+    load_ids(u_first);
+    constexpr int LT = (2 * kFineLogEntries + kMfmaThreads - 1) / kMfmaThreads;
+    double lt[LT];
+#pragma unroll
+    for (int k = 0; k < LT; ++k) {
+        const int i = (int)threadIdx.x + k * kMfmaThreads;
+        lt[k] = i < 2 * kFineLogEntries ? reinterpret_cast<const double*>(p.logtab)[i] : 0.0;
+    }
+    const bool has_meta = META && (int)threadIdx.x < SL * TPB;
+    const int m_sl = (int)threadIdx.x / TPB, m_t = (int)threadIdx.x % TPB;
+    const int m_slot = has_meta ? slot_of(m_sl) : -1;
+    uint32_t m_pat = 0xFFu, m_g[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) m_g[c] = 0xFFFFFFFFu;
+    if (m_slot >= 0) {                                   // (m_t < TPB <= kMaxTuples: the rows exist whatever KT is)
+        m_pat = p.tuple_p[(int64_t)m_slot * p.tuple_p_stride + m_t];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) m_g[c] = p.tuple_g[(int64_t)m_slot * p.tuple_g_stride + m_t * kMaxComponents + c];
+    }
+    if (has_meta) meta[m_sl * TPB + m_t] = meta_of(m_slot, m_t, m_pat, m_g);
+    (void)meta;
+#pragma unroll
+    for (int k = 0; k < LT; ++k) {
+        const int i = (int)threadIdx.x + k * kMfmaThreads;
+        if (i < 2 * kFineLogEntries) reinterpret_cast<double*>(lds_raw + tab_off)[i] = lt[k];
+    }
+    for (int u0 = u_first; u0 < n_units; u0 += UB * kMfmaThreads) {
+        if (u0 != u_first) load_ids(u0);
+        emit(u0);
     }
 }
 

@@ -1,7 +1,5 @@
 // sbe_mixture_tuple.hip -- the group-tuple forms of the fused mixture log-likelihood on the vector pipe (k_mixture_combo: tuple
 // metadata in LDS, any tile width, both streams; k_mixture_tuple64: the scalar-unit form at 64-feature tiles) and their launchers.
-#include <cstdlib>
-
 #include "sbe_kernels_mixture.hip.h"
 
 namespace sbe {
@@ -29,7 +27,6 @@ static void launch_tuple64_o(int C, const Mix2Params& p, dim3 grid, size_t lds, 
 }
 
 void launch_tuple64(int C, const Mix2Params& p, dim3 grid, size_t lds, hipStream_t st) {
-    if (const char* env = getenv("SBE_T64_LDS_PAD")) lds += (size_t)atoi(env);        // experiments: fewer blocks per CU
     // 16-bit tuple-block offsets when the whole log table sits below 64 KiB
     const bool off16 = (int64_t)p.KT * (p.S + 1) * 512 <= 65536;
     if (off16) launch_tuple64_o<true, 4>(C, p, grid, lds, st); else launch_tuple64_o<false, 4>(C, p, grid, lds, st);

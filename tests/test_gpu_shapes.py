@@ -234,7 +234,7 @@ def test_tuple_kernel_batches(shape):
     (8900, 6,   2,  [2, 1],     5),       # 140 k-blocks: 4 slots x 1 M tile, the A image 140 KB -- the largest that fits a CU's LDS
 ], ids=lambda s: f"N{s[0]}F{s[1]}S{s[2]}C{len(s[3])}B{s[4]}")
 def test_mfma_kernel_batches(shape):
-    """Batches through the matrix-pipe group-tuple kernel (counts per (slot, tuple, feature, state) by i8 MFMA, one log per
+    """Batches through the matrix-pipe group-tuple kernel (counts per (slot, tuple, feature, state) by FP4 MFMA, one log per
     table entry): every slot holds a different state and must get the oracle's value and its own single-launch value.
     States include inapplicable feature states (probability exactly 0 where no observation falls) and one slot with
     fewer group tuples than the launch's maximum."""
@@ -502,9 +502,9 @@ def test_rows_kernel_pattern_sorted_objects(shape, monkeypatch):
         np.testing.assert_allclose(eng.mixture_loglik_batch(0, B), got2, rtol=1e-12)
 
 
-def test_mfma_wave_specialised_form():
-    """The opt-in wave-specialised form of the matrix-pipe kernel (SBE_MFMA_WS=1: producer waves count, consumer waves evaluate;
-    sbe_mixture_mfma_ws.hip) gives the oracle's values.  The switch is read once per process, so this runs in a child."""
+def test_mfma_kernel_16_slot_form():
+    """The matrix-pipe kernel with 16 slots per block gives the oracle's values, also for small launches that would
+    otherwise take four slots per block (SBE_MFMA_SMALL_SL4=0).  The switch is read once per process, so this runs in a child."""
     import subprocess
     code = r'''
 import sys
@@ -540,11 +540,12 @@ for (N, F, S, n_groups, B) in [(203, 72, 4, [3, 1], 19), (1000, 37, 3, [5, 1], 6
             want.append(orc.mixture_loglik(feats, na, groups, counts, conc, weights))
         eng.set_option(kernel=MIXTURE_PACKED_TUPLE_MFMA)
         got = eng.mixture_loglik_batch(0, B)
-        assert "k_mixture_tuple_mfma_ws" in eng.last_mixture_kernel(), eng.last_mixture_kernel()
+        name = eng.last_mixture_kernel()
+        assert "k_mixture_tuple_mfma<" in name and "16 slots" in name, name
         np.testing.assert_allclose(got, np.array(want), rtol=1e-10)
         assert np.array_equal(eng.mixture_loglik_batch(0, B), got)
-print("ws ok")
+print("16-slot form ok")
 ''' % str(Path(__file__).resolve().parent.parent)
-    env = dict(os.environ, SBE_MFMA_WS="1", SBE_MFMA_SMALL_SL4="0")      # (small launches would take four slots per block: no ws form there)
+    env = dict(os.environ, SBE_MFMA_SMALL_SL4="0")      # (small launches would take four slots per block)
     res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
-    assert res.returncode == 0 and "ws ok" in res.stdout, res.stdout[-2000:] + res.stderr[-3000:]
+    assert res.returncode == 0 and "16-slot form ok" in res.stdout, res.stdout[-2000:] + res.stderr[-3000:]

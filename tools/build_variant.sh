@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-u
 mkdir -p build/obj_var
 /opt/rocm/bin/hipcc $FLAGS "$@" -c sbayes_amd/csrc/$UNIT.hip -o build/obj_var/${UNIT}_$TAG.o
 OBJS=""
-for u in sbe_engine sbe_engine_steps sbe_engine_resident sbe_engine_stateless sbe_mixture sbe_mixture_tuple sbe_mixture_rows sbe_mixture_mfma sbe_mixture_mfma_ws; do
+for u in sbe_engine sbe_engine_steps sbe_engine_resident sbe_engine_stateless sbe_mixture sbe_mixture_tuple sbe_mixture_rows sbe_mixture_mfma; do
   if [ $u = $UNIT ]; then OBJS="$OBJS build/obj_var/${UNIT}_$TAG.o"; else OBJS="$OBJS build/obj/$u.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -o sbayes_amd/libsbe_var_$TAG.so
