@@ -33,6 +33,9 @@ constexpr int kElpdWaves = kElpdBlock / 64;
 constexpr int kMaxM = 96;                            // _gpdfit candidates: 30 + sqrt(T) <= 85 for S <= 2^20 (T <= 3072)
 constexpr size_t kLdsBudget = (size_t)160 << 10;     // LDS per CU on MI355X (MI355X_MICROARCH.md)
 constexpr size_t kStaticLds = 8192;                  // headroom for the kernel's static LDS (histogram, reductions, fit)
+// workgroups per launch along x: an AQL dispatch holds its grid in work-items as a uint32, so every launch below stays
+// under 2^32 work-items and longer ranges are launched in chunks, each with its offset
+constexpr int64_t kMaxGridBlocks = ((int64_t)1 << 24) - 1;
 
 inline int tail_count(int64_t s) { return (int)std::ceil(std::min(0.2 * (double)s, 3.0 * std::sqrt((double)s))); }
 inline int pow2_at_least(int v) { int p = 1; while (p < v) p <<= 1; return p; }
@@ -128,6 +131,7 @@ struct ElpdArgs {
     int staged;
     double* out;              // [4][n_kept]: loo_i, k_i, lppd_i, v_i
     int64_t n_kept;
+    int64_t j0;               // first kept column of this launch (launches are chunked: kMaxGridBlocks)
     int* bad;                 // device word: count of columns holding a value that is not positive and finite
 };
 
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
     __shared__ double red[kElpdWaves];
     __shared__ double fit_b[kMaxM], fit_k[kMaxM], fit_ls[kMaxM], fit_w[kMaxM];
     __shared__ double fit_post[1];                  // b_post
-    const int64_t j = blockIdx.x;
+    const int64_t j = a.j0 + blockIdx.x;
     const int s = a.s, tid = threadIdx.x;
     const uint32_t* g = reinterpret_cast<const uint32_t*>(a.lh + (int64_t)a.cols[j] * a.cap + a.burn);
     double* ary = reinterpret_cast<double*>(dyn);                            // [tail_p] tail exceedances
@@ -308,8 +312,9 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
 }
 
 // NA rule of elpd.py:31 without a mask: keep[m] = 0 where every stored row is isclose(lh, 1); one wave per column
-__global__ __launch_bounds__(256) void k_elpd_isclose(const float* lh, int64_t cap, int64_t n_rows, int64_t M, uint8_t* keep) {
-    const int64_t col = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+__global__ __launch_bounds__(256) void k_elpd_isclose(const float* lh, int64_t cap, int64_t n_rows, int64_t M, uint8_t* keep,
+                                                      int64_t col0) {
+    const int64_t col = col0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (col >= M) return;
     const float* c = lh + col * cap;
     int far = 0;
@@ -319,9 +324,10 @@ __global__ __launch_bounds__(256) void k_elpd_isclose(const float* lh, int64_t c
 }
 
 // host rows [n][M] (staging) -> store columns [M][cap] at row offset r0: 32 x 32 tiles through LDS
-__global__ __launch_bounds__(256) void k_elpd_transpose(const float* rows, int64_t n, int64_t M, float* lh, int64_t cap, int64_t r0) {
+__global__ __launch_bounds__(256) void k_elpd_transpose(const float* rows, int64_t n, int64_t M, float* lh, int64_t cap, int64_t r0,
+                                                        int64_t mt0) {
     __shared__ float tile[32][33];
-    const int64_t m0 = (int64_t)blockIdx.x * 32, n0 = (int64_t)blockIdx.y * 32;
+    const int64_t m0 = (mt0 + blockIdx.x) * 32, n0 = (int64_t)blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
     for (int r = ty; r < 32; r += 8) {
         const int64_t row = n0 + r, col = m0 + tx;
@@ -335,9 +341,10 @@ __global__ __launch_bounds__(256) void k_elpd_transpose(const float* rows, int64
 }
 
 // store columns -> host row order [n][M] (rows read back)
-__global__ __launch_bounds__(256) void k_elpd_untranspose(const float* lh, int64_t cap, int64_t r0, int64_t n, int64_t M, float* rows) {
+__global__ __launch_bounds__(256) void k_elpd_untranspose(const float* lh, int64_t cap, int64_t r0, int64_t n, int64_t M, float* rows,
+                                                          int64_t mt0) {
     __shared__ float tile[32][33];
-    const int64_t m0 = (int64_t)blockIdx.x * 32, n0 = (int64_t)blockIdx.y * 32;
+    const int64_t m0 = (mt0 + blockIdx.x) * 32, n0 = (int64_t)blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int c = ty; c < 32; c += 8) {
         const int64_t col = m0 + c, row = n0 + tx;
@@ -507,9 +514,12 @@ int sbe_elpd_append_rows(sbe_elpd_store* st, const float* rows, int64_t n_rows) 
     for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
         const int64_t k = std::min(st->stage_rows, n_rows - r);
         EHIP(st, hipMemcpyAsync(st->d_stage, rows + r * st->M, (size_t)k * st->M * sizeof(float), hipMemcpyHostToDevice, st->stream));
-        const dim3 grid((unsigned)((st->M + 31) / 32), (unsigned)((k + 31) / 32));
-        k_elpd_transpose<<<grid, 256, 0, st->stream>>>(st->d_stage, k, st->M, st->d_lh, st->cap, st->n + r);
-        EHIP(st, hipGetLastError());
+        const int64_t tiles = (st->M + 31) / 32;
+        for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
+            const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
+            k_elpd_transpose<<<grid, 256, 0, st->stream>>>(st->d_stage, k, st->M, st->d_lh, st->cap, st->n + r, t0);
+            EHIP(st, hipGetLastError());
+        }
     }
     EHIP(st, hipStreamSynchronize(st->stream));
     st->n += n_rows;
@@ -550,9 +560,12 @@ int sbe_elpd_get_rows(sbe_elpd_store* st, int64_t row0, int64_t n_rows, float* o
     if (rc) return rc;
     for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
         const int64_t k = std::min(st->stage_rows, n_rows - r);
-        const dim3 grid((unsigned)((st->M + 31) / 32), (unsigned)((k + 31) / 32));
-        k_elpd_untranspose<<<grid, 256, 0, st->stream>>>(st->d_lh, st->cap, row0 + r, k, st->M, st->d_stage);
-        EHIP(st, hipGetLastError());
+        const int64_t tiles = (st->M + 31) / 32;
+        for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
+            const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
+            k_elpd_untranspose<<<grid, 256, 0, st->stream>>>(st->d_lh, st->cap, row0 + r, k, st->M, st->d_stage, t0);
+            EHIP(st, hipGetLastError());
+        }
         EHIP(st, hipMemcpyAsync(out + r * st->M, st->d_stage, (size_t)k * st->M * sizeof(float), hipMemcpyDeviceToHost, st->stream));
         EHIP(st, hipStreamSynchronize(st->stream));
     }
@@ -576,8 +589,12 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
     if (na_values) {
         for (int64_t m = 0; m < st->M; ++m) keep[m] = na_values[m] == 0;
     } else if (na_isclose) {
-        k_elpd_isclose<<<div_up(st->M, 4), 256, 0, st->stream>>>(st->d_lh, st->cap, st->n, st->M, st->d_keep);
-        EHIP(st, hipGetLastError());
+        const int64_t blocks = div_up(st->M, 4);
+        for (int64_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+            k_elpd_isclose<<<(unsigned)std::min(kMaxGridBlocks, blocks - b0), 256, 0, st->stream>>>(st->d_lh, st->cap, st->n, st->M,
+                                                                                                 st->d_keep, b0 * 4);
+            EHIP(st, hipGetLastError());
+        }
         EHIP(st, hipMemcpyAsync(keep.data(), st->d_keep, (size_t)st->M, hipMemcpyDeviceToHost, st->stream));
         EHIP(st, hipStreamSynchronize(st->stream));
     }
@@ -593,10 +610,12 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
     EHIP(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
     EHIP(st, hipMemcpyAsync(st->d_cols, cols.data(), (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st->stream));
     EHIP(st, hipMemsetAsync(st->d_bad, 0, sizeof(int), st->stream));
-    const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, st->d_bad};
     EHIP(st, hipEventRecord(st->ev[0], st->stream));
-    k_elpd_column<<<(unsigned)nk, kElpdBlock, lds, st->stream>>>(args);     // one workgroup per kept column (nk < 2^31)
-    EHIP(st, hipGetLastError());
+    for (int64_t j0 = 0; j0 < nk; j0 += kMaxGridBlocks) {                  // one workgroup per kept column
+        const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, j0, st->d_bad};
+        k_elpd_column<<<(unsigned)std::min(kMaxGridBlocks, nk - j0), kElpdBlock, lds, st->stream>>>(args);
+        EHIP(st, hipGetLastError());
+    }
     EHIP(st, hipEventRecord(st->ev[1], st->stream));
     int bad = 0;
     EHIP(st, hipMemcpyAsync(&bad, st->d_bad, sizeof(int), hipMemcpyDeviceToHost, st->stream));

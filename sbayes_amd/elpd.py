@@ -21,7 +21,6 @@ pickled, forgotten (not destroyed) in a fork()ed child, where every further call
 from __future__ import annotations
 
 import ctypes as ct
-import math
 import os
 from dataclasses import dataclass
 from pathlib import Path
@@ -225,7 +224,7 @@ def _check_na(na_values, m):
 
 def _loo(loo_i, k_i, lppd_i, s):
     m = len(loo_i)
-    good_k = min(1 - 1 / math.log10(s), 0.7)
+    good_k = float(min(1 - 1 / np.log10(s), 0.7))          # np.log10, as arviz.loo: math.log10 differs in the last bit at some S
     elpd = float(np.sum(loo_i))
     lppd = float(np.sum(lppd_i))
     return LooResult(elpd_loo=elpd, se=float((m * np.var(loo_i)) ** 0.5), p_loo=lppd - elpd, lppd=lppd, n_samples=s,

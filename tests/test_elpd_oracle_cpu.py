@@ -117,3 +117,59 @@ def test_values_that_are_not_positive_and_finite_are_refused():
     lh[4, 1] = 0.0
     with pytest.raises(ValueError, match="positive and finite"):
         eo.pointwise(lh, burnin=0.0)
+
+
+# ---- known answers across the sample range (the device is held to the same ones: tests/test_gpu_elpd_range.py) ----
+def _beta_bernoulli(s, seed, n=20, ones=14, a=1.0, b=1.0):
+    """The two distinct columns of a Beta-Bernoulli model under s exact posterior draws (y = 1, y = 0) and the exact
+    log leave-one-out predictive of each: p(y_i | y_-i) = (a + sum_{j != i} y_j) / (a + b + n - 1) for y_i = 1."""
+    theta = np.random.default_rng(seed).beta(a + ones, b + n - ones, s)
+    exact = [math.log((a + ones - 1) / (a + b + n - 1)), math.log(1 - (a + ones) / (a + b + n - 1))]
+    return theta.astype(np.float32), (1 - theta).astype(np.float32), exact
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 3])
+def test_beta_bernoulli_smoothed_loo_at_2_20_samples(seed):
+    """A smoothed loo_i tied to a known value: at S = 2^20 (T = 3072, 85 fit candidates) PSIS recovers the exact
+    leave-one-out predictive.  Over seeds 0 .. 15 the error was at most 7.8e-4 (k = 0.003 .. 0.17): 2e-3 has margin."""
+    c1, c0, exact = _beta_bernoulli(1 << 20, seed)
+    for col, want in ((c1, exact[0]), (c0, exact[1])):
+        loo_i, k, _lppd, _v = _col(col)
+        assert 0 < k < 0.5
+        assert abs(loo_i - want) <= 2e-3, (loo_i, want)
+
+
+@pytest.mark.parametrize("s", [2, 3, 4, 20])
+def test_columns_up_to_20_samples_are_never_smoothed(s):
+    """T = ceil(min(0.2 S, 3 sqrt(S))) <= 4 up to S = 20: k = inf, loo_i = -log(mean(1/lh)), lppd_i = log(mean(lh)),
+    v_i = var(log lh)."""
+    lh = np.random.default_rng(s).uniform(0.01, 1.0, s).astype(np.float32)
+    x = lh.astype(np.float64)
+    loo_i, k, lppd_i, v_i = _col(lh)
+    assert k == np.inf
+    assert loo_i == pytest.approx(-math.log(np.mean(1 / x)), rel=1e-14)
+    assert lppd_i == pytest.approx(math.log(np.mean(x)), rel=1e-14)
+    assert v_i == pytest.approx(np.var(np.log(x)), rel=1e-12, abs=1e-300)
+
+
+def test_21_samples_fit_five_distinct_tail_values_but_not_four():
+    """S = 21, T = 5: the sixth smallest value is the cutoff.  Five distinct values below it are fitted; a tie of the
+    fifth and sixth smallest leaves four, unsmoothed (the harmonic mean)."""
+    v = np.linspace(0.05, 0.95, 21)
+    loo_i, k, _lppd, _v = _col(v)
+    assert np.isfinite(k) and loo_i != pytest.approx(-math.log(np.mean(1 / v.astype(np.float32).astype(float))), rel=1e-9)
+    tied = v.copy()
+    tied[5] = tied[4]
+    x = tied.astype(np.float32).astype(np.float64)
+    loo_i, k, _lppd, _v = _col(tied)
+    assert k == np.inf
+    assert loo_i == pytest.approx(-math.log(np.mean(1 / x)), rel=1e-14)
+
+
+def test_good_k_uses_arviz_log10():
+    """arviz.loo forms good_k with np.log10; math.log10 differs in the last bit at S = 11, 40, 43, 119, ... and the
+    reported good_k (and the warning at a k that equals it) must be arviz's."""
+    from sbayes_amd import elpd
+    for s in (11, 40, 43, 119, 1002, 1 << 20):
+        z = np.zeros(1)
+        assert elpd._loo(z, z, z, s).good_k == eo.totals(z, z, z, z, s)["good_k"] == min(1 - 1 / np.log10(s), 0.7)

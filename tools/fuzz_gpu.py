@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised differential test on the GPU box: random shapes / states / batch sizes through every fused-kernel form,
 both sbe_step forms and the one-call Gibbs step, against the CPU oracle.  Not part of the pytest suite (open-ended
-run time):  python tools/fuzz_gpu.py --seconds 300 [--seed 0]"""
+run time):  python tools/fuzz_gpu.py --seconds 300 [--seed 0]
+With --elpd it draws PSIS-LOO / WAIC cases instead (tests/test_gpu_elpd_range.py: random_elpd_case) and compares each with
+the NumPy restatement; a mismatch prints the case seed, which --elpd-case SEED replays."""
 import argparse
 import sys
 import time
@@ -496,12 +498,40 @@ def one_case(rng, stats, big=False):
     stats["cases"] += 1
 
 
+def elpd_main(args):
+    from tests.test_gpu_elpd_range import random_elpd_case, run_elpd_case
+    from sbayes_amd.registry import release_all
+    seeds = np.random.default_rng(args.seed)
+    stats = {"cases": 0, "columns": 0, "samples_max": 0}
+    t0 = last = time.time()
+    while (time.time() - t0 < args.seconds) if args.elpd_case is None else stats["cases"] == 0:
+        seed = int(seeds.integers(1 << 62)) if args.elpd_case is None else args.elpd_case
+        lh, na, burnin = random_elpd_case(np.random.default_rng(seed))
+        try:
+            run_elpd_case(lh, na, burnin)
+        except BaseException:
+            print(f"[fuzz] elpd mismatch: case seed {seed} (S_total {lh.shape[0]}, M {lh.shape[1]}, burnin {burnin})", flush=True)
+            raise
+        release_all()
+        stats["cases"] += 1
+        stats["columns"] += lh.shape[1]
+        stats["samples_max"] = max(stats["samples_max"], lh.shape[0] - int(burnin * lh.shape[0]))
+        if time.time() - last > 30:
+            last = time.time()
+            print(f"[fuzz] {time.time() - t0:5.0f} s  {stats}", flush=True)
+    print(f"[fuzz] done, no mismatch: {stats}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--big", action="store_true", help="large shapes and batches (long chunks, several block generations)")
+    ap.add_argument("--elpd", action="store_true", help="PSIS-LOO / WAIC cases against tests/_elpd_oracle.py")
+    ap.add_argument("--elpd-case", type=int, default=None, help="replay one --elpd case by its seed")
     args = ap.parse_args()
+    if args.elpd or args.elpd_case is not None:
+        return elpd_main(args)
     rng = np.random.default_rng(args.seed)
     stats = {"cases": 0, "evals": 0, "steps": 0, "gibbs": 0}
     t0 = last = time.time()
