@@ -148,8 +148,9 @@ class Likelihood:
         if how is not None:
             from . import patch
             cur = patch.installed()
-            if cur is None or (how["operators"] and not cur["operators"]) or (how.get("gibbs_source") and not cur.get("gibbs_source")):
-                patch.install(operators=how["operators"], gibbs_source=bool(how.get("gibbs_source")))
+            if (cur is None or (how["operators"] and not cur["operators"]) or (how.get("gibbs_source") and not cur.get("gibbs_source"))
+                    or (how.get("em_init") and not cur.get("em_init"))):
+                patch.install(operators=how["operators"], gibbs_source=bool(how.get("gibbs_source")), em_init=bool(how.get("em_init")))
         registry.note_features(self.features, self.n_groups)
 
     @property

@@ -81,6 +81,8 @@ MIRRORED_SOURCES = {
     "ConfoundingEffectsPrior.concentration_array": "a089466a31285e330baf46ecc81f435fcd63a359",
     "ArrayParameter.resolve_sharing": "9456c9d76c849a1e341c66b73e69d630c52fb3bf",
     "GroupedParameters.resolve_sharing": "e26fbdc96e79af850e2840a33297ddb0d997d967",
+    # install(em_init=True): the EM cluster initializer (sbayes_amd/em.py)
+    "SbayesInitializer.generate_clusters_em": "6e88242a00990dd9469737a9f513f30502fc5316",
 }
 
 
@@ -102,7 +104,8 @@ def _check_mirrored(owner, name):
 
 
 def installed():
-    """{"operators": bool} if install() ran in this process (and uninstall() has not), else None."""
+    """{"operators": bool, "gibbs_source": bool} (plus "em_init": True when that hook is on) if install() ran in this
+    process (and uninstall() has not), else None."""
     return dict(_INSTALLED) if _INSTALLED is not None else None
 
 
@@ -130,7 +133,7 @@ def set_mp_start_method(method):
     return method
 
 
-def install(operators=False, mp_start_method=None, gibbs_source=False):
+def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=False):
     """operators=True: the device forms listed in the module docstring.  gibbs_source=True (implies operators): the two
     Gibbs source resamplings of the reference run on the device, with the uniforms np.random yields
     at the point where the reference's `sample_categorical` draws them (draw for draw: the same Markov chain) --
@@ -141,7 +144,10 @@ def install(operators=False, mp_start_method=None, gibbs_source=False):
         AlterClusterWide / ClusterJump proposal: likelihood under the kept observations, both posteriors, draw, selected
         probabilities AND the count delta the reference asks for next (update_feature_counts, :827) in ONE engine call
         (operators.cluster_gibbs_sample_source -> sbe_given_unchanged_gibbs_counts).
-    At the headline shape these two bodies are the largest items of the reference's per-step Python."""
+    At the headline shape these two bodies are the largest items of the reference's per-step Python.
+    em_init=True: SbayesInitializer.generate_clusters_em (initializers.py:93-169) runs its EM steps on the device
+    (sbayes_amd/em.py); its draws are the reference's, but z is carried in fp64, so the initial clusters can differ from an
+    unpatched run's on objects near a tie.  Off by default."""
     global _INSTALLED
     operators = bool(operators) or bool(gibbs_source)
     if mp_start_method is not None:
@@ -202,8 +208,26 @@ def install(operators=False, mp_start_method=None, gibbs_source=False):
                           ("compute_effect_counts", my_counts.compute_effect_counts),
                           ("compute_component_likelihood", my_lik.compute_component_likelihood)):
             swap(m, name, new)
+    em_init = bool(em_init) and not (_INSTALLED and _INSTALLED.get("em_init"))
+    if em_init:
+        _install_em_init_form(swap)
+    was_em = bool(_INSTALLED and _INSTALLED.get("em_init"))
     _INSTALLED = {"operators": bool(operators) or bool(_INSTALLED and _INSTALLED["operators"]),
                   "gibbs_source": bool(gibbs_source) or bool(_INSTALLED and _INSTALLED.get("gibbs_source"))}
+    if em_init or was_em:
+        _INSTALLED["em_init"] = True
+
+
+def _install_em_init_form(swap):
+    """SbayesInitializer.generate_clusters_em -> sbayes_amd.em.generate_clusters_em (the EM steps on the device)."""
+    ref_init = importlib.import_module("sbayes.sampling.initializers")
+    from . import em as my_em
+    _check_mirrored(ref_init.SbayesInitializer, "generate_clusters_em")
+
+    def generate_clusters_em(self):
+        return my_em.generate_clusters_em(self)
+
+    swap(ref_init.SbayesInitializer, "generate_clusters_em", generate_clusters_em)
 
 
 _NODE_CLASSES = []
