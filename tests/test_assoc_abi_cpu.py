@@ -1,0 +1,142 @@
+"""CPU checks of the feature-screening boundary (include/sbe_assoc.h, sbayes_amd/assoc.py): the symbols are exported and
+bound by the module's own prototype table, and bad arguments are refused before the device is touched."""
+import ast
+import ctypes as ct
+import inspect
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from sbayes_amd import _lib, assoc
+
+REPO = Path(__file__).resolve().parent.parent
+HEADER = (REPO / "include" / "sbe_assoc.h").read_text()
+
+
+def _declared():
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_symbol_of_the_header_is_exported_and_bound():
+    lib = assoc.load()
+    names = _declared()
+    assert len(names) == 9
+    for name in names:
+        assert hasattr(lib, name), f"{name} declared in include/sbe_assoc.h but not exported"
+    assert sorted(assoc.PROTOTYPES) == names
+    assert lib.sbe_assoc_abi_version() == assoc.ABI_VERSION
+    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+
+
+def test_limits_agree_with_the_header():
+    def macro(name):
+        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
+    assert macro("SBE_ASSOC_NA") == str(assoc.NA)
+    assert macro("SBE_ASSOC_MAX_OBJECTS") == "(1 << 24)" and assoc.MAX_OBJECTS == 1 << 24
+    assert macro("SBE_ASSOC_MAX_STATES") == str(assoc.MAX_STATES)
+    assert macro("SBE_ASSOC_MAX_FEATURES") == str(assoc.MAX_FEATURES)
+    assert macro("SBE_ASSOC_MAX_CODES") == "((int64_t)1 << 31)" and assoc.MAX_CODES == 1 << 31
+
+
+def test_every_array_handed_to_the_library_is_bound_to_a_name():
+    """assoc.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
+    tree = ast.parse(inspect.getsource(assoc))
+    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
+           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
+           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
+    assert not bad, bad
+
+
+@pytest.fixture
+def no_handle(monkeypatch):
+    def refuse(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(assoc, "AssocHandle", refuse)
+    monkeypatch.setattr(assoc, "_HANDLES", {})
+
+
+@pytest.mark.parametrize("features,n_states,err,match", [
+    (np.zeros((4, 3), dtype=np.int64), None, TypeError, "uint8"),
+    (np.zeros(4, dtype=np.uint8), None, ValueError, "n_objects, n_features"),
+    (np.zeros((0, 3), dtype=np.uint8), None, ValueError, "both positive"),
+    (np.zeros((4, 3), dtype=np.uint8), [2, 2], ValueError, "n_states must be 3 integers"),
+    (np.zeros((4, 3), dtype=np.uint8), [2, 33, 2], ValueError, r"\[1, 32\]"),
+    (np.full((4, 3), 40, dtype=np.uint8), None, ValueError, r"\[1, 32\]"),
+    (np.array([[0, 2], [1, 255]], dtype=np.uint8), [2, 2], ValueError, r"features\[0, 1\] = 2 is neither below n_states\[1\] = 2"),
+    (np.zeros((4, 3, 33), dtype=bool), None, ValueError, "at most 32"),
+    (np.ones((4, 3, 2), dtype=bool), None, ValueError, "more than one state"),
+    (np.zeros((2, assoc.MAX_FEATURES + 1), dtype=np.uint8), None, ValueError, "4096 features"),
+])
+def test_bad_input_is_refused_before_the_device(no_handle, features, n_states, err, match):
+    with pytest.raises(err, match=match):
+        assoc.feature_association(features, n_states)
+
+
+def test_too_many_objects_are_refused_with_the_limit(no_handle):
+    x = np.broadcast_to(np.zeros((1, 1), dtype=np.uint8), (assoc.MAX_OBJECTS + 1, 1))      # (no memory behind it)
+    with pytest.raises(ValueError, match=r"2\^24"):
+        assoc.feature_association(x)
+
+
+def test_one_hot_features_become_codes():
+    onehot = np.zeros((3, 2, 4), dtype=bool)
+    onehot[0, 0, 2] = onehot[1, 0, 0] = onehot[2, 1, 3] = True
+    assert np.array_equal(assoc.state_codes(onehot), np.array([[2, 255], [0, 255], [255, 3]], dtype=np.uint8))
+    x, ns = assoc._check_inputs(onehot, None)
+    assert x.dtype == np.uint8 and np.array_equal(ns, [4, 4])
+    x, ns = assoc._check_inputs(np.array([[0, 255], [3, 255]], dtype=np.uint8), None)
+    assert np.array_equal(ns, [4, 1])                      # one more than the largest code; a feature never observed: 1
+
+
+def test_c_abi_validates_before_the_device():
+    lib = assoc.load()
+    h = ct.c_void_p()
+    assert lib.sbe_assoc_create(None, 0) == 1
+    assert b"null pointer argument: out" in lib.sbe_assoc_last_error(None)
+    assert lib.sbe_assoc_create(ct.byref(h), -1) == 1 and not h
+    assert b"device -1 out of range" in lib.sbe_assoc_last_error(None)
+    assert lib.sbe_assoc_compute(None, None, 1, 1, None, None, None, None, None, None) == 1
+    assert b"null handle" in lib.sbe_assoc_last_error(None)
+    assert lib.sbe_assoc_tables(None, None, 0, None) == 1
+    assert lib.sbe_assoc_destroy(None) == 1
+    assert lib.sbe_assoc_set_launch_tiles(None, 4) == 1
+    ms = ct.c_float()
+    assert lib.sbe_assoc_last_kernel_ms(None, ct.byref(ms)) == 1
+
+
+def test_frame_codes_number_states_in_sorted_order():
+    pd = pytest.importorskip("pandas")
+    frame = pd.DataFrame({"F1": ["Y", "N", None, "Y"], "F2": ["B", "A", "C", None], "F3": [None] * 4}, dtype=object)
+    codes, n_states, names, states = assoc.frame_codes(frame)
+    assert names == ["F1", "F2", "F3"] and states == [["N", "Y"], ["A", "B", "C"], []]
+    assert np.array_equal(n_states, [2, 3, 1])
+    assert np.array_equal(codes, np.array([[1, 1, 255], [0, 0, 255], [255, 2, 255], [1, 255, 255]], dtype=np.uint8))
+
+
+def test_csv_needs_the_metadata_columns(tmp_path):
+    pytest.importorskip("pandas")
+    path = tmp_path / "features.csv"
+    path.write_text("id,name,family,x,y,F1,F2\na,A,,0,0, Y ,\nb,B,fam,1,1,N,Q\n")
+    frame = assoc.read_features_csv(path)
+    assert list(frame.columns) == ["F1", "F2"]
+    assert frame["F1"].tolist() == ["Y", "N"] and frame["F2"].isna().tolist() == [True, False]
+    path.write_text("id,name,x,y,F1\na,A,0,0,Y\n")
+    with pytest.raises(ValueError, match="Required column 'family' missing"):
+        assoc.read_features_csv(path)
+
+
+def test_handles_are_not_picklable_and_results_sort_like_the_tool():
+    import pickle
+    h = object.__new__(assoc.AssocHandle)
+    h._h = ct.c_void_p()
+    with pytest.raises(TypeError):
+        pickle.dumps(h)
+    p = np.array([[np.nan, 1e-9, 0.5], [1e-9, np.nan, 1e-12], [0.5, 1e-12, np.nan]])
+    valid = ~np.isnan(p)
+    res = assoc.AssociationResult(np.zeros((3, 3)), p, np.ones((3, 3), np.int32), np.ones((3, 3), np.int32), valid,
+                                  np.array([2, 2, 2], np.int32))
+    assert res.correlated() == [(1e-12, 1, 2), (1e-9, 0, 1)]
+    assert res.correlated(1e-10) == [(1e-12, 1, 2)]
