@@ -24,13 +24,11 @@ uses it, never pickled, forgotten (not destroyed) in a fork()ed child, where eve
 from __future__ import annotations
 
 import ctypes as ct
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _fast, _lib, _proc
-from .engine import EngineError
+from . import _fast, _handle, _proc
 
 ABI_VERSION = 1                          # SBE_ASSOC_ABI_VERSION of include/sbe_assoc.h
 NA = 255                                 # SBE_ASSOC_NA
@@ -56,48 +54,24 @@ PROTOTYPES = {
     "sbe_assoc_last_shape": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]),
     "sbe_assoc_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
 }
-_BOUND = [None]
 
 _ptr = _fast.addr                        # buffer address as a plain int (engine.py: every array argument is c_void_p)
 
 
 def load():
     """The engine library with the prototypes of include/sbe_assoc.h attached."""
-    lib = _lib.load()
-    if _BOUND[0] is not lib:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(lib, name)       # AttributeError if the library lacks a declared symbol
-            fn.restype = restype
-            fn.argtypes = argtypes
-        if lib.sbe_assoc_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"sbayes_amd.assoc: ABI version mismatch ({lib.sbe_assoc_abi_version()} != {ABI_VERSION})")
-        _BOUND[0] = lib
-    return lib
+    return _handle.bind("sbe_assoc", PROTOTYPES, ABI_VERSION)
 
 
-class AssocHandle:
-    """Owner of one sbe_assoc handle: a stream and the device buffers of the last data set on one device."""
+class AssocHandle(_handle.UnitHandle):
+    """Owner of one sbe_assoc handle: a stream and the device buffers of the last data set on one device.
+    last_kernel_ms(): the pair kernel's launches of the last compute call."""
+    _prefix, _noun = "sbe_assoc", "an association handle"
 
     def __init__(self, device=0):
-        _proc.check_usable()
-        self._lib = load()
-        self._h = ct.c_void_p()
-        self._pid = None
         self.device = int(device)
         self._data = None                  # the codes the device holds (AssociationResult.tables)
-        _proc.mark_hip_touched()
-        rc = self._lib.sbe_assoc_create(ct.byref(self._h), self.device)
-        if rc != 0:
-            msg = self._lib.sbe_assoc_last_error(None)
-            self._h = ct.c_void_p()
-            raise EngineError(rc, msg.decode() if msg else "sbe_assoc_create failed")
-        self._pid = os.getpid()
-        _proc.register_engine(self)
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.sbe_assoc_last_error(self._h)
-            raise EngineError(rc, msg.decode() if msg else "?")
+        self._create(load, self.device)
 
     def set_launch_tiles(self, tile_pairs):
         """Tile pairs per launch of the pair kernel (0: the default).  Results do not depend on it."""
@@ -125,32 +99,6 @@ class AssocHandle:
         s_pad, tiles, launches = ct.c_int32(0), ct.c_int64(0), ct.c_int64(0)
         self._check(self._lib.sbe_assoc_last_shape(self._h, ct.byref(s_pad), ct.byref(tiles), ct.byref(launches)))
         return s_pad.value, tiles.value, launches.value
-
-    def last_kernel_ms(self) -> float:
-        """Device time of the pair kernel's launches of the last compute call (HIP events)."""
-        ms = ct.c_float(0)
-        self._check(self._lib.sbe_assoc_last_kernel_ms(self._h, ct.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            if self._pid == os.getpid():
-                self._lib.sbe_assoc_destroy(self._h)
-            self._h = ct.c_void_p()
-
-    def _forget(self, lib_face):
-        """After fork(), in the child: drop the inherited handle without destroying it (_proc._after_fork_in_child)."""
-        self._h = ct.c_void_p()
-        self._lib = lib_face
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        raise TypeError("an association handle holds device memory and is not picklable; re-create it in the new process")
 
 
 _HANDLES: dict = {}          # device -> AssocHandle; per process, emptied in a fork()ed child

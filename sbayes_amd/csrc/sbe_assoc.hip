@@ -23,13 +23,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <limits>
-#include <string>
 #include <vector>
 
-#include "sbe_engine_internal.hip.h"
+#include "sbe_unit.hip.h"
 #include "../../include/sbe_assoc.h"
 
 namespace {
@@ -308,14 +305,9 @@ __global__ __launch_bounds__(kTableBlock) void k_assoc_table(const uint8_t* xt, 
 
 inline size_t pair_lds_bytes(int sub) { return (size_t)kTile * kTile * sizeof(double) + (size_t)(2 * kTile * sub + 2 * sub * sub) * 4; }
 
-thread_local std::string g_assoc_error;
-
 }  // namespace
 
-struct sbe_assoc {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};       // around the pair kernel's launches of the last compute call
+struct sbe_assoc : sbe_unit_handle {             // (sbe_unit.hip.h; ev: around the pair kernel's launches)
     uint8_t* d_xt = nullptr;                     // codes of the last compute call, feature-major [F][n_pad]
     size_t xt_bytes = 0;
     void* d_out = nullptr;                       // the five [F][F] outputs, or the tables of one sbe_assoc_tables call
@@ -326,51 +318,13 @@ struct sbe_assoc {
     int s_max = 0, s_pad = 0;
     int64_t launch_tiles = 0;                    // 0: the default
     int64_t tile_pairs = 0, launches = 0;
-    float last_kernel_ms = 0.0f;
-    std::string last_error;
+    std::vector<void*> buffers() const { return {d_xt, d_out, d_pairs}; }
 };
 
 namespace {
 
-int afail(sbe_assoc* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_assoc_error = buf;
-    if (h) h->last_error = buf;
-    return code;
-}
-
-#define AHIP(h, call)                                                                                      \
-    do {                                                                                                   \
-        hipError_t _err = (call);                                                                          \
-        if (_err != hipSuccess)                                                                            \
-            return afail(h, SBE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
-#define ACHECK_HANDLE(h) \
-    if (!(h)) return afail(nullptr, SBE_ERR_ARG, "null handle")
-
-template <typename T>
-int ensure(sbe_assoc* h, T*& p, size_t& have, size_t want) {
-    if (have >= want) return SBE_OK;
-    if (p) AHIP(h, hipFree(p));
-    p = nullptr;
-    have = 0;
-    AHIP(h, hipMalloc((void**)&p, want));
-    have = want;
-    return SBE_OK;
-}
-
-void release(sbe_assoc* h) {
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_xt, h->d_out, (void*)h->d_pairs})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t ev : h->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-}
+constexpr sbe_assoc* kNone = nullptr;               // (fail without a handle: the type names the unit)
+constexpr char kNullHandle[] = "null handle";
 
 }  // namespace
 
@@ -378,68 +332,48 @@ extern "C" {
 
 int sbe_assoc_abi_version(void) { return SBE_ASSOC_ABI_VERSION; }
 
-const char* sbe_assoc_last_error(const sbe_assoc* h) { return h ? h->last_error.c_str() : g_assoc_error.c_str(); }
+const char* sbe_assoc_last_error(const sbe_assoc* h) { return unit_last_error(h); }
 
 int sbe_assoc_create(sbe_assoc** out, int device) {
-    if (!out) return afail(nullptr, SBE_ERR_ARG, "null pointer argument: out");
+    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
     *out = nullptr;
-    if (device < 0) return afail(nullptr, SBE_ERR_ARG, "device %d out of range", device);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return afail(nullptr, SBE_ERR_NODEVICE, "no usable GPU (hipGetDeviceCount reports none); there is no CPU fallback");
-    if (device >= count) return afail(nullptr, SBE_ERR_ARG, "device %d out of range [0,%d)", device, count);
-    sbe_assoc* h = new sbe_assoc();
-    h->device = device;
-    auto bail = [&](hipError_t err, const char* what) {
-        afail(nullptr, SBE_ERR_HIP, "sbe_assoc_create: %s failed: %s", what, hipGetErrorString(err));
-        release(h);
-        delete h;
-        return SBE_ERR_HIP;
-    };
-    hipError_t err;
-    if ((err = hipSetDevice(device)) != hipSuccess) return bail(err, "hipSetDevice");
-    if ((err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(err, "hipStreamCreate");
-    for (hipEvent_t& ev : h->ev)
-        if ((err = hipEventCreate(&ev)) != hipSuccess) return bail(err, "hipEventCreate");
+    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
+    sbe_assoc* h = nullptr;
+    const int rc = unit_open(h, device, "sbe_assoc_create", "");
+    if (rc) return rc;
     *out = h;
     return SBE_OK;
 }
 
-int sbe_assoc_destroy(sbe_assoc* h) {
-    ACHECK_HANDLE(h);
-    (void)hipSetDevice(h->device);
-    release(h);
-    delete h;
-    return SBE_OK;
-}
+int sbe_assoc_destroy(sbe_assoc* h) { return unit_destroy(h, kNullHandle); }
 
 int sbe_assoc_set_launch_tiles(sbe_assoc* h, int64_t tile_pairs) {
-    ACHECK_HANDLE(h);
+    CHECK_HANDLE(h, kNullHandle);
     if (tile_pairs < 0 || tile_pairs > kMaxLaunchTiles)
-        return afail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
+        return fail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
     h->launch_tiles = tile_pairs;
     return SBE_OK;
 }
 
 int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t n_features, const int32_t* n_states,
                       double* statistic, double* pvalue, int32_t* dof, int32_t* n, uint8_t* valid) {
-    ACHECK_HANDLE(h);
-    if (!x || !n_states) return afail(h, SBE_ERR_ARG, "null pointer argument: %s", !x ? "x" : "n_states");
-    if (!statistic || !pvalue || !dof || !n || !valid) return afail(h, SBE_ERR_ARG, "null pointer argument: output");
+    CHECK_HANDLE(h, kNullHandle);
+    if (!x || !n_states) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !x ? "x" : "n_states");
+    if (!statistic || !pvalue || !dof || !n || !valid) return fail(h, SBE_ERR_ARG, "null pointer argument: output");
     const int64_t N = n_objects, F = n_features;
     if (N < 1 || N > SBE_ASSOC_MAX_OBJECTS)
-        return afail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (2^24: counts are exact in the f32 accumulator up to there)",
+        return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (2^24: counts are exact in the f32 accumulator up to there)",
                      (long long)N, SBE_ASSOC_MAX_OBJECTS);
     if (F < 1 || F > SBE_ASSOC_MAX_FEATURES)
-        return afail(h, SBE_ERR_ARG, "n_features=%lld out of range [1, %d] (the [F][F] outputs take 25 bytes per entry)",
+        return fail(h, SBE_ERR_ARG, "n_features=%lld out of range [1, %d] (the [F][F] outputs take 25 bytes per entry)",
                      (long long)F, SBE_ASSOC_MAX_FEATURES);
     if (N * F > SBE_ASSOC_MAX_CODES)
-        return afail(h, SBE_ERR_ARG, "n_objects * n_features = %lld exceeds the limit of %lld (2^31) codes", (long long)(N * F),
+        return fail(h, SBE_ERR_ARG, "n_objects * n_features = %lld exceeds the limit of %lld (2^31) codes", (long long)(N * F),
                      (long long)SBE_ASSOC_MAX_CODES);
     int s_max = 1;
     for (int64_t f = 0; f < F; ++f) {
         if (n_states[f] < 1 || n_states[f] > SBE_ASSOC_MAX_STATES)
-            return afail(h, SBE_ERR_ARG, "n_states[%lld]=%d out of range [1, %d] (this unit's limit: a 32 x 32 tile holds whole pairs)",
+            return fail(h, SBE_ERR_ARG, "n_states[%lld]=%d out of range [1, %d] (this unit's limit: a 32 x 32 tile holds whole pairs)",
                          (long long)f, n_states[f], SBE_ASSOC_MAX_STATES);
         s_max = std::max(s_max, (int)n_states[f]);
     }
@@ -454,7 +388,7 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
             for (int64_t i = i0; i < i1; ++i) {
                 const uint8_t c = x[i * F + f];
                 if (c != SBE_ASSOC_NA && c >= ns)
-                    return afail(h, SBE_ERR_DATA, "x[%lld][%lld]=%d is neither below n_states[%lld]=%d nor %d (not observed)", (long long)i,
+                    return fail(h, SBE_ERR_DATA, "x[%lld][%lld]=%d is neither below n_states[%lld]=%d nor %d (not observed)", (long long)i,
                                  (long long)f, (int)c, (long long)f, ns, SBE_ASSOC_NA);
                 dst[i] = c;
             }
@@ -468,36 +402,36 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
         ? h->launch_tiles
         : std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / (n_pad / kStep)));
 
-    AHIP(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     h->F = 0;                                       // (until the new codes are in place)
-    int rc = ensure(h, h->d_xt, h->xt_bytes, xt.size());
+    int rc = unit_ensure(h, h->d_xt, h->xt_bytes, xt.size());
     if (rc) return rc;
     const size_t ff = (size_t)F * F;
-    if ((rc = ensure(h, h->d_out, h->out_bytes, ff * 25))) return rc;
+    if ((rc = unit_ensure(h, h->d_out, h->out_bytes, ff * 25))) return rc;
     double* d_stat = (double*)h->d_out;
     double* d_p = d_stat + ff;
     int32_t* d_dof = (int32_t*)(d_p + ff);
     int32_t* d_n = d_dof + ff;
     uint8_t* d_valid = (uint8_t*)(d_n + ff);
-    AHIP(h, hipMemcpyAsync(h->d_xt, xt.data(), xt.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_xt, xt.data(), xt.size(), hipMemcpyHostToDevice, h->stream));
     k_assoc_diagonal<<<div_up(F, 256), 256, 0, h->stream>>>((int)F, d_stat, d_p, d_dof, d_n, d_valid);
-    AHIP(h, hipGetLastError());
-    AHIP(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     int64_t launches = 0;
     for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch, ++launches) {          // one wave per tile pair
         const int64_t t_end = std::min(tile_pairs, t0 + per_launch);
         const PairArgs args{h->d_xt, n_pad, (int)F, log_s, t0, t_end, d_stat, d_p, d_dof, d_n, d_valid};
         k_assoc_pairs<<<(unsigned)(t_end - t0), 64, pair_lds_bytes(sub), h->stream>>>(args);
-        AHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
     }
-    AHIP(h, hipEventRecord(h->ev[1], h->stream));
-    AHIP(h, hipMemcpyAsync(statistic, d_stat, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipMemcpyAsync(pvalue, d_p, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipMemcpyAsync(dof, d_dof, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipMemcpyAsync(n, d_n, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipMemcpyAsync(valid, d_valid, ff, hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipStreamSynchronize(h->stream));
-    AHIP(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipMemcpyAsync(statistic, d_stat, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pvalue, d_p, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dof, d_dof, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(n, d_n, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(valid, d_valid, ff, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
     h->N = N;
     h->n_pad = n_pad;
     h->F = F;
@@ -509,51 +443,46 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
 }
 
 int sbe_assoc_tables(sbe_assoc* h, const int32_t* pairs, int64_t n_pairs, int32_t* out) {
-    ACHECK_HANDLE(h);
+    CHECK_HANDLE(h, kNullHandle);
     if (n_pairs < 0 || n_pairs > (int64_t)SBE_ASSOC_MAX_FEATURES * SBE_ASSOC_MAX_FEATURES)
-        return afail(h, SBE_ERR_ARG, "n_pairs=%lld out of range [0, %lld]", (long long)n_pairs,
+        return fail(h, SBE_ERR_ARG, "n_pairs=%lld out of range [0, %lld]", (long long)n_pairs,
                      (long long)SBE_ASSOC_MAX_FEATURES * SBE_ASSOC_MAX_FEATURES);
-    if (n_pairs > 0 && (!pairs || !out)) return afail(h, SBE_ERR_ARG, "null pointer argument: %s", !pairs ? "pairs" : "out");
-    if (h->F == 0) return afail(h, SBE_ERR_STATE, "sbe_assoc_tables needs the codes of a successful sbe_assoc_compute");
+    if (n_pairs > 0 && (!pairs || !out)) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !pairs ? "pairs" : "out");
+    if (h->F == 0) return fail(h, SBE_ERR_STATE, "sbe_assoc_tables needs the codes of a successful sbe_assoc_compute");
     for (int64_t p = 0; p < 2 * n_pairs; ++p)
         if (pairs[p] < 0 || pairs[p] >= h->F)
-            return afail(h, SBE_ERR_ARG, "pairs[%lld][%d]=%d out of range [0, %lld)", (long long)(p / 2), (int)(p & 1), pairs[p],
+            return fail(h, SBE_ERR_ARG, "pairs[%lld][%d]=%d out of range [0, %lld)", (long long)(p / 2), (int)(p & 1), pairs[p],
                          (long long)h->F);
     if (n_pairs == 0) return SBE_OK;
-    AHIP(h, hipSetDevice(h->device));
+    HIPCHK(h, hipSetDevice(h->device));
     const size_t cells = (size_t)h->s_max * h->s_max;
-    int rc = ensure(h, h->d_pairs, h->pairs_bytes, (size_t)n_pairs * 2 * sizeof(int32_t));
+    int rc = unit_ensure(h, h->d_pairs, h->pairs_bytes, (size_t)n_pairs * 2 * sizeof(int32_t));
     if (rc) return rc;
-    if ((rc = ensure(h, h->d_out, h->out_bytes, (size_t)n_pairs * cells * sizeof(int32_t)))) return rc;
-    AHIP(h, hipMemcpyAsync(h->d_pairs, pairs, (size_t)n_pairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = unit_ensure(h, h->d_out, h->out_bytes, (size_t)n_pairs * cells * sizeof(int32_t)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_pairs, pairs, (size_t)n_pairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     // a block walks all N objects of its pair: as many pairs per launch as the pair kernel's budget allows steps
     const int64_t per_launch = std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / (h->n_pad / kStep)));
     for (int64_t p0 = 0; p0 < n_pairs; p0 += per_launch) {
         k_assoc_table<<<(unsigned)std::min(per_launch, n_pairs - p0), kTableBlock, 0, h->stream>>>(h->d_xt, h->n_pad, h->N, h->d_pairs, p0,
                                                                                                h->s_max, (int32_t*)h->d_out);
-        AHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
     }
-    AHIP(h, hipMemcpyAsync(out, h->d_out, (size_t)n_pairs * cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    AHIP(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, h->d_out, (size_t)n_pairs * cells * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return SBE_OK;
 }
 
 int sbe_assoc_last_shape(const sbe_assoc* h, int32_t* s_pad_out, int64_t* tile_pairs_out, int64_t* launches_out) {
-    if (!h) return afail(nullptr, SBE_ERR_ARG, "null handle");
+    CHECK_HANDLE(h, kNullHandle);
     if (!s_pad_out || !tile_pairs_out || !launches_out)
-        return afail(const_cast<sbe_assoc*>(h), SBE_ERR_ARG, "null pointer argument: output");
-    if (h->F == 0) return afail(const_cast<sbe_assoc*>(h), SBE_ERR_STATE, "no successful sbe_assoc_compute yet");
+        return fail(h, SBE_ERR_ARG, "null pointer argument: output");
+    if (h->F == 0) return fail(h, SBE_ERR_STATE, "no successful sbe_assoc_compute yet");
     *s_pad_out = h->s_pad;
     *tile_pairs_out = h->tile_pairs;
     *launches_out = h->launches;
     return SBE_OK;
 }
 
-int sbe_assoc_last_kernel_ms(const sbe_assoc* h, float* ms_out) {
-    if (!h) return afail(nullptr, SBE_ERR_ARG, "null handle");
-    if (!ms_out) return afail(const_cast<sbe_assoc*>(h), SBE_ERR_ARG, "null pointer argument: ms_out");
-    *ms_out = h->last_kernel_ms;
-    return SBE_OK;
-}
+int sbe_assoc_last_kernel_ms(const sbe_assoc* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
 
 }  // extern "C"

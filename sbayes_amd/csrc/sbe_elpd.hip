@@ -18,12 +18,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 #include <vector>
 
-#include "sbe_engine_internal.hip.h"
+#include "sbe_unit.hip.h"
+#include "sbe_engine_internal.hip.h"   // sbe_elpd_append_engine reads the engine's row on the device
 #include "../../include/sbe_elpd.h"
 
 namespace {
@@ -363,14 +361,10 @@ __global__ __launch_bounds__(256) void k_elpd_store_row(const double* row, int64
     if (m < M) lh[m * cap + r] = (float)row[m];
 }
 
-thread_local std::string g_elpd_error;
-
 }  // namespace
 
-struct sbe_elpd_store {
-    int device = 0;
+struct sbe_elpd_store : sbe_unit_handle {     // (sbe_unit.hip.h; ev: around the column kernel of the last compute call)
     int64_t M = 0, cap = 0, n = 0;
-    hipStream_t stream = nullptr;
     float* d_lh = nullptr;              // [M][cap]
     float* d_stage = nullptr;           // host rows in flight / rows read back: up to kStageRows rows
     int32_t* d_cols = nullptr;          // [M]
@@ -378,49 +372,19 @@ struct sbe_elpd_store {
     double* d_out = nullptr;            // [4][M]
     int* d_bad = nullptr;
     int64_t stage_rows = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // around the column kernel of the last compute call
-    float last_kernel_ms = 0.0f;
-    std::string last_error;
+    std::vector<void*> buffers() const { return {d_lh, d_stage, d_cols, d_keep, d_out, d_bad}; }
 };
 
 namespace {
 
-int efail(sbe_elpd_store* st, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_elpd_error = buf;
-    if (st) st->last_error = buf;
-    return code;
-}
-
-#define EHIP(st, call)                                                                                     \
-    do {                                                                                                   \
-        hipError_t _err = (call);                                                                          \
-        if (_err != hipSuccess)                                                                            \
-            return efail(st, SBE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
-#define ECHECK_STORE(st) \
-    if (!(st)) return efail(nullptr, SBE_ERR_ARG, "null store handle")
+constexpr sbe_elpd_store* kNone = nullptr;           // (fail without a handle: the type names the unit)
+constexpr char kNullHandle[] = "null store handle";
 
 constexpr int64_t kStageBytes = (int64_t)64 << 20;    // host rows are moved in pieces of at most 64 MiB
 
 int ensure_stage(sbe_elpd_store* st) {
-    if (st->d_stage) return SBE_OK;
     st->stage_rows = std::max<int64_t>(1, std::min<int64_t>(st->cap, kStageBytes / ((int64_t)sizeof(float) * st->M)));
-    EHIP(st, hipMalloc((void**)&st->d_stage, (size_t)st->stage_rows * st->M * sizeof(float)));
-    return SBE_OK;
-}
-
-void release(sbe_elpd_store* st) {
-    if (st->stream) (void)hipStreamSynchronize(st->stream);
-    for (void* p : {(void*)st->d_lh, (void*)st->d_stage, (void*)st->d_cols, (void*)st->d_keep, (void*)st->d_out, (void*)st->d_bad})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t ev : st->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (st->stream) (void)hipStreamDestroy(st->stream);
+    return unit_ensure(st, st->d_stage, (size_t)st->stage_rows * st->M * sizeof(float));
 }
 
 }  // namespace
@@ -429,7 +393,7 @@ extern "C" {
 
 int sbe_elpd_abi_version(void) { return SBE_ELPD_ABI_VERSION; }
 
-const char* sbe_elpd_last_error(const sbe_elpd_store* st) { return st ? st->last_error.c_str() : g_elpd_error.c_str(); }
+const char* sbe_elpd_last_error(const sbe_elpd_store* st) { return unit_last_error(st); }
 
 int64_t sbe_elpd_lds_max_samples(void) {
     static const int64_t v = lds_max_samples();
@@ -437,32 +401,21 @@ int64_t sbe_elpd_lds_max_samples(void) {
 }
 
 int sbe_elpd_create(sbe_elpd_store** out, int device, int64_t n_columns, int64_t capacity) {
-    if (!out) return efail(nullptr, SBE_ERR_ARG, "null pointer argument: out");
+    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
     *out = nullptr;
     if (n_columns < 1 || n_columns > INT32_MAX)
-        return efail(nullptr, SBE_ERR_ARG, "n_columns=%lld out of range [1, %d]", (long long)n_columns, INT32_MAX);
-    if (capacity < 1) return efail(nullptr, SBE_ERR_ARG, "capacity=%lld must be positive", (long long)capacity);
-    if (device < 0) return efail(nullptr, SBE_ERR_ARG, "device %d out of range", device);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return efail(nullptr, SBE_ERR_NODEVICE, "no usable GPU (hipGetDeviceCount reports none); there is no CPU fallback");
-    if (device >= count) return efail(nullptr, SBE_ERR_ARG, "device %d out of range [0,%d)", device, count);
-    sbe_elpd_store* st = new sbe_elpd_store();
-    st->device = device;
+        return fail(kNone, SBE_ERR_ARG, "n_columns=%lld out of range [1, %d]", (long long)n_columns, INT32_MAX);
+    if (capacity < 1) return fail(kNone, SBE_ERR_ARG, "capacity=%lld must be positive", (long long)capacity);
+    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
+    char shape[96];
+    snprintf(shape, sizeof shape, " (%lld x %lld float32 store)", (long long)n_columns, (long long)capacity);
+    sbe_elpd_store* st = nullptr;
+    const int rc = unit_open(st, device, "sbe_elpd_create", shape);
+    if (rc) return rc;
     st->M = n_columns;
     st->cap = capacity;
-    auto bail = [&](hipError_t err, const char* what) {
-        efail(nullptr, SBE_ERR_HIP, "sbe_elpd_create: %s failed: %s (%lld x %lld float32 store)", what, hipGetErrorString(err),
-              (long long)n_columns, (long long)capacity);
-        release(st);
-        delete st;
-        return SBE_ERR_HIP;
-    };
+    auto bail = [&](hipError_t err, const char* what) { return unit_create_failed(st, "sbe_elpd_create", what, err, shape); };
     hipError_t err;
-    if ((err = hipSetDevice(device)) != hipSuccess) return bail(err, "hipSetDevice");
-    if ((err = hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking)) != hipSuccess) return bail(err, "hipStreamCreate");
-    for (hipEvent_t& ev : st->ev)
-        if ((err = hipEventCreate(&ev)) != hipSuccess) return bail(err, "hipEventCreate");
     if ((err = hipMalloc((void**)&st->d_lh, (size_t)n_columns * capacity * sizeof(float))) != hipSuccess) return bail(err, "hipMalloc");
     if ((err = hipMalloc((void**)&st->d_cols, (size_t)n_columns * sizeof(int32_t))) != hipSuccess) return bail(err, "hipMalloc");
     if ((err = hipMalloc((void**)&st->d_keep, (size_t)n_columns)) != hipSuccess) return bail(err, "hipMalloc");
@@ -472,70 +425,59 @@ int sbe_elpd_create(sbe_elpd_store** out, int device, int64_t n_columns, int64_t
     return SBE_OK;
 }
 
-int sbe_elpd_destroy(sbe_elpd_store* st) {
-    ECHECK_STORE(st);
-    (void)hipSetDevice(st->device);
-    release(st);
-    delete st;
-    return SBE_OK;
-}
+int sbe_elpd_destroy(sbe_elpd_store* st) { return unit_destroy(st, kNullHandle); }
 
 int sbe_elpd_n_rows(const sbe_elpd_store* st, int64_t* n_rows_out) {
-    if (!st) return efail(nullptr, SBE_ERR_ARG, "null store handle");
-    if (!n_rows_out) return efail(const_cast<sbe_elpd_store*>(st), SBE_ERR_ARG, "null pointer argument: n_rows_out");
+    CHECK_HANDLE(st, kNullHandle);
+    if (!n_rows_out) return fail(st, SBE_ERR_ARG, "null pointer argument: n_rows_out");
     *n_rows_out = st->n;
     return SBE_OK;
 }
 
-int sbe_elpd_last_kernel_ms(const sbe_elpd_store* st, float* ms_out) {
-    if (!st) return efail(nullptr, SBE_ERR_ARG, "null store handle");
-    if (!ms_out) return efail(const_cast<sbe_elpd_store*>(st), SBE_ERR_ARG, "null pointer argument: ms_out");
-    *ms_out = st->last_kernel_ms;
-    return SBE_OK;
-}
+int sbe_elpd_last_kernel_ms(const sbe_elpd_store* st, float* ms_out) { return unit_last_kernel_ms(st, ms_out, kNullHandle); }
 
 int sbe_elpd_reset(sbe_elpd_store* st) {
-    ECHECK_STORE(st);
+    CHECK_HANDLE(st, kNullHandle);
     st->n = 0;
     return SBE_OK;
 }
 
 int sbe_elpd_append_rows(sbe_elpd_store* st, const float* rows, int64_t n_rows) {
-    ECHECK_STORE(st);
-    if (n_rows < 0) return efail(st, SBE_ERR_ARG, "n_rows=%lld is negative", (long long)n_rows);
-    if (n_rows > 0 && !rows) return efail(st, SBE_ERR_ARG, "null pointer argument: rows");
+    CHECK_HANDLE(st, kNullHandle);
+    if (n_rows < 0) return fail(st, SBE_ERR_ARG, "n_rows=%lld is negative", (long long)n_rows);
+    if (n_rows > 0 && !rows) return fail(st, SBE_ERR_ARG, "null pointer argument: rows");
     if (st->n + n_rows > st->cap)
-        return efail(st, SBE_ERR_ARG, "store overflow: %lld rows + %lld exceed the capacity of %lld rows", (long long)st->n,
+        return fail(st, SBE_ERR_ARG, "store overflow: %lld rows + %lld exceed the capacity of %lld rows", (long long)st->n,
                      (long long)n_rows, (long long)st->cap);
     if (n_rows == 0) return SBE_OK;
-    EHIP(st, hipSetDevice(st->device));
+    HIPCHK(st, hipSetDevice(st->device));
     int rc = ensure_stage(st);
     if (rc) return rc;
     for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
         const int64_t k = std::min(st->stage_rows, n_rows - r);
-        EHIP(st, hipMemcpyAsync(st->d_stage, rows + r * st->M, (size_t)k * st->M * sizeof(float), hipMemcpyHostToDevice, st->stream));
+        HIPCHK(st, hipMemcpyAsync(st->d_stage, rows + r * st->M, (size_t)k * st->M * sizeof(float), hipMemcpyHostToDevice, st->stream));
         const int64_t tiles = (st->M + 31) / 32;
         for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
             const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
             k_elpd_transpose<<<grid, 256, 0, st->stream>>>(st->d_stage, k, st->M, st->d_lh, st->cap, st->n + r, t0);
-            EHIP(st, hipGetLastError());
+            HIPCHK(st, hipGetLastError());
         }
     }
-    EHIP(st, hipStreamSynchronize(st->stream));
+    HIPCHK(st, hipStreamSynchronize(st->stream));
     st->n += n_rows;
     return SBE_OK;
 }
 
 int sbe_elpd_append_engine(sbe_elpd_store* st, sbe_engine* e, int slot) {
-    ECHECK_STORE(st);
-    if (!e) return efail(st, SBE_ERR_ARG, "null engine handle");
-    if (slot < 0 || slot >= e->n_slots) return efail(st, SBE_ERR_ARG, "slot %d out of range [0,%d)", slot, e->n_slots);
+    CHECK_HANDLE(st, kNullHandle);
+    if (!e) return fail(st, SBE_ERR_ARG, "null engine handle");
+    if (slot < 0 || slot >= e->n_slots) return fail(st, SBE_ERR_ARG, "slot %d out of range [0,%d)", slot, e->n_slots);
     if (e->device != st->device)
-        return efail(st, SBE_ERR_ARG, "the store lives on device %d, the engine on device %d", st->device, e->device);
+        return fail(st, SBE_ERR_ARG, "the store lives on device %d, the engine on device %d", st->device, e->device);
     if ((int64_t)e->N * e->F != st->M)
-        return efail(st, SBE_ERR_ARG, "the store has %lld columns, the engine's rows have N*F = %lld", (long long)st->M,
+        return fail(st, SBE_ERR_ARG, "the store has %lld columns, the engine's rows have N*F = %lld", (long long)st->M,
                      (long long)e->N * e->F);
-    if (st->n + 1 > st->cap) return efail(st, SBE_ERR_ARG, "store overflow: capacity of %lld rows reached", (long long)st->cap);
+    if (st->n + 1 > st->cap) return fail(st, SBE_ERR_ARG, "store overflow: capacity of %lld rows reached", (long long)st->cap);
     int rc = enqueue_lh_exact(e, slot, "sbe_elpd_append_engine");
     if (rc == SBE_OK) {
         k_elpd_store_row<<<div_up(st->M, 256), 256, 0, e->stream>>>((const double*)e->d_scratch, st->M, st->d_lh, st->cap, st->n);
@@ -543,19 +485,19 @@ int sbe_elpd_append_engine(sbe_elpd_store* st, sbe_engine* e, int slot) {
         if (err != hipSuccess) rc = fail(e, SBE_ERR_HIP, "k_elpd_store_row launch: %s", hipGetErrorString(err));
     }
     if (rc == SBE_OK) rc = lh_exact_report(e);            // the engine's stream wait and its status word: nothing else is read back
-    if (rc) return efail(st, rc, "%s", e->last_error.c_str());
+    if (rc) return fail(st, rc, "%s", e->last_error.c_str());
     ++st->n;
     return SBE_OK;
 }
 
 int sbe_elpd_get_rows(sbe_elpd_store* st, int64_t row0, int64_t n_rows, float* out) {
-    ECHECK_STORE(st);
+    CHECK_HANDLE(st, kNullHandle);
     if (row0 < 0 || n_rows < 0 || row0 + n_rows > st->n)
-        return efail(st, SBE_ERR_ARG, "rows [%lld, %lld) out of range [0, %lld)", (long long)row0, (long long)(row0 + n_rows),
+        return fail(st, SBE_ERR_ARG, "rows [%lld, %lld) out of range [0, %lld)", (long long)row0, (long long)(row0 + n_rows),
                      (long long)st->n);
-    if (n_rows > 0 && !out) return efail(st, SBE_ERR_ARG, "null pointer argument: out");
+    if (n_rows > 0 && !out) return fail(st, SBE_ERR_ARG, "null pointer argument: out");
     if (n_rows == 0) return SBE_OK;
-    EHIP(st, hipSetDevice(st->device));
+    HIPCHK(st, hipSetDevice(st->device));
     int rc = ensure_stage(st);
     if (rc) return rc;
     for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
@@ -564,27 +506,27 @@ int sbe_elpd_get_rows(sbe_elpd_store* st, int64_t row0, int64_t n_rows, float* o
         for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
             const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
             k_elpd_untranspose<<<grid, 256, 0, st->stream>>>(st->d_lh, st->cap, row0 + r, k, st->M, st->d_stage, t0);
-            EHIP(st, hipGetLastError());
+            HIPCHK(st, hipGetLastError());
         }
-        EHIP(st, hipMemcpyAsync(out + r * st->M, st->d_stage, (size_t)k * st->M * sizeof(float), hipMemcpyDeviceToHost, st->stream));
-        EHIP(st, hipStreamSynchronize(st->stream));
+        HIPCHK(st, hipMemcpyAsync(out + r * st->M, st->d_stage, (size_t)k * st->M * sizeof(float), hipMemcpyDeviceToHost, st->stream));
+        HIPCHK(st, hipStreamSynchronize(st->stream));
     }
     return SBE_OK;
 }
 
 int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_values, int na_isclose,
                      double* loo_i, double* k_i, double* lppd_i, double* v_i, int64_t* n_kept_out) {
-    ECHECK_STORE(st);
-    if (!loo_i || !k_i || !lppd_i || !v_i || !n_kept_out) return efail(st, SBE_ERR_ARG, "null pointer argument: output");
+    CHECK_HANDLE(st, kNullHandle);
+    if (!loo_i || !k_i || !lppd_i || !v_i || !n_kept_out) return fail(st, SBE_ERR_ARG, "null pointer argument: output");
     if (burn_rows < 0 || burn_rows >= st->n)
-        return efail(st, SBE_ERR_ARG, "burn_rows=%lld out of range [0, %lld) (rows stored: %lld)", (long long)burn_rows,
+        return fail(st, SBE_ERR_ARG, "burn_rows=%lld out of range [0, %lld) (rows stored: %lld)", (long long)burn_rows,
                      (long long)st->n, (long long)st->n);
     const int64_t s = st->n - burn_rows;
     if (s < SBE_ELPD_MIN_SAMPLES || s > SBE_ELPD_MAX_SAMPLES)
-        return efail(st, SBE_ERR_ARG, "%lld samples after burn-in; PSIS needs %d .. %d (2^20) per observation", (long long)s,
+        return fail(st, SBE_ERR_ARG, "%lld samples after burn-in; PSIS needs %d .. %d (2^20) per observation", (long long)s,
                      SBE_ELPD_MIN_SAMPLES, SBE_ELPD_MAX_SAMPLES);
     *n_kept_out = 0;
-    EHIP(st, hipSetDevice(st->device));
+    HIPCHK(st, hipSetDevice(st->device));
     std::vector<uint8_t> keep((size_t)st->M, 1);
     if (na_values) {
         for (int64_t m = 0; m < st->M; ++m) keep[m] = na_values[m] == 0;
@@ -593,10 +535,10 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
         for (int64_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
             k_elpd_isclose<<<(unsigned)std::min(kMaxGridBlocks, blocks - b0), 256, 0, st->stream>>>(st->d_lh, st->cap, st->n, st->M,
                                                                                                  st->d_keep, b0 * 4);
-            EHIP(st, hipGetLastError());
+            HIPCHK(st, hipGetLastError());
         }
-        EHIP(st, hipMemcpyAsync(keep.data(), st->d_keep, (size_t)st->M, hipMemcpyDeviceToHost, st->stream));
-        EHIP(st, hipStreamSynchronize(st->stream));
+        HIPCHK(st, hipMemcpyAsync(keep.data(), st->d_keep, (size_t)st->M, hipMemcpyDeviceToHost, st->stream));
+        HIPCHK(st, hipStreamSynchronize(st->stream));
     }
     std::vector<int32_t> cols;
     cols.reserve((size_t)st->M);
@@ -607,24 +549,24 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
     const bool staged = column_staged(s);
     const int tn = tail_count(s), tp = pow2_at_least(std::max(tn, 1));
     const size_t lds = (staged ? (size_t)s * sizeof(uint32_t) : 0) + tail_lds_bytes(s);
-    EHIP(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
-    EHIP(st, hipMemcpyAsync(st->d_cols, cols.data(), (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st->stream));
-    EHIP(st, hipMemsetAsync(st->d_bad, 0, sizeof(int), st->stream));
-    EHIP(st, hipEventRecord(st->ev[0], st->stream));
+    HIPCHK(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
+    HIPCHK(st, hipMemcpyAsync(st->d_cols, cols.data(), (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st->stream));
+    HIPCHK(st, hipMemsetAsync(st->d_bad, 0, sizeof(int), st->stream));
+    HIPCHK(st, hipEventRecord(st->ev[0], st->stream));
     for (int64_t j0 = 0; j0 < nk; j0 += kMaxGridBlocks) {                  // one workgroup per kept column
         const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, j0, st->d_bad};
         k_elpd_column<<<(unsigned)std::min(kMaxGridBlocks, nk - j0), kElpdBlock, lds, st->stream>>>(args);
-        EHIP(st, hipGetLastError());
+        HIPCHK(st, hipGetLastError());
     }
-    EHIP(st, hipEventRecord(st->ev[1], st->stream));
+    HIPCHK(st, hipEventRecord(st->ev[1], st->stream));
     int bad = 0;
-    EHIP(st, hipMemcpyAsync(&bad, st->d_bad, sizeof(int), hipMemcpyDeviceToHost, st->stream));
+    HIPCHK(st, hipMemcpyAsync(&bad, st->d_bad, sizeof(int), hipMemcpyDeviceToHost, st->stream));
     double* outs[4] = {loo_i, k_i, lppd_i, v_i};
     for (int q = 0; q < 4; ++q)
-        EHIP(st, hipMemcpyAsync(outs[q], st->d_out + q * nk, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, st->stream));
-    EHIP(st, hipStreamSynchronize(st->stream));
-    EHIP(st, hipEventElapsedTime(&st->last_kernel_ms, st->ev[0], st->ev[1]));
-    if (bad) return efail(st, SBE_ERR_DATA, "%d observation column%s hold likelihood values that are not positive and finite "
+        HIPCHK(st, hipMemcpyAsync(outs[q], st->d_out + q * nk, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, st->stream));
+    HIPCHK(st, hipStreamSynchronize(st->stream));
+    HIPCHK(st, hipEventElapsedTime(&st->last_kernel_ms, st->ev[0], st->ev[1]));
+    if (bad) return fail(st, SBE_ERR_DATA, "%d observation column%s hold likelihood values that are not positive and finite "
                           "in rows [%lld, %lld)", bad, bad == 1 ? "" : "s", (long long)burn_rows, (long long)st->n);
     *n_kept_out = nk;
     return SBE_OK;

@@ -13,13 +13,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
-#include "sbe_engine_internal.hip.h"
+#include "sbe_unit.hip.h"
 #include "../../include/sbe_em.h"
 
 namespace {
@@ -160,14 +157,10 @@ __global__ __launch_bounds__(kEmBlock) void k_em_update(const double* __restrict
     if (!(s > 0.0) || !isfinite(s) || !isfinite(m)) atomicOr(status, 1);
 }
 
-thread_local std::string g_em_error;
-
 }  // namespace
 
-struct sbe_em {
-    int device = 0;
+struct sbe_em : sbe_unit_handle {       // (sbe_unit.hip.h; ev: around the steps of the last run)
     int64_t N = 0, F = 0, S = 0, G = 0, K = 0;
-    hipStream_t stream = nullptr;
     uint8_t* d_xt = nullptr;            // [F][N] state index, NA = S
     int32_t* d_perm = nullptr;          // [F][N] objects ordered by state, ascending n within a state
     int32_t* d_off = nullptr;           // [F][S+1] start of each state's objects in d_perm (bucket S = NA is not summed)
@@ -183,62 +176,36 @@ struct sbe_em {
     double* d_fill = nullptr;
     bool geo = false;
     double scale = 0.0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    float last_kernel_ms = 0.0f;
-    std::string last_error;
+    std::vector<void*> buffers() const {
+        return {d_xt, d_perm, d_off, d_app, d_avail, d_z, d_logp, d_ll, d_status, d_cost, d_zp, d_geo, d_fill};
+    }
 };
 
 namespace {
 
-int mfail(sbe_em* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_em_error = buf;
-    if (h) h->last_error = buf;
-    return code;
-}
-
-#define MHIP(h, call)                                                                                      \
-    do {                                                                                                   \
-        hipError_t _err = (call);                                                                          \
-        if (_err != hipSuccess)                                                                            \
-            return mfail(h, SBE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), __FILE__, __LINE__); \
-    } while (0)
-
-void release(sbe_em* h) {
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_xt, (void*)h->d_perm, (void*)h->d_off, (void*)h->d_app, (void*)h->d_avail, (void*)h->d_z,
-                    (void*)h->d_logp, (void*)h->d_ll, (void*)h->d_status, (void*)h->d_cost, (void*)h->d_zp, (void*)h->d_geo,
-                    (void*)h->d_fill})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t ev : h->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-}
+constexpr sbe_em* kNone = nullptr;                   // (fail without a handle: the type names the unit)
+constexpr char kNullHandle[] = "null EM handle";
 
 int enqueue_step(sbe_em* h, double t) {
     const unsigned n_tiles = (unsigned)div_up(h->N, kEmBlock);
     k_em_table<<<dim3((unsigned)h->F, (unsigned)h->G), kEmTableThreads, 0, h->stream>>>(h->d_z, h->d_perm, h->d_off, h->d_app, h->N,
                                                                                         (int)h->F, (int)h->S, h->d_logp);
-    MHIP(h, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     k_em_ll<<<dim3(n_tiles, (unsigned)h->G), kEmBlock, 0, h->stream>>>(h->d_logp, h->d_xt, h->d_avail, h->N, (int)h->F, (int)h->S,
                                                                        h->d_ll);
-    MHIP(h, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     if (h->geo) {
         k_em_peaky<<<(unsigned)h->K, kEmBlock, 0, h->stream>>>(h->d_z, h->N, h->d_zp);
-        MHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
         k_em_geo<<<dim3(n_tiles, (unsigned)div_up(h->K, kEmGeoRows)), kEmBlock, 0, h->stream>>>(h->d_zp, h->d_cost, h->N, (int)h->K,
                                                                                                  h->scale, h->d_geo);
-        MHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
         k_em_fill<<<1, kEmBlock, 0, h->stream>>>(h->d_geo, h->K * h->N, h->d_fill);
-        MHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
     }
     k_em_update<<<n_tiles, kEmBlock, 0, h->stream>>>(h->d_ll, h->d_avail, h->geo ? h->d_geo : nullptr, h->d_fill, h->N, (int)h->G,
                                                       (int)h->K, t, h->d_z, h->d_status);
-    MHIP(h, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     return SBE_OK;
 }
 
@@ -248,24 +215,24 @@ extern "C" {
 
 int sbe_em_abi_version(void) { return SBE_EM_ABI_VERSION; }
 
-const char* sbe_em_last_error(const sbe_em* h) { return h ? h->last_error.c_str() : g_em_error.c_str(); }
+const char* sbe_em_last_error(const sbe_em* h) { return unit_last_error(h); }
 
 int sbe_em_create(sbe_em** out, int device, int64_t n_objects, int64_t n_features, int64_t n_states, const uint8_t* state_idx,
                   const uint8_t* applicable, int64_t n_groups, int64_t n_clusters, const uint8_t* groups_available) {
-    if (!out) return mfail(nullptr, SBE_ERR_ARG, "null pointer argument: out");
+    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
     *out = nullptr;
     const int64_t N = n_objects, F = n_features, S = n_states, G = n_groups, K = n_clusters;
     if (N < 1 || N > SBE_EM_MAX_OBJECTS)
-        return mfail(nullptr, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d]", (long long)N, SBE_EM_MAX_OBJECTS);
+        return fail(kNone, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d]", (long long)N, SBE_EM_MAX_OBJECTS);
     if (F < 1 || F > SBE_EM_MAX_FEATURES)
-        return mfail(nullptr, SBE_ERR_ARG, "n_features=%lld out of range [1, %d]", (long long)F, SBE_EM_MAX_FEATURES);
+        return fail(kNone, SBE_ERR_ARG, "n_features=%lld out of range [1, %d]", (long long)F, SBE_EM_MAX_FEATURES);
     if (S < 1 || S > SBE_EM_MAX_STATES)
-        return mfail(nullptr, SBE_ERR_ARG, "n_states=%lld out of range [1, %d]", (long long)S, SBE_EM_MAX_STATES);
+        return fail(kNone, SBE_ERR_ARG, "n_states=%lld out of range [1, %d]", (long long)S, SBE_EM_MAX_STATES);
     if (G < 1 || G > SBE_EM_MAX_GROUPS)
-        return mfail(nullptr, SBE_ERR_ARG, "n_groups=%lld out of range [1, %d]", (long long)G, SBE_EM_MAX_GROUPS);
-    if (K < 1 || K > G) return mfail(nullptr, SBE_ERR_ARG, "n_clusters=%lld out of range [1, n_groups=%lld]", (long long)K, (long long)G);
-    if (!state_idx || !applicable || !groups_available) return mfail(nullptr, SBE_ERR_ARG, "null pointer argument: data");
-    if (device < 0) return mfail(nullptr, SBE_ERR_ARG, "device %d out of range", device);
+        return fail(kNone, SBE_ERR_ARG, "n_groups=%lld out of range [1, %d]", (long long)G, SBE_EM_MAX_GROUPS);
+    if (K < 1 || K > G) return fail(kNone, SBE_ERR_ARG, "n_clusters=%lld out of range [1, n_groups=%lld]", (long long)K, (long long)G);
+    if (!state_idx || !applicable || !groups_available) return fail(kNone, SBE_ERR_ARG, "null pointer argument: data");
+    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
     // data checks and the per-feature object lists (host, before any device call)
     std::vector<uint8_t> xt((size_t)(F * N));
     std::vector<int32_t> off((size_t)(F * (S + 1))), perm((size_t)(F * N));
@@ -273,12 +240,12 @@ int sbe_em_create(sbe_em** out, int device, int64_t n_objects, int64_t n_feature
     for (int64_t f = 0; f < F; ++f) {
         bool any = false;
         for (int64_t s = 0; s < S; ++s) any |= applicable[f * S + s] != 0;
-        if (!any) return mfail(nullptr, SBE_ERR_DATA, "feature %lld has no applicable state", (long long)f);
+        if (!any) return fail(kNone, SBE_ERR_DATA, "feature %lld has no applicable state", (long long)f);
         std::fill(cnt.begin(), cnt.end(), 0);
         for (int64_t i = 0; i < N; ++i) {
             const uint8_t x = state_idx[i * F + f];
             if (x > S)
-                return mfail(nullptr, SBE_ERR_DATA, "state_idx[%lld][%lld] = %d exceeds n_states=%lld (NA is n_states)", (long long)i,
+                return fail(kNone, SBE_ERR_DATA, "state_idx[%lld][%lld] = %d exceeds n_states=%lld (NA is n_states)", (long long)i,
                              (long long)f, (int)x, (long long)S);
             xt[(size_t)(f * N + i)] = x;
             ++cnt[x];
@@ -297,30 +264,19 @@ int sbe_em_create(sbe_em** out, int device, int64_t n_objects, int64_t n_feature
     for (int64_t i = 0; i < N; ++i) {
         bool any = false;
         for (int64_t g = 0; g < G && !any; ++g) any = groups_available[g * N + i] != 0;
-        if (!any) return mfail(nullptr, SBE_ERR_DATA, "object %lld has no available group", (long long)i);
+        if (!any) return fail(kNone, SBE_ERR_DATA, "object %lld has no available group", (long long)i);
     }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-        return mfail(nullptr, SBE_ERR_NODEVICE, "no usable GPU (hipGetDeviceCount reports none); there is no CPU fallback");
-    if (device >= count) return mfail(nullptr, SBE_ERR_ARG, "device %d out of range [0,%d)", device, count);
-    sbe_em* h = new sbe_em();
-    h->device = device;
+    char shape[96];
+    snprintf(shape, sizeof shape, " (N=%lld F=%lld S=%lld G=%lld)", (long long)N, (long long)F, (long long)S, (long long)G);
+    sbe_em* h = nullptr;
+    const int rc = unit_open(h, device, "sbe_em_create", shape);
+    if (rc) return rc;
     h->N = N, h->F = F, h->S = S, h->G = G, h->K = K;
-    auto bail = [&](hipError_t err, const char* what) {
-        mfail(nullptr, SBE_ERR_HIP, "sbe_em_create: %s failed: %s (N=%lld F=%lld S=%lld G=%lld)", what, hipGetErrorString(err),
-              (long long)N, (long long)F, (long long)S, (long long)G);
-        release(h);
-        delete h;
-        return SBE_ERR_HIP;
-    };
+    auto bail = [&](hipError_t err, const char* what) { return unit_create_failed(h, "sbe_em_create", what, err, shape); };
     std::vector<uint8_t> app((size_t)(F * S)), avail((size_t)(G * N));
     for (int64_t q = 0; q < F * S; ++q) app[(size_t)q] = applicable[q] != 0;
     for (int64_t q = 0; q < G * N; ++q) avail[(size_t)q] = groups_available[q] != 0;
     hipError_t err;
-    if ((err = hipSetDevice(device)) != hipSuccess) return bail(err, "hipSetDevice");
-    if ((err = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(err, "hipStreamCreate");
-    for (hipEvent_t& ev : h->ev)
-        if ((err = hipEventCreate(&ev)) != hipSuccess) return bail(err, "hipEventCreate");
     struct { void** p; size_t bytes; const void* src; } bufs[] = {
         {(void**)&h->d_xt, (size_t)(F * N), xt.data()},
         {(void**)&h->d_perm, (size_t)(F * N) * sizeof(int32_t), perm.data()},
@@ -342,71 +298,64 @@ int sbe_em_create(sbe_em** out, int device, int64_t n_objects, int64_t n_feature
     return SBE_OK;
 }
 
-int sbe_em_destroy(sbe_em* h) {
-    if (!h) return mfail(nullptr, SBE_ERR_ARG, "null EM handle");
-    (void)hipSetDevice(h->device);
-    release(h);
-    delete h;
-    return SBE_OK;
-}
+int sbe_em_destroy(sbe_em* h) { return unit_destroy(h, kNullHandle); }
 
 int sbe_em_set_geo_cost(sbe_em* h, const double* cost, double scale) {
-    if (!h) return mfail(nullptr, SBE_ERR_ARG, "null EM handle");
+    CHECK_HANDLE(h, kNullHandle);
     if (!cost) {
         h->geo = false;
         return SBE_OK;
     }
-    if (!(scale > 0.0) || !std::isfinite(scale)) return mfail(h, SBE_ERR_ARG, "scale=%g must be positive and finite", scale);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(h, SBE_ERR_ARG, "scale=%g must be positive and finite", scale);
     const int64_t bytes = h->N * h->N * (int64_t)sizeof(double);
     if (bytes > SBE_EM_MAX_COST_BYTES)
-        return mfail(h, SBE_ERR_ARG, "the cost matrix of N=%lld objects needs %lld bytes; the limit is %lld (N <= 32768)",
+        return fail(h, SBE_ERR_ARG, "the cost matrix of N=%lld objects needs %lld bytes; the limit is %lld (N <= 32768)",
                      (long long)h->N, (long long)bytes, (long long)SBE_EM_MAX_COST_BYTES);
     for (int64_t q = 0; q < h->N * h->N; ++q)
         if (!std::isfinite(cost[q]))
-            return mfail(h, SBE_ERR_DATA, "cost[%lld][%lld] = %g is not finite", (long long)(q / h->N), (long long)(q % h->N), cost[q]);
-    MHIP(h, hipSetDevice(h->device));
-    if (!h->d_cost) {
-        MHIP(h, hipMalloc((void**)&h->d_cost, (size_t)bytes));
-        MHIP(h, hipMalloc((void**)&h->d_zp, (size_t)(h->K * h->N) * sizeof(double)));
-        MHIP(h, hipMalloc((void**)&h->d_geo, (size_t)(h->K * h->N) * sizeof(double)));
-        MHIP(h, hipMalloc((void**)&h->d_fill, sizeof(double)));
-    }
-    MHIP(h, hipMemcpyAsync(h->d_cost, cost, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
-    MHIP(h, hipStreamSynchronize(h->stream));
+            return fail(h, SBE_ERR_DATA, "cost[%lld][%lld] = %g is not finite", (long long)(q / h->N), (long long)(q % h->N), cost[q]);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t kn_bytes = (size_t)(h->K * h->N) * sizeof(double);
+    int rc;                                           // (each buffer on its own: one that failed is tried again by the next call)
+    if ((rc = unit_ensure(h, h->d_cost, (size_t)bytes)) || (rc = unit_ensure(h, h->d_zp, kn_bytes)) ||
+        (rc = unit_ensure(h, h->d_geo, kn_bytes)) || (rc = unit_ensure(h, h->d_fill, sizeof(double))))
+        return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_cost, cost, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     h->geo = true;
     h->scale = scale;
     return SBE_OK;
 }
 
 int sbe_em_run(sbe_em* h, const double* z_in, int64_t n_steps, const double* temperatures, double* z_out) {
-    if (!h) return mfail(nullptr, SBE_ERR_ARG, "null EM handle");
-    if (!z_in || !z_out) return mfail(h, SBE_ERR_ARG, "null pointer argument: z_in / z_out");
+    CHECK_HANDLE(h, kNullHandle);
+    if (!z_in || !z_out) return fail(h, SBE_ERR_ARG, "null pointer argument: z_in / z_out");
     if (n_steps < 0 || n_steps > SBE_EM_MAX_STEPS)
-        return mfail(h, SBE_ERR_ARG, "n_steps=%lld out of range [0, %d]", (long long)n_steps, SBE_EM_MAX_STEPS);
-    if (n_steps > 0 && !temperatures) return mfail(h, SBE_ERR_ARG, "null pointer argument: temperatures");
+        return fail(h, SBE_ERR_ARG, "n_steps=%lld out of range [0, %d]", (long long)n_steps, SBE_EM_MAX_STEPS);
+    if (n_steps > 0 && !temperatures) return fail(h, SBE_ERR_ARG, "null pointer argument: temperatures");
     for (int64_t i = 0; i < n_steps; ++i)
         if (!(temperatures[i] > 0.0) || !std::isfinite(temperatures[i]))
-            return mfail(h, SBE_ERR_ARG, "temperatures[%lld] = %g must be positive and finite", (long long)i, temperatures[i]);
+            return fail(h, SBE_ERR_ARG, "temperatures[%lld] = %g must be positive and finite", (long long)i, temperatures[i]);
     const int64_t N = h->N, G = h->G;
     for (int64_t i = 0; i < N; ++i) {
         double s = 0.0;
         for (int64_t g = 0; g < G; ++g) {
             const double v = z_in[g * N + i];
             if (!std::isfinite(v))
-                return mfail(h, SBE_ERR_DATA, "z_in[%lld][%lld] = %g is not finite", (long long)g, (long long)i, v);
+                return fail(h, SBE_ERR_DATA, "z_in[%lld][%lld] = %g is not finite", (long long)g, (long long)i, v);
             s += v;
         }
-        if (s == 0.0) return mfail(h, SBE_ERR_DATA, "column %lld of z_in sums to 0", (long long)i);
+        if (s == 0.0) return fail(h, SBE_ERR_DATA, "column %lld of z_in sums to 0", (long long)i);
     }
     if (n_steps == 0) {
         if (z_out != z_in) std::memmove(z_out, z_in, (size_t)(G * N) * sizeof(double));
         h->last_kernel_ms = 0.0f;
         return SBE_OK;
     }
-    MHIP(h, hipSetDevice(h->device));
-    MHIP(h, hipMemcpyAsync(h->d_z, z_in, (size_t)(G * N) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    MHIP(h, hipMemsetAsync(h->d_status, 0, sizeof(int), h->stream));
-    MHIP(h, hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(h->d_z, z_in, (size_t)(G * N) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_status, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     for (int64_t i = 0; i < n_steps; ++i) {
         const int rc = enqueue_step(h, temperatures[i]);
         if (rc) {
@@ -414,22 +363,17 @@ int sbe_em_run(sbe_em* h, const double* z_in, int64_t n_steps, const double* tem
             return rc;
         }
     }
-    MHIP(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     int status = 0;
-    MHIP(h, hipMemcpyAsync(&status, h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    MHIP(h, hipMemcpyAsync(z_out, h->d_z, (size_t)(G * N) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    MHIP(h, hipStreamSynchronize(h->stream));
-    MHIP(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
-    if (status) return mfail(h, SBE_ERR_DATA, "an EM step produced a non-finite z (an object whose available groups all have "
+    HIPCHK(h, hipMemcpyAsync(&status, h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(z_out, h->d_z, (size_t)(G * N) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    if (status) return fail(h, SBE_ERR_DATA, "an EM step produced a non-finite z (an object whose available groups all have "
                              "likelihood 0, or a non-finite geo prior)");
     return SBE_OK;
 }
 
-int sbe_em_last_kernel_ms(const sbe_em* h, float* ms_out) {
-    if (!h) return mfail(nullptr, SBE_ERR_ARG, "null EM handle");
-    if (!ms_out) return mfail(const_cast<sbe_em*>(h), SBE_ERR_ARG, "null pointer argument: ms_out");
-    *ms_out = h->last_kernel_ms;
-    return SBE_OK;
-}
+int sbe_em_last_kernel_ms(const sbe_em* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 // layer.  One engine = one process' view of one GPU.  The one-hot feature block and every
 // slot's state stay resident in HBM; only small tables / id vectors cross PCIe per call.
 #include "sbe_kernels.hip.h"
+#include "sbe_unit.hip.h"      // HIPCHK and div_up, shared with the side units
 #include "../../include/sbe_engine.h"
 #include "../../include/sbe_engine_steps.h"
 #include "../../include/sbe_engine_diag.h"
@@ -243,14 +244,6 @@ int fail(sbe_engine* e, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIPCHK(e, call)                                                                        \
-    do {                                                                                       \
-        hipError_t _err = (call);                                                              \
-        if (_err != hipSuccess)                                                                \
-            return fail(e, SBE_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_err), \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
-
 #define CHECK_ENGINE(e) \
     if (!(e)) return fail(nullptr, SBE_ERR_ARG, "null engine handle")
 #define CHECK_SLOT(e, s) \
@@ -260,7 +253,6 @@ int fail(sbe_engine* e, int code, const char* fmt, ...) {
 #define CHECK_PTR(e, p) \
     if (!(p)) return fail(e, SBE_ERR_ARG, "null pointer argument: %s", #p)
 
-inline int div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 template <class T>

@@ -21,14 +21,12 @@ pickled, forgotten (not destroyed) in a fork()ed child, where every further call
 from __future__ import annotations
 
 import ctypes as ct
-import os
 from dataclasses import dataclass
 from pathlib import Path
 
 import numpy as np
 
-from . import _fast, _lib, _proc
-from .engine import EngineError
+from . import _fast, _handle
 
 ABI_VERSION = 1                          # SBE_ELPD_ABI_VERSION of include/sbe_elpd.h
 MAX_SAMPLES = 1 << 20                    # SBE_ELPD_MAX_SAMPLES
@@ -52,23 +50,13 @@ PROTOTYPES = {
     "sbe_elpd_compute": (ct.c_int, [c_store_p, ct.c_int64, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                     ct.c_void_p, ct.POINTER(ct.c_int64)]),
 }
-_BOUND = [None]
 
 _ptr = _fast.addr                        # buffer address as a plain int (engine.py: every array argument is c_void_p)
 
 
 def load():
     """The engine library with the prototypes of include/sbe_elpd.h attached."""
-    lib = _lib.load()
-    if _BOUND[0] is not lib:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(lib, name)       # AttributeError if the library lacks a declared symbol
-            fn.restype = restype
-            fn.argtypes = argtypes
-        if lib.sbe_elpd_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"sbayes_amd.elpd: ABI version mismatch ({lib.sbe_elpd_abi_version()} != {ABI_VERSION})")
-        _BOUND[0] = lib
-    return lib
+    return _handle.bind("sbe_elpd", PROTOTYPES, ABI_VERSION)
 
 
 def lds_max_samples() -> int:
@@ -106,28 +94,14 @@ class WaicResult:
     scale: str = "log"
 
 
-class _Store:
-    """Owner of one sbe_elpd_store: float32 likelihood rows on one device."""
+class _Store(_handle.UnitHandle):
+    """Owner of one sbe_elpd_store: float32 likelihood rows on one device.  last_kernel_ms(): the column kernel of the last
+    compute call."""
+    _prefix, _noun = "sbe_elpd", "an ELPD likelihood store"
 
     def __init__(self, device, n_columns, capacity):
-        _proc.check_usable()
-        self._lib = load()
-        self._h = ct.c_void_p()
-        self._pid = None
         self.device, self.n_columns, self.capacity = int(device), int(n_columns), int(capacity)
-        _proc.mark_hip_touched()
-        rc = self._lib.sbe_elpd_create(ct.byref(self._h), self.device, self.n_columns, self.capacity)
-        if rc != 0:
-            msg = self._lib.sbe_elpd_last_error(None)
-            self._h = ct.c_void_p()
-            raise EngineError(rc, msg.decode() if msg else "sbe_elpd_create failed")
-        self._pid = os.getpid()
-        _proc.register_engine(self)
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.sbe_elpd_last_error(self._h)
-            raise EngineError(rc, msg.decode() if msg else "?")
+        self._create(load, self.device, self.n_columns, self.capacity)
 
     @property
     def n_rows(self) -> int:
@@ -151,12 +125,6 @@ class _Store:
     def reset(self):
         self._check(self._lib.sbe_elpd_reset(self._h))
 
-    def last_kernel_ms(self) -> float:
-        """Device time of the column kernel of the last compute call (HIP events)."""
-        ms = ct.c_float(0)
-        self._check(self._lib.sbe_elpd_last_kernel_ms(self._h, ct.byref(ms)))
-        return float(ms.value)
-
     def compute(self, burn_rows, na_values, isclose_na):
         """(loo_i, k_i, lppd_i, v_i) over the kept columns; na_values: bool [n_columns] or None (validated by the caller)."""
         m = self.n_columns
@@ -168,26 +136,6 @@ class _Store:
                                                _ptr(k_i), _ptr(lppd_i), _ptr(v_i), ct.byref(n_kept)))
         k = n_kept.value
         return loo_i[:k].copy(), k_i[:k].copy(), lppd_i[:k].copy(), v_i[:k].copy()
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            if self._pid == os.getpid():
-                self._lib.sbe_elpd_destroy(self._h)
-            self._h = ct.c_void_p()
-
-    def _forget(self, lib_face):
-        """After fork(), in the child: drop the inherited handle without destroying it (_proc._after_fork_in_child)."""
-        self._h = ct.c_void_p()
-        self._lib = lib_face
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        raise TypeError("an ELPD likelihood store holds device memory and is not picklable; re-create it in the new process")
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------

@@ -19,13 +19,11 @@ The handle of an initializer's data is cached per data object: a chain initializ
 from __future__ import annotations
 
 import ctypes as ct
-import os
 import weakref
 
 import numpy as np
 
-from . import _fast, _lib, _proc
-from .engine import EngineError
+from . import _fast, _handle, _proc
 
 ABI_VERSION = 1                          # SBE_EM_ABI_VERSION of include/sbe_em.h
 MAX_STATES = 254                         # SBE_EM_MAX_STATES
@@ -48,23 +46,13 @@ PROTOTYPES = {
     "sbe_em_run": (ct.c_int, [c_em_p, ct.c_void_p, ct.c_int64, ct.c_void_p, ct.c_void_p]),
     "sbe_em_last_kernel_ms": (ct.c_int, [c_em_p, ct.POINTER(ct.c_float)]),
 }
-_BOUND = [None]
 
 _ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 
 def load():
     """The engine library with the prototypes of include/sbe_em.h attached."""
-    lib = _lib.load()
-    if _BOUND[0] is not lib:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(lib, name)       # AttributeError if the library lacks a declared symbol
-            fn.restype = restype
-            fn.argtypes = argtypes
-        if lib.sbe_em_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"sbayes_amd.em: ABI version mismatch ({lib.sbe_em_abi_version()} != {ABI_VERSION})")
-        _BOUND[0] = lib
-    return lib
+    return _handle.bind("sbe_em", PROTOTYPES, ABI_VERSION)
 
 
 def temperatures(n_em_steps: int) -> np.ndarray:
@@ -89,15 +77,12 @@ def state_index(features, na_values=None) -> np.ndarray:
     return x
 
 
-class EmHandle:
-    """Owner of one sbe_em: the data of one initializer resident on one device."""
+class EmHandle(_handle.UnitHandle):
+    """Owner of one sbe_em: the data of one initializer resident on one device.  last_kernel_ms(): the steps of the last run."""
+    _prefix, _noun = "sbe_em", "an EM handle"
 
     def __init__(self, x, applicable, groups_available, n_clusters, device=None):
         x, applicable, groups_available = _check_data(x, applicable, groups_available, n_clusters)
-        _proc.check_usable()
-        self._lib = load()
-        self._h = ct.c_void_p()
-        self._pid = None
         if device is None:
             from .registry import default_device
             device = default_device()
@@ -107,20 +92,8 @@ class EmHandle:
         self.n_groups, self.n_clusters = groups_available.shape[0], int(n_clusters)
         self.geo_key = None
         xa, aa, ga = x, applicable.view(np.uint8), groups_available.view(np.uint8)
-        _proc.mark_hip_touched()
-        rc = self._lib.sbe_em_create(ct.byref(self._h), self.device, self.n_objects, self.n_features, self.n_states, _ptr(xa),
-                                     _ptr(aa), self.n_groups, self.n_clusters, _ptr(ga))
-        if rc != 0:
-            msg = self._lib.sbe_em_last_error(None)
-            self._h = ct.c_void_p()
-            raise EngineError(rc, msg.decode() if msg else "sbe_em_create failed")
-        self._pid = os.getpid()
-        _proc.register_engine(self)
-
-    def _check(self, rc):
-        if rc != 0:
-            msg = self._lib.sbe_em_last_error(self._h)
-            raise EngineError(rc, msg.decode() if msg else "?")
+        self._create(load, self.device, self.n_objects, self.n_features, self.n_states, _ptr(xa), _ptr(aa), self.n_groups,
+                     self.n_clusters, _ptr(ga))
 
     def set_geo_cost(self, cost, scale, key=None):
         """Cost-based geo prior on (cost float64 [N, N]) or off (cost None).  `key`: an identity under which the upload
@@ -146,32 +119,6 @@ class EmHandle:
         out = np.empty_like(z_in)
         self._check(self._lib.sbe_em_run(self._h, _ptr(z_in), t.size, _ptr(t), _ptr(out)))
         return out
-
-    def last_kernel_ms(self) -> float:
-        """Device time of the steps of the last run (HIP events)."""
-        ms = ct.c_float(0)
-        self._check(self._lib.sbe_em_last_kernel_ms(self._h, ct.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            if self._pid == os.getpid():
-                self._lib.sbe_em_destroy(self._h)
-            self._h = ct.c_void_p()
-
-    def _forget(self, lib_face):
-        """After fork(), in the child: drop the inherited handle without destroying it (_proc._after_fork_in_child)."""
-        self._h = ct.c_void_p()
-        self._lib = lib_face
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __getstate__(self):
-        raise TypeError("an EM handle holds device memory and is not picklable; re-create it in the new process")
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------

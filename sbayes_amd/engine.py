@@ -8,11 +8,11 @@ Device handles are created lazily per process and are never pickled (MC3 workers
 from __future__ import annotations
 
 import ctypes as ct
-import os
 
 import numpy as np
 
 from . import _fast, _lib, _proc
+from ._handle import DeviceHandle, EngineError
 
 MIXTURE_PACKED, MIXTURE_ONEHOT, MIXTURE_PACKED_GENERAL, MIXTURE_PACKED_TUPLE, MIXTURE_ONEHOT_GENERAL = 0, 1, 2, 3, 4
 MIXTURE_PACKED_TUPLE_LDS = 5
@@ -20,12 +20,6 @@ MIXTURE_PACKED_V2 = 6
 MIXTURE_PACKED_TUPLE_MFMA = 7
 LOG_PER_OBS, LOG_PRODUCT = 0, 1
 _OPT_KERNEL, _OPT_LOG, _OPT_DEFERRED = 1, 2, 3
-
-
-class EngineError(RuntimeError):
-    def __init__(self, code, message):
-        super().__init__(f"sbe error {code}: {message}")
-        self.code = code
 
 
 class GroupOverlapError(EngineError):
@@ -69,14 +63,12 @@ def device_count() -> int:
     return n.value
 
 
-class Engine:
+class Engine(DeviceHandle):
     """One resident one-hot feature block + `n_slots` sample states on one GPU."""
+    _prefix, _noun = "sbe", "Engine"
 
     def __init__(self, features, n_groups, n_slots=2, device=0):
-        _proc.check_usable()             # ForkedWithHipError in a fork()ed child of a HIP-initialised parent
-        self._lib = _lib.load()
-        self._h = ct.c_void_p()
-        self._pid = None                 # pid of the process the handle lives in (set once sbe_create succeeded)
+        _proc.check_usable()             # (before the shape checks: a fork()ed child of a HIP-initialised parent hears that first)
         self.h2d_bytes = self.d2h_bytes = self.n_calls = 0
         features = np.asarray(features)
         if features.ndim != 3:
@@ -90,19 +82,8 @@ class Engine:
         self.device = int(device)
         feats = _c(features, np.uint8)
         ng = np.asarray(self.n_groups, dtype=np.int32)
-        # marked on the ATTEMPT, not on success: a create that fails after the runtime came up (out of memory,
-        # a bad shape behind hipSetDevice) has initialised HIP all the same, and a child forked afterwards must not be
-        # taken for a fresh process
-        _proc.mark_hip_touched()
-        rc = self._lib.sbe_create(ct.byref(self._h), self.device, self.n_objects, self.n_features,
-                                  self.n_states, self.n_components,
-                                  ng.ctypes.data_as(ct.POINTER(ct.c_int32)), self.n_slots, self._i(feats))
-        if rc != 0:
-            msg = self._lib.sbe_last_error(None)
-            self._h = ct.c_void_p()
-            raise EngineError(rc, msg.decode() if msg else "sbe_create failed")
-        self._pid = os.getpid()
-        _proc.register_engine(self)
+        self._create(_lib.load, self.device, self.n_objects, self.n_features, self.n_states, self.n_components,
+                     ng.ctypes.data_as(ct.POINTER(ct.c_int32)), self.n_slots, self._i(feats))
         self.group_offsets = np.concatenate([[0], np.cumsum(self.n_groups)]).astype(int)
         self.n_groups_total = int(self.group_offsets[-1])
         self._deferred = False
@@ -138,42 +119,24 @@ class Engine:
     def _check(self, rc):
         self.n_calls += 1
         if rc != 0:
-            msg = self._lib.sbe_last_error(self._h)
-            msg = msg.decode() if msg else "?"
+            msg = self._last_error()
             if rc == 4 and " is in groups " in msg:
                 raise GroupOverlapError(rc, msg)
             raise EngineError(rc, msg)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            if self._pid == os.getpid():         # (a handle that reached another process by any road is never destroyed there)
-                self._lib.sbe_destroy(self._h)
-            self._h = ct.c_void_p()
-
     def _forget(self, lib_face):
-        """After fork(), in the child (_proc._after_fork_in_child): drop the inherited handle WITHOUT sbe_destroy -- its
-        device memory, pinned arenas and stream belong to the parent -- and make every later call on this object raise."""
-        self._h = ct.c_void_p()
-        self._lib = lib_face
+        """After fork(), in the child: the base's, and the bind caches (they describe the parent's device state)."""
+        super()._forget(lib_face)
         self._bound = {}
         self._bound_conc = {}
         self._bound_unif = None
         self._mirror = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
         self.close()
-
-    def __getstate__(self):
-        raise TypeError("Engine holds device memory and is not picklable; re-create it in the new process")
 
     def info(self):
         inf = _lib.SbeInfo()
