@@ -83,6 +83,9 @@ MIRRORED_SOURCES = {
     "GroupedParameters.resolve_sharing": "e26fbdc96e79af850e2840a33297ddb0d997d967",
     # install(em_init=True): the EM cluster initializer (sbayes_amd/em.py)
     "SbayesInitializer.generate_clusters_em": "6e88242a00990dd9469737a9f513f30502fc5316",
+    # install(geo_prior=True): the cost-based geo prior (sbayes_amd/geo.py)
+    "GeoPrior.__call__": "6f3aca457d938e4acac29e5b79a272e2bc03a0fd",
+    "GeoPrior.get_costs_per_object": "5c4ef85dc56ecfe73608c3e74229f91267bb6527",
 }
 
 
@@ -91,7 +94,7 @@ def source_digest(obj) -> str:
     return hashlib.sha1(" ".join(inspect.getsource(obj).split()).encode()).hexdigest()
 
 
-def _check_mirrored(owner, name):
+def _check_mirrored(owner, name, where="sbayes_amd/operators.py"):
     key = f"{getattr(owner, '__name__', owner)}.{name}"
     want = MIRRORED_SOURCES.get(key)
     try:
@@ -100,12 +103,12 @@ def _check_mirrored(owner, name):
         return
     if want is not None and got != want:
         warnings.warn(f"sbayes_amd.patch: the installed sBayes' {key} differs from the revision its device form mirrors; "
-                      f"the device form replaces it anyway -- re-check sbayes_amd/operators.py against it", RuntimeWarning)
+                      f"the device form replaces it anyway -- re-check {where} against it", RuntimeWarning)
 
 
 def installed():
-    """{"operators": bool, "gibbs_source": bool} (plus "em_init": True when that hook is on) if install() ran in this
-    process (and uninstall() has not), else None."""
+    """{"operators": bool, "gibbs_source": bool} (plus "em_init": True / "geo_prior": True when those hooks are on) if
+    install() ran in this process (and uninstall() has not), else None."""
     return dict(_INSTALLED) if _INSTALLED is not None else None
 
 
@@ -133,7 +136,7 @@ def set_mp_start_method(method):
     return method
 
 
-def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=False):
+def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=False, geo_prior=False):
     """operators=True: the device forms listed in the module docstring.  gibbs_source=True (implies operators): the two
     Gibbs source resamplings of the reference run on the device, with the uniforms np.random yields
     at the point where the reference's `sample_categorical` draws them (draw for draw: the same Markov chain) --
@@ -211,11 +214,48 @@ def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=F
     em_init = bool(em_init) and not (_INSTALLED and _INSTALLED.get("em_init"))
     if em_init:
         _install_em_init_form(swap)
+    geo_prior = bool(geo_prior) and not (_INSTALLED and _INSTALLED.get("geo_prior"))
+    if geo_prior:
+        _install_geo_prior_form(swap)
+    was_geo = bool(_INSTALLED and _INSTALLED.get("geo_prior"))
     was_em = bool(_INSTALLED and _INSTALLED.get("em_init"))
     _INSTALLED = {"operators": bool(operators) or bool(_INSTALLED and _INSTALLED["operators"]),
                   "gibbs_source": bool(gibbs_source) or bool(_INSTALLED and _INSTALLED.get("gibbs_source"))}
     if em_init or was_em:
         _INSTALLED["em_init"] = True
+    if geo_prior or was_geo:
+        _INSTALLED["geo_prior"] = True
+
+
+def _install_geo_prior_form(swap):
+    """GeoPrior.__call__ and GeoPrior.get_costs_per_object -> sbayes_amd.geo (the MST skeleton on the device).  A prior the
+    device form does not cover (geo.covered: simulated, the skeletons delaunay and diameter), and a cluster with fewer than
+    geo.HOST_BELOW_MEMBERS members, run the reference's own body."""
+    import numpy as np
+
+    ref_prior = importlib.import_module("sbayes.model.prior")
+    from . import geo as my_geo
+    _check_mirrored(ref_prior.GeoPrior, "__call__", where="sbayes_amd/geo.py")
+    _check_mirrored(ref_prior.GeoPrior, "get_costs_per_object", where="sbayes_amd/geo.py")
+    reference_call = ref_prior.GeoPrior.__dict__["__call__"]
+    reference_costs = ref_prior.GeoPrior.__dict__["get_costs_per_object"]
+
+    def small(sample, clusters):
+        floor = my_geo.HOST_BELOW_MEMBERS
+        return floor > 0 and int(np.count_nonzero(np.asarray(sample.clusters.value)[clusters], axis=-1).max(initial=0)) < floor
+
+    def geo_prior_call(self, sample, caching=True):
+        if not my_geo.covered(self, for_call=True) or small(sample, slice(None)):
+            return reference_call(self, sample, caching=caching)
+        return my_geo.geo_prior_call(self, sample, caching=caching)
+
+    def get_costs_per_object(self, sample, i_cluster):
+        if not my_geo.covered(self, for_call=False) or small(sample, i_cluster):
+            return reference_costs(self, sample, i_cluster)
+        return my_geo.get_costs_per_object(self, sample, i_cluster)
+
+    swap(ref_prior.GeoPrior, "__call__", geo_prior_call)
+    swap(ref_prior.GeoPrior, "get_costs_per_object", get_costs_per_object)
 
 
 def _install_em_init_form(swap):
