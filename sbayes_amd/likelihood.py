@@ -149,9 +149,10 @@ class Likelihood:
             from . import patch
             cur = patch.installed()
             if (cur is None or (how["operators"] and not cur["operators"]) or (how.get("gibbs_source") and not cur.get("gibbs_source"))
-                    or (how.get("em_init") and not cur.get("em_init")) or (how.get("geo_prior") and not cur.get("geo_prior"))):
+                    or (how.get("em_init") and not cur.get("em_init")) or (how.get("geo_prior") and not cur.get("geo_prior"))
+                    or (how.get("gibbs_weights") and not cur.get("gibbs_weights"))):
                 patch.install(operators=how["operators"], gibbs_source=bool(how.get("gibbs_source")), em_init=bool(how.get("em_init")),
-                              geo_prior=bool(how.get("geo_prior")))
+                              geo_prior=bool(how.get("geo_prior")), gibbs_weights=bool(how.get("gibbs_weights")))
         registry.note_features(self.features, self.n_groups)
 
     @property

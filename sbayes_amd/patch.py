@@ -26,6 +26,11 @@ has to cross PCIe for them:
         evaluates that sample's resident state on the device -- the two [N, F, C] arrays per call are never built)
 Proposal logic, RNG use and everything else of the operators stay the reference's.
 
+install(gibbs_weights=True) (implies operators) replaces GibbsSampleWeights._propose itself (operators.py:597-676): the
+three random draws stay on the host, in the reference's order and amounts, and everything else of the step -- the source
+counts, the proposed weights, the Metropolis ratio per feature, the decision -- is two engine calls on the sample's
+resident state (sbayes_amd/wgibbs.py, include/sbe_wgibbs.h).
+
 Process model (sbayes_amd/_proc.py, INTEGRATION.md "Processes").  The reference starts MC3 workers and run pools with
 `multiprocessing`'s default start method -- fork on Linux (mcmc_setup.py:271-282, cli.py:104-109) -- and a HIP context does
 not survive fork().  install(mp_start_method="forkserver" | "spawn") fixes the start method before the first worker exists;
@@ -86,6 +91,8 @@ MIRRORED_SOURCES = {
     # install(geo_prior=True): the cost-based geo prior (sbayes_amd/geo.py)
     "GeoPrior.__call__": "6f3aca457d938e4acac29e5b79a272e2bc03a0fd",
     "GeoPrior.get_costs_per_object": "5c4ef85dc56ecfe73608c3e74229f91267bb6527",
+    # install(gibbs_weights=True): the Gibbs weights operator (sbayes_amd/wgibbs.py; GibbsSampleWeights._propose is above)
+    "GibbsSampleWeights.resample_weight_for_two_components": "bf0c0f43a0f1f824a322bdc61623519f56a6a700",
 }
 
 
@@ -107,8 +114,8 @@ def _check_mirrored(owner, name, where="sbayes_amd/operators.py"):
 
 
 def installed():
-    """{"operators": bool, "gibbs_source": bool} (plus "em_init": True / "geo_prior": True when those hooks are on) if
-    install() ran in this process (and uninstall() has not), else None."""
+    """{"operators": bool, "gibbs_source": bool} (plus "em_init": True / "geo_prior": True / "gibbs_weights": True when
+    those hooks are on) if install() ran in this process (and uninstall() has not), else None."""
     return dict(_INSTALLED) if _INSTALLED is not None else None
 
 
@@ -136,7 +143,7 @@ def set_mp_start_method(method):
     return method
 
 
-def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=False, geo_prior=False):
+def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=False, geo_prior=False, gibbs_weights=False):
     """operators=True: the device forms listed in the module docstring.  gibbs_source=True (implies operators): the two
     Gibbs source resamplings of the reference run on the device, with the uniforms np.random yields
     at the point where the reference's `sample_categorical` draws them (draw for draw: the same Markov chain) --
@@ -150,9 +157,13 @@ def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=F
     At the headline shape these two bodies are the largest items of the reference's per-step Python.
     em_init=True: SbayesInitializer.generate_clusters_em (initializers.py:93-169) runs its EM steps on the device
     (sbayes_amd/em.py); its draws are the reference's, but z is carried in fp64, so the initial clusters can differ from an
-    unpatched run's on objects near a tie.  Off by default."""
+    unpatched run's on objects near a tie.  Off by default.
+    gibbs_weights=True (implies operators): GibbsSampleWeights._propose (operators.py:597-676) draws i1, i2, a2 and u on the
+    host as the reference does and runs the rest of the step in two engine calls (sbayes_amd/wgibbs.py); a weights prior
+    the device form does not cover, fewer than two components and a sample no live engine holds run the reference's own
+    body.  Off by default."""
     global _INSTALLED
-    operators = bool(operators) or bool(gibbs_source)
+    operators = bool(operators) or bool(gibbs_source) or bool(gibbs_weights)
     if mp_start_method is not None:
         set_mp_start_method(mp_start_method)
     from . import conditionals as my_cond
@@ -217,6 +228,10 @@ def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=F
     geo_prior = bool(geo_prior) and not (_INSTALLED and _INSTALLED.get("geo_prior"))
     if geo_prior:
         _install_geo_prior_form(swap)
+    gibbs_weights = bool(gibbs_weights) and not (_INSTALLED and _INSTALLED.get("gibbs_weights"))
+    if gibbs_weights:
+        _install_gibbs_weights_form(swap)
+    was_wgibbs = bool(_INSTALLED and _INSTALLED.get("gibbs_weights"))
     was_geo = bool(_INSTALLED and _INSTALLED.get("geo_prior"))
     was_em = bool(_INSTALLED and _INSTALLED.get("em_init"))
     _INSTALLED = {"operators": bool(operators) or bool(_INSTALLED and _INSTALLED["operators"]),
@@ -225,6 +240,28 @@ def install(operators=False, mp_start_method=None, gibbs_source=False, em_init=F
         _INSTALLED["em_init"] = True
     if geo_prior or was_geo:
         _INSTALLED["geo_prior"] = True
+    if gibbs_weights or was_wgibbs:
+        _INSTALLED["gibbs_weights"] = True
+
+
+def _install_gibbs_weights_form(swap):
+    """GibbsSampleWeights._propose -> sbayes_amd.wgibbs.gibbs_sample_weights (the step after the draws on the device).  The
+    reference's own body runs for a weights prior the device form does not cover, for fewer than two components, and
+    when the engine lookup declines (the conditions of source_lh_by_feature below: a sample object of another form, an
+    NA mask no live engine holds).  An error of the bind or of an engine call is a real error and propagates."""
+    from . import wgibbs as my_wgibbs
+    ref_ops = importlib.import_module("sbayes.sampling.operators")
+    _check_mirrored(ref_ops.GibbsSampleWeights, "_propose", where="sbayes_amd/wgibbs.py")
+    _check_mirrored(ref_ops.GibbsSampleWeights, "resample_weight_for_two_components", where="sbayes_amd/wgibbs.py")
+    reference_propose = ref_ops.GibbsSampleWeights.__dict__["_propose"]
+
+    def _propose(self, sample, **kwargs):
+        eng = my_wgibbs.engine_for(self, sample) if my_wgibbs.covered(self, sample) else None
+        if eng is None:
+            return reference_propose(self, sample, **kwargs)
+        return my_wgibbs.gibbs_sample_weights(self, sample, eng)
+
+    swap(ref_ops.GibbsSampleWeights, "_propose", _propose)
 
 
 def _install_geo_prior_form(swap):
