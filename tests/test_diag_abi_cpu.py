@@ -1,0 +1,166 @@
+"""CPU checks of the diagnostics boundary (include/sbe_diag.h, sbayes_amd/diag.py): the symbols are exported and bound by
+the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
+import ast
+import ctypes as ct
+import inspect
+import pickle
+import re
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from sbayes_amd import _lib, diag
+
+REPO = Path(__file__).resolve().parent.parent
+HEADER = (REPO / "include" / "sbe_diag.h").read_text()
+
+
+def _declared():
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_every_symbol_of_the_header_is_exported_and_bound():
+    lib = diag.load()
+    names = _declared()
+    assert len(names) == 12
+    for name in names:
+        assert hasattr(lib, name), f"{name} declared in include/sbe_diag.h but not exported"
+    assert sorted(diag.PROTOTYPES) == names
+    assert lib.sbe_diag_abi_version() == diag.ABI_VERSION
+    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+
+
+def test_limits_and_codes_agree_with_the_header():
+    def macro(name):
+        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
+    assert macro("SBE_DIAG_MAX_CHAINS") == str(diag.MAX_CHAINS) == "64"
+    assert macro("SBE_DIAG_MIN_DRAWS") == str(diag.MIN_DRAWS) == "4"
+    assert macro("SBE_DIAG_MAX_DRAWS") == "(1 << 20)" and diag.MAX_DRAWS == 1 << 20
+    assert diag.MAX_COLUMNS == 2 ** 31 - 1
+    assert (macro("SBE_DIAG_FLAG_CONSTANT"), macro("SBE_DIAG_FLAG_NONFINITE"), macro("SBE_DIAG_FLAG_TRUNCATED")) == \
+        (str(diag.FLAG_CONSTANT), str(diag.FLAG_NONFINITE), str(diag.FLAG_TRUNCATED))
+    assert {int(macro("SBE_DIAG_PATH_LDS")): "lds", int(macro("SBE_DIAG_PATH_GLOBAL")): "global"} == diag.PATHS
+    # the staged column, the rho_t entries kept in LDS and the kernel's static LDS fit the 160 KiB of a CU
+    limit = diag.lds_max_draws()
+    assert 8192 <= limit and (limit + 2048) * 8 + 4096 <= 160 * 1024 < (limit + 1 + 2048) * 8 + 4096
+
+
+def test_every_array_handed_to_the_library_is_bound_to_a_name():
+    """diag.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
+    tree = ast.parse(inspect.getsource(diag))
+    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
+           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
+           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
+    assert not bad, bad
+
+
+@pytest.fixture
+def no_device(monkeypatch):
+    """Any attempt to create a handle fails the test."""
+    def refuse(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(diag.DiagHandle, "__init__", refuse)
+
+
+class _Flat:
+    """Passes for an array of a given shape without holding its memory."""
+    def __init__(self, shape):
+        self.shape = shape
+
+    def __array__(self, dtype=None, copy=None):
+        return np.broadcast_to(np.zeros((), dtype=dtype or np.float64), self.shape)
+
+
+@pytest.mark.parametrize("chains,kw,err,match", [
+    ([], {}, ValueError, r"0 chains; the diagnostics take 1 \.\. 64"),
+    ([np.zeros((10, 2))] * 65, {}, ValueError, r"65 chains; the diagnostics take 1 \.\. 64"),
+    (np.zeros((65, 10, 2)), {}, ValueError, "65 chains"),
+    (np.zeros((10, 2)), {}, ValueError, r"\[M, S, P\]"),
+    ([np.zeros((7, 2))], dict(burnin=0.0), ValueError, "3 draws per chain after burn-in and split; at least 4"),
+    ([np.zeros((3, 2))], dict(burnin=0.0, split=False), ValueError, "3 draws per chain after burn-in; at least 4"),
+    ([np.zeros((20, 2)), np.zeros((8, 2))], dict(burnin=0.2), ValueError, "3 draws per chain"),
+    ([np.broadcast_to(np.zeros((1, 1)), ((1 << 19) + 2, 1))] * 2, dict(burnin=0.0), ValueError, r"exceed 1048576 \(2\^20\)"),
+    ([np.zeros((10, 2)), np.zeros((10, 3))], {}, ValueError, "unequal column counts"),
+    ([np.zeros((10, 2))], dict(burnin=1.0), ValueError, r"must lie in \[0, 1\)"),
+    ([np.zeros((10, 2))], dict(burnin=-0.1), ValueError, r"must lie in \[0, 1\)"),
+    ([np.zeros((10, 2))], dict(max_lag=-1), ValueError, "max_lag"),
+    ([np.zeros((10, 2))], dict(names=["a"]), ValueError, "1 names for 2 columns"),
+    ([np.zeros((10, 0))], {}, ValueError, "0 columns"),
+    ([np.zeros((10, 2), dtype="U1")], dict(burnin=0.0), TypeError, "numeric"),
+])
+def test_bad_input_is_refused_before_the_device(no_device, chains, kw, err, match):
+    with pytest.raises(err, match=match):
+        diag.convergence(chains, **kw)
+
+
+def test_plan_follows_drop_burnin_cut_and_split():
+    assert diag._plan([100], 0.1, True) == ([10], (0,), 2, 45)
+    assert diag._plan([101, 90], 0.1, True) == ([10, 9], (10, 0), 4, 40)
+    assert diag._plan([101, 90], 0.1, False) == ([10, 9], (10, 0), 2, 81)
+    assert diag._plan([9], 0.0, True) == ([0], (0,), 2, 4)                 # the middle draw of an odd length is dropped
+    assert diag._plan([1 << 20], 0.0, True)[2:] == (2, 1 << 19)
+
+
+def test_c_abi_validates_before_the_device():
+    lib = diag.load()
+    h = ct.c_void_p()
+    assert lib.sbe_diag_create(None, 0) == 1
+    assert b"null pointer argument: out" in lib.sbe_diag_last_error(None)
+    assert lib.sbe_diag_create(ct.byref(h), -1) == 1 and not h
+    assert b"device -1 out of range" in lib.sbe_diag_last_error(None)
+    assert lib.sbe_diag_reset(None, 1, 1, 1) == 1
+    assert b"null handle" in lib.sbe_diag_last_error(None)
+    assert lib.sbe_diag_append_rows(None, 0, None, 0) == 1
+    n = ct.c_int64()
+    assert lib.sbe_diag_rows(None, 0, ct.byref(n)) == 1
+    assert lib.sbe_diag_set_launch_columns(None, 4) == 1
+    assert lib.sbe_diag_compute(None, None, 1, 0, None, None, None, None, None, None, None) == 1
+    m, path = ct.c_int(), ct.c_int()
+    assert lib.sbe_diag_last_shape(None, ct.byref(m), ct.byref(n), ct.byref(path), ct.byref(n)) == 1
+    assert lib.sbe_diag_destroy(None) == 1
+    ms = ct.c_float()
+    assert lib.sbe_diag_last_kernel_ms(None, ct.byref(ms)) == 1
+    assert lib.sbe_diag_lds_max_draws() == diag.lds_max_draws()
+
+
+def test_handles_are_not_picklable():
+    h = object.__new__(diag.DiagHandle)
+    h._h = ct.c_void_p()
+    with pytest.raises(TypeError, match="not picklable"):
+        pickle.dumps(h)
+
+
+def test_a_handle_checks_its_own_arguments_before_the_library():
+    h = object.__new__(diag.DiagHandle)
+    h._h = ct.c_void_p()
+    h.n_chains, h.n_columns, h.capacity = 2, 3, 10
+
+    def refuse(*a, **k):
+        raise AssertionError("the device was touched")
+    h._lib = SimpleNamespace(**{name: refuse for name in diag.PROTOTYPES})
+    with pytest.raises(ValueError, match=r"65 chains"):
+        h.reset(65, 3, 10)
+    h.n_chains, h.n_columns = 2, 3
+    with pytest.raises(ValueError, match="chain 2 out of range"):
+        h.append(2, np.zeros((1, 3)))
+    with pytest.raises(ValueError, match="rows have 4 columns, the store has 3"):
+        h.append(0, np.zeros((1, 4)))
+    with pytest.raises(ValueError, match="max_lag"):
+        h.compute(max_lag=-3)
+
+
+def test_result_summary_and_worst():
+    res = diag.DiagResult(mean=np.zeros(5), sd=np.ones(5), ess=np.array([500.0, 20.0, np.nan, 150.0, 40.0]),
+                          rhat=np.array([1.0, 1.2, np.nan, 1.02, np.nan]), mcse_mean=np.zeros(5), n_lags=np.zeros(5, dtype=np.int32),
+                          flag=np.array([0, 0, 2, 4, 1], dtype=np.uint8), names=list("abcde"), n_chains=4, n_draws=10)
+    assert [w[0] for w in res.worst(3)] == ["b", "e", "d"]
+    assert [w[0] for w in res.worst(9)][-1] == "c"                          # the non-finite column comes last
+    s = res.summary()
+    assert (s["n_rhat_above"], s["n_ess_below"], s["n_constant"], s["n_nonfinite"], s["n_truncated"]) == (2, 2, 1, 1, 1)
+    assert (s["ess_min"], s["ess_median"], s["ess_max"]) == (20.0, 150.0, 500.0)
+    assert (s["rhat_threshold"], s["ess_threshold"]) == (1.01, 200.0)
+    s = res.summary(rhat_threshold=1.1, ess_threshold=100)
+    assert (s["n_rhat_above"], s["n_ess_below"]) == (1, 1)
