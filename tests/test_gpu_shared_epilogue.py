@@ -71,10 +71,12 @@ def run_cases():
     return out
 
 
-def _forced_old():
+def _forced_old(module_file=__file__):
+    """run_cases() of the test module `module_file` in a fresh child process with SBE_MFMA_SHARED=0 (also used by
+    tests/test_gpu_mixture_log_range.py)."""
     with tempfile.TemporaryDirectory() as d:
         code = ("import importlib.util, sys, numpy as np\n"
-                f"spec = importlib.util.spec_from_file_location('t', {str(Path(__file__))!r})\n"
+                f"spec = importlib.util.spec_from_file_location('t', {str(Path(module_file))!r})\n"
                 "m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)\n"
                 "out = m.run_cases()\n"
                 "np.savez(sys.argv[1], **{k + '__v': v[0] for k, v in out.items()}, **{k + '__n': np.array(v[1]) for k, v in out.items()})\n")
