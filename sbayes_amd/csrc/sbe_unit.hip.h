@@ -1,5 +1,5 @@
 #pragma once
-// sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip: each an opaque
+// sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip, sbe_align.hip: each an opaque
 // handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check, the
 // device part of create, destroy, and device buffers that only grow.  Host code only and nothing of the engine: a unit
 // that includes this header alone compiles no kernels but its own.  sbe_engine_internal.hip.h takes HIPCHK and div_up
