@@ -8,7 +8,10 @@ from __future__ import annotations
 import ctypes as ct
 import os
 
-from . import _lib, _proc
+from . import _fast, _lib, _proc
+
+c_handle_p = ct.c_void_p                 # every handle type of the C ABI is opaque
+_ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 
 class EngineError(RuntimeError):
@@ -34,6 +37,16 @@ def bind(prefix, prototypes, abi_version):
             raise RuntimeError(f"sbayes_amd.{prefix[4:]}: ABI version mismatch ({found} != {abi_version})")
         _BOUND[prefix] = lib
     return lib
+
+
+def unit_prototypes(prefix):
+    """The rows every side unit's prototype table has (name -> (restype, argtypes)); the unit adds <prefix>_create and its own."""
+    return {
+        f"{prefix}_abi_version": (ct.c_int, []),
+        f"{prefix}_last_error": (ct.c_char_p, [c_handle_p]),
+        f"{prefix}_destroy": (ct.c_int, [c_handle_p]),
+        f"{prefix}_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
+    }
 
 
 class DeviceHandle:
@@ -95,10 +108,39 @@ class DeviceHandle:
 
 
 class UnitHandle(DeviceHandle):
-    """Owner of a side unit's handle: those also have <prefix>_last_kernel_ms."""
+    """Owner of a side unit's handle: those live on one device (self.device) and also have <prefix>_last_kernel_ms."""
+
+    def _create_on(self, load, device, *args):
+        """<prefix>_create(&handle, device, *args); device None: the device of the process's engine (registry.default_device)."""
+        if device is None:
+            from .registry import default_device
+            device = default_device()
+        self.device = int(device)
+        self._create(load, self.device, *args)
 
     def last_kernel_ms(self) -> float:
         """Device time of the unit's kernels in the last compute call (HIP events)."""
         ms = ct.c_float(0)
         self._check(self._fn("last_kernel_ms")(self._h, ct.byref(ms)))
         return float(ms.value)
+
+
+# ---- one handle per device, created lazily (assoc.py, geo.py): device -> handle; per process, emptied in a fork()ed child --
+def device_cache():
+    cache = {}
+    _proc.on_fork_clear(cache.clear)
+    return cache
+
+
+def cached_handle(cache, make, device):
+    """The handle on `device` in `cache`, made by make(device) on first use (or after it was closed)."""
+    h = cache.get(int(device))
+    if h is None or not h._h:
+        h = cache[int(device)] = make(device)
+    return h
+
+
+def release_cached(cache):
+    for h in list(cache.values()):
+        h.close()
+    cache.clear()

@@ -33,7 +33,8 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _fast, _handle, diag
+from . import _handle, diag
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_ALIGN_ABI_VERSION of include/sbe_align.h
 MAX_CLUSTERS = 8                         # SBE_ALIGN_MAX_CLUSTERS
@@ -43,25 +44,18 @@ MAX_SEED_ROWS = 1024                     # SBE_ALIGN_MAX_SEED_ROWS
 LDS_BYTES = 160 * 1024                   # SBE_ALIGN_LDS_BYTES
 STATIC_LDS = 4096                        # SBE_ALIGN_STATIC_LDS
 
-c_handle_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_align.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    "sbe_align_abi_version": (ct.c_int, []),
-    "sbe_align_last_error": (ct.c_char_p, [c_handle_p]),
+    **_handle.unit_prototypes("sbe_align"),
     "sbe_align_max_objects": (ct.c_int64, [ct.c_int]),
     "sbe_align_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_align_destroy": (ct.c_int, [c_handle_p]),
     "sbe_align_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_int64, ct.c_int64]),
     "sbe_align_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
     "sbe_align_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
     "sbe_align_within": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p]),
     "sbe_align_counts": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_void_p]),
     "sbe_align_runs": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p]),
-    "sbe_align_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 
 def load():
@@ -138,13 +132,9 @@ class AlignHandle(_handle.UnitHandle):
     _prefix, _noun = "sbe_align", "an alignment handle"
 
     def __init__(self, device=None):
-        if device is None:
-            from .registry import default_device
-            device = default_device()
-        self.device = int(device)
         self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
         self._stored = []
-        self._create(load, self.device)
+        self._create_on(load, device)
 
     def reset(self, n_runs, n_clusters, n_objects, capacity):
         """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits."""

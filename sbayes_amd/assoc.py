@@ -28,7 +28,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _fast, _handle, _proc
+from . import _handle
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_ASSOC_ABI_VERSION of include/sbe_assoc.h
 NA = 255                                 # SBE_ASSOC_NA
@@ -38,24 +39,17 @@ MAX_FEATURES = 4096                      # SBE_ASSOC_MAX_FEATURES
 MAX_CODES = 1 << 31                      # SBE_ASSOC_MAX_CODES
 METADATA_COLUMNS = ("id", "name", "family", "x", "y")
 
-c_handle_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_assoc.h one to one (the engine's own table, _lib.PROTOTYPES, covers
 # the three engine headers and is not extended)
 PROTOTYPES = {
-    "sbe_assoc_abi_version": (ct.c_int, []),
-    "sbe_assoc_last_error": (ct.c_char_p, [c_handle_p]),
+    **_handle.unit_prototypes("sbe_assoc"),
     "sbe_assoc_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_assoc_destroy": (ct.c_int, [c_handle_p]),
     "sbe_assoc_set_launch_tiles": (ct.c_int, [c_handle_p, ct.c_int64]),
     "sbe_assoc_compute": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64, ct.c_int64, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                      ct.c_void_p, ct.c_void_p, ct.c_void_p]),
     "sbe_assoc_tables": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64, ct.c_void_p]),
     "sbe_assoc_last_shape": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]),
-    "sbe_assoc_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (engine.py: every array argument is c_void_p)
 
 
 def load():
@@ -69,9 +63,8 @@ class AssocHandle(_handle.UnitHandle):
     _prefix, _noun = "sbe_assoc", "an association handle"
 
     def __init__(self, device=0):
-        self.device = int(device)
         self._data = None                  # the codes the device holds (AssociationResult.tables)
-        self._create(load, self.device)
+        self._create_on(load, device)
 
     def set_launch_tiles(self, tile_pairs):
         """Tile pairs per launch of the pair kernel (0: the default).  Results do not depend on it."""
@@ -101,26 +94,16 @@ class AssocHandle(_handle.UnitHandle):
         return s_pad.value, tiles.value, launches.value
 
 
-_HANDLES: dict = {}          # device -> AssocHandle; per process, emptied in a fork()ed child
-
-
-@_proc.on_fork_clear
-def _forget_inherited():
-    _HANDLES.clear()
+_HANDLES = _handle.device_cache()          # device -> AssocHandle
 
 
 def release_all():
-    for h in list(_HANDLES.values()):
-        h.close()
-    _HANDLES.clear()
+    _handle.release_cached(_HANDLES)
 
 
 def handle_for(device=0) -> AssocHandle:
     """The process's handle on `device`, created on first use."""
-    h = _HANDLES.get(int(device))
-    if h is None or not h._h:
-        h = _HANDLES[int(device)] = AssocHandle(device)
-    return h
+    return _handle.cached_handle(_HANDLES, AssocHandle, device)
 
 
 # ---- validation and conversion (host side, before any library call) ------------------------------------------------

@@ -33,10 +33,6 @@ constexpr int kAlignBlock = 256;
 constexpr int kAlignWaves = kAlignBlock / 64;
 constexpr int kMaxK = SBE_ALIGN_MAX_CLUSTERS;
 constexpr uint64_t kIdentityPack = 0x0706050403020100ull;   // byte i holds i
-// workgroups per launch: an AQL dispatch holds its grid in work-items as a uint32 ("Column count")
-constexpr int64_t kMaxGridBlocks = ((int64_t)1 << 24) - 1;
-
-constexpr int pow2_at_least(int v) { return v <= 1 ? 1 : 2 * pow2_at_least((v + 1) / 2); }
 
 // ---- the K * K partial sums of a wave: lane l ends with the wave's total of entry l & (L - 1) -----------------------
 template <int L>
@@ -316,15 +312,15 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_pack(const uint8_t* rows,
 }  // namespace
 
 struct sbe_align : sbe_unit_handle {           // (sbe_unit.hip.h; ev: around the within-run kernel of the last sbe_align_within)
-    int runs = 0, K = 0;
-    int64_t N = 0, W = 0, cap = 0;
-    std::vector<int64_t> rows;          // [runs]
+    unit_lanes runs;                    // (empty: no shape yet)
+    int K = 0;
+    int64_t N = 0, W = 0;
     bool perm_valid = false;
     uint32_t* d_bits = nullptr;         // [runs][cap][K][W]
     size_t bits_bytes = 0;
     int8_t* d_perm = nullptr;           // [runs][cap][K]
     size_t perm_bytes = 0;
-    uint8_t* d_stage = nullptr;         // host rows in flight
+    void* d_stage = nullptr;            // host rows in flight
     size_t stage_bytes = 0;
     int32_t* d_cnt = nullptr;           // [runs][K][N]
     size_t cnt_bytes = 0;
@@ -337,9 +333,8 @@ struct sbe_align : sbe_unit_handle {           // (sbe_unit.hip.h; ev: around th
 
 namespace {
 
-constexpr sbe_align* kNone = nullptr;                 // (fail without a handle: the type names the unit)
 constexpr char kNullHandle[] = "null handle";
-constexpr int64_t kStageBytes = (int64_t)64 << 20;    // host rows are moved in pieces of at most 64 MiB
+constexpr char kLane[] = "run", kReset[] = "sbe_align_reset";
 
 int64_t max_objects(int K) {
     if (K < 1 || K > kMaxK) return 0;
@@ -348,8 +343,8 @@ int64_t max_objects(int K) {
 
 int upload_rows(sbe_align* h) {
     int32_t rows32[SBE_ALIGN_MAX_RUNS];
-    for (int r = 0; r < h->runs; ++r) rows32[r] = (int32_t)h->rows[(size_t)r];
-    HIPCHK(h, hipMemcpyAsync(h->d_rows, rows32, (size_t)h->runs * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    for (int r = 0; r < h->runs.count(); ++r) rows32[r] = (int32_t)h->runs.rows[(size_t)r];
+    HIPCHK(h, hipMemcpyAsync(h->d_rows, rows32, (size_t)h->runs.count() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));              // (rows32 lives on this frame)
     return SBE_OK;
 }
@@ -358,14 +353,14 @@ template <int K>
 int launch_within(sbe_align* h, const WithinArgs& args, size_t lds) {
     HIPCHK(h, hipFuncSetAttribute((const void*)k_align_within<K>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(SBE_ALIGN_LDS_BYTES - SBE_ALIGN_STATIC_LDS + 4 * 31 * kMaxK)));
-    k_align_within<K><<<(unsigned)h->runs, kAlignBlock, lds, h->stream>>>(args);
+    k_align_within<K><<<(unsigned)h->runs.count(), kAlignBlock, lds, h->stream>>>(args);
     HIPCHK(h, hipGetLastError());
     return SBE_OK;
 }
 
 template <int K>
 int launch_runs(sbe_align* h, int pivot) {
-    k_align_runs<K><<<(unsigned)h->runs, kAlignBlock, 0, h->stream>>>(h->d_cnt, pivot, (int)h->N, h->d_run_perm, h->d_agree);
+    k_align_runs<K><<<(unsigned)h->runs.count(), kAlignBlock, 0, h->stream>>>(h->d_cnt, pivot, (int)h->N, h->d_run_perm, h->d_agree);
     HIPCHK(h, hipGetLastError());
     return SBE_OK;
 }
@@ -375,22 +370,22 @@ int run_counts(sbe_align* h, int aligned, const int64_t* burn_rows) {
     HIPCHK(h, hipSetDevice(h->device));
     int rc = upload_rows(h);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_burn, burn_rows, (size_t)h->runs * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    const int64_t threads = (int64_t)h->runs * h->K * h->W;
+    HIPCHK(h, hipMemcpyAsync(h->d_burn, burn_rows, (size_t)h->runs.count() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    const int64_t threads = (int64_t)h->runs.count() * h->K * h->W;
     k_align_counts<<<(unsigned)div_up(threads, kAlignBlock), kAlignBlock, 0, h->stream>>>(h->d_bits, h->d_perm, h->d_rows, h->d_burn, aligned ? 1 : 0,
-                                                                                        h->runs, h->K, (int)h->N, (int)h->W, h->cap, h->d_cnt);
+                                                                                        h->runs.count(), h->K, (int)h->N, (int)h->W, h->runs.cap, h->d_cnt);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));              // (burn_rows is the caller's)
     return SBE_OK;
 }
 
 int check_counts_args(sbe_align* h, int aligned, const int64_t* burn_rows) {
-    if (h->runs == 0) return fail(h, SBE_ERR_STATE, "the store has no shape yet (sbe_align_reset)");
+    if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
     if (!burn_rows) return fail(h, SBE_ERR_ARG, "null pointer argument: burn_rows");
-    for (int r = 0; r < h->runs; ++r)
-        if (burn_rows[r] < 0 || burn_rows[r] > h->rows[(size_t)r])
+    for (int r = 0; r < h->runs.count(); ++r)
+        if (burn_rows[r] < 0 || burn_rows[r] > h->runs.rows[(size_t)r])
             return fail(h, SBE_ERR_ARG, "burn_rows[%d]=%lld out of range [0, %lld] (rows stored for the run)", r, (long long)burn_rows[r],
-                        (long long)h->rows[(size_t)r]);
+                        (long long)h->runs.rows[(size_t)r]);
     if (aligned && !h->perm_valid)
         return fail(h, SBE_ERR_STATE, "no permutations for the rows stored (sbe_align_within comes first, after the last append)");
     return SBE_OK;
@@ -406,16 +401,7 @@ const char* sbe_align_last_error(const sbe_align* h) { return unit_last_error(h)
 
 int64_t sbe_align_max_objects(int n_clusters) { return max_objects(n_clusters); }
 
-int sbe_align_create(sbe_align** out, int device) {
-    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
-    *out = nullptr;
-    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
-    sbe_align* h = nullptr;
-    const int rc = unit_open(h, device, "sbe_align_create", "");
-    if (rc) return rc;
-    *out = h;
-    return SBE_OK;
-}
+int sbe_align_create(sbe_align** out, int device) { return unit_create_on_device(out, device, "sbe_align_create"); }
 
 int sbe_align_destroy(sbe_align* h) { return unit_destroy(h, kNullHandle); }
 
@@ -431,8 +417,7 @@ int sbe_align_reset(sbe_align* h, int n_runs, int n_clusters, int64_t n_objects,
     if (capacity_rows < 1 || capacity_rows > SBE_ALIGN_MAX_ROWS)
         return fail(h, SBE_ERR_ARG, "capacity_rows=%lld out of range [1, %d]", (long long)capacity_rows, SBE_ALIGN_MAX_ROWS);
     const int64_t W = (n_objects + 31) / 32;
-    h->runs = 0;                                          // (a failed allocation leaves an unshaped store)
-    h->rows.clear();
+    h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
     h->perm_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = unit_ensure(h, h->d_bits, h->bits_bytes, (size_t)n_runs * (size_t)capacity_rows * (size_t)n_clusters * (size_t)W * sizeof(uint32_t));
@@ -443,58 +428,44 @@ int sbe_align_reset(sbe_align* h, int n_runs, int n_clusters, int64_t n_objects,
     if (!rc) rc = unit_ensure(h, h->d_run_perm, (size_t)SBE_ALIGN_MAX_RUNS * kMaxK);
     if (!rc) rc = unit_ensure(h, h->d_agree, (size_t)SBE_ALIGN_MAX_RUNS * kMaxK * kMaxK * sizeof(long long));
     if (rc) return rc;
-    h->runs = n_runs;
     h->K = n_clusters;
     h->N = n_objects;
     h->W = W;
-    h->cap = capacity_rows;
-    h->rows.assign((size_t)n_runs, 0);
+    h->runs.cap = capacity_rows;
+    h->runs.rows.assign((size_t)n_runs, 0);
     return SBE_OK;
 }
 
 int sbe_align_rows(const sbe_align* h, int run, int64_t* n_rows_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!n_rows_out) return fail(h, SBE_ERR_ARG, "null pointer argument: n_rows_out");
-    if (run < 0 || run >= h->runs) return fail(h, SBE_ERR_ARG, "run %d out of range [0,%d)", run, h->runs);
-    *n_rows_out = h->rows[(size_t)run];
-    return SBE_OK;
+    return h->runs.get(h, kLane, run, n_rows_out);
 }
 
 int sbe_align_append_rows(sbe_align* h, int run, const uint8_t* rows, int64_t n_rows) {
     CHECK_HANDLE(h, kNullHandle);
-    if (h->runs == 0) return fail(h, SBE_ERR_STATE, "the store has no shape yet (sbe_align_reset)");
-    if (run < 0 || run >= h->runs) return fail(h, SBE_ERR_ARG, "run %d out of range [0,%d)", run, h->runs);
-    if (n_rows < 0) return fail(h, SBE_ERR_ARG, "n_rows=%lld is negative", (long long)n_rows);
-    if (n_rows > 0 && !rows) return fail(h, SBE_ERR_ARG, "null pointer argument: rows");
-    const int64_t have = h->rows[(size_t)run];
-    if (have + n_rows > h->cap)
-        return fail(h, SBE_ERR_ARG, "store overflow: run %d holds %lld rows, %lld more exceed the capacity of %lld rows", run, (long long)have,
-                    (long long)n_rows, (long long)h->cap);
-    if (n_rows == 0) return SBE_OK;
+    int rc = h->runs.check_append(h, kLane, kReset, run, rows, n_rows);
+    if (rc || n_rows == 0) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    const int64_t row_bytes = (int64_t)h->K * h->N;
-    const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(h->cap, kStageBytes / row_bytes));
-    const int rc = unit_ensure(h, h->d_stage, h->stage_bytes, (size_t)piece * (size_t)row_bytes);
-    if (rc) return rc;
-    h->perm_valid = false;
-    for (int64_t r = 0; r < n_rows; r += piece) {
-        const int64_t k = std::min(piece, n_rows - r), lines = k * h->K;
-        HIPCHK(h, hipMemcpyAsync(h->d_stage, rows + r * row_bytes, (size_t)k * (size_t)row_bytes, hipMemcpyHostToDevice, h->stream));
-        uint32_t* out = h->d_bits + ((int64_t)run * h->cap + have + r) * h->K * h->W;
-        for (int64_t l0 = 0; l0 < lines; l0 += kMaxGridBlocks) {
-            const dim3 grid((unsigned)std::min(kMaxGridBlocks, lines - l0), (unsigned)div_up(h->N, kAlignBlock));
-            k_align_pack<<<grid, kAlignBlock, 0, h->stream>>>(h->d_stage, lines, (int)h->N, (int)h->W, out, l0);
+    const int64_t have = h->runs.rows[(size_t)run];
+    rc = unit_append_pieces(h, h->d_stage, h->stage_bytes, rows, n_rows, (int64_t)h->K * h->N, h->runs.cap, [&](int64_t k, int64_t r) {
+        h->perm_valid = false;                            // (the store changes from the first piece on)
+        const int64_t lines = k * h->K;
+        uint32_t* out = h->d_bits + ((int64_t)run * h->runs.cap + have + r) * h->K * h->W;
+        return unit_for_grid_chunks(lines, [&](int64_t l0, int64_t n) {
+            k_align_pack<<<dim3((unsigned)n, (unsigned)div_up(h->N, kAlignBlock)), kAlignBlock, 0, h->stream>>>((const uint8_t*)h->d_stage, lines,
+                                                                                                             (int)h->N, (int)h->W, out, l0);
             HIPCHK(h, hipGetLastError());
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));      // (the staging buffer is reused by the next piece)
-    }
-    h->rows[(size_t)run] = have + n_rows;
+            return SBE_OK;
+        });
+    });
+    if (rc) return rc;
+    h->runs.rows[(size_t)run] = have + n_rows;
     return SBE_OK;
 }
 
 int sbe_align_within(sbe_align* h, int seed_rows, int8_t* perm_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (h->runs == 0) return fail(h, SBE_ERR_STATE, "the store has no shape yet (sbe_align_reset)");
+    if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
     if (seed_rows < 0 || seed_rows > SBE_ALIGN_MAX_SEED_ROWS)
         return fail(h, SBE_ERR_ARG, "seed_rows=%d out of range [0, %d]", seed_rows, SBE_ALIGN_MAX_SEED_ROWS);
     if (!perm_out) return fail(h, SBE_ERR_ARG, "null pointer argument: perm_out");
@@ -503,28 +474,27 @@ int sbe_align_within(sbe_align* h, int seed_rows, int8_t* perm_out) {
     if (rc) return rc;
     int G = 1;                                            // slices per word: the items fill the block where they can
     while (G < 32 && h->W * G * 2 <= kAlignBlock) G *= 2;
-    const WithinArgs args{h->d_bits, h->d_rows, h->d_perm, h->cap, (int)h->N, (int)h->W, G, seed_rows};
+    const WithinArgs args{h->d_bits, h->d_rows, h->d_perm, h->runs.cap, (int)h->N, (int)h->W, G, seed_rows};
     const size_t lds = (size_t)h->K * 32 * (size_t)h->W * sizeof(int32_t);
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    switch (h->K) {
-        case 1: rc = launch_within<1>(h, args, lds); break;
-        case 2: rc = launch_within<2>(h, args, lds); break;
-        case 3: rc = launch_within<3>(h, args, lds); break;
-        case 4: rc = launch_within<4>(h, args, lds); break;
-        case 5: rc = launch_within<5>(h, args, lds); break;
-        case 6: rc = launch_within<6>(h, args, lds); break;
-        case 7: rc = launch_within<7>(h, args, lds); break;
-        default: rc = launch_within<8>(h, args, lds); break;
-    }
+    rc = unit_timed(h, [&] {
+        switch (h->K) {
+            case 1: return launch_within<1>(h, args, lds);
+            case 2: return launch_within<2>(h, args, lds);
+            case 3: return launch_within<3>(h, args, lds);
+            case 4: return launch_within<4>(h, args, lds);
+            case 5: return launch_within<5>(h, args, lds);
+            case 6: return launch_within<6>(h, args, lds);
+            case 7: return launch_within<7>(h, args, lds);
+            default: return launch_within<8>(h, args, lds);
+        }
+    });
     if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    for (int r = 0; r < h->runs; ++r) {
-        const size_t bytes = (size_t)h->rows[(size_t)r] * (size_t)h->K;
+    for (int r = 0; r < h->runs.count(); ++r) {
+        const size_t bytes = (size_t)h->runs.rows[(size_t)r] * (size_t)h->K;
         if (bytes)
-            HIPCHK(h, hipMemcpyAsync(perm_out + (int64_t)r * h->cap * h->K, h->d_perm + (int64_t)r * h->cap * h->K, bytes, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(perm_out + (int64_t)r * h->runs.cap * h->K, h->d_perm + (int64_t)r * h->runs.cap * h->K, bytes, hipMemcpyDeviceToHost, h->stream));
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    if ((rc = unit_sync_timed(h))) return rc;
     h->perm_valid = true;
     return SBE_OK;
 }
@@ -536,7 +506,7 @@ int sbe_align_counts(sbe_align* h, int aligned, const int64_t* burn_rows, int32_
     if (!counts_out) return fail(h, SBE_ERR_ARG, "null pointer argument: counts_out");
     rc = run_counts(h, aligned, burn_rows);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->d_cnt, (size_t)h->runs * (size_t)h->K * (size_t)h->N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->d_cnt, (size_t)h->runs.count() * (size_t)h->K * (size_t)h->N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return SBE_OK;
 }
@@ -545,7 +515,7 @@ int sbe_align_runs(sbe_align* h, int pivot, int aligned, const int64_t* burn_row
     CHECK_HANDLE(h, kNullHandle);
     int rc = check_counts_args(h, aligned, burn_rows);
     if (rc) return rc;
-    if (pivot < 0 || pivot >= h->runs) return fail(h, SBE_ERR_ARG, "pivot %d out of range [0,%d)", pivot, h->runs);
+    if (pivot < 0 || pivot >= h->runs.count()) return fail(h, SBE_ERR_ARG, "pivot %d out of range [0,%d)", pivot, h->runs.count());
     if (!run_perm_out || !agreement_out) return fail(h, SBE_ERR_ARG, "null pointer argument: output");
     rc = run_counts(h, aligned, burn_rows);
     if (rc) return rc;
@@ -560,8 +530,8 @@ int sbe_align_runs(sbe_align* h, int pivot, int aligned, const int64_t* burn_row
         default: rc = launch_runs<8>(h, pivot); break;
     }
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(run_perm_out, h->d_run_perm, (size_t)h->runs * (size_t)h->K, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(agreement_out, h->d_agree, (size_t)h->runs * (size_t)h->K * (size_t)h->K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(run_perm_out, h->d_run_perm, (size_t)h->runs.count() * (size_t)h->K, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(agreement_out, h->d_agree, (size_t)h->runs.count() * (size_t)h->K * (size_t)h->K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return SBE_OK;
 }

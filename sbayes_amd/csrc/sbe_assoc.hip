@@ -323,7 +323,6 @@ struct sbe_assoc : sbe_unit_handle {             // (sbe_unit.hip.h; ev: around 
 
 namespace {
 
-constexpr sbe_assoc* kNone = nullptr;               // (fail without a handle: the type names the unit)
 constexpr char kNullHandle[] = "null handle";
 
 }  // namespace
@@ -334,16 +333,7 @@ int sbe_assoc_abi_version(void) { return SBE_ASSOC_ABI_VERSION; }
 
 const char* sbe_assoc_last_error(const sbe_assoc* h) { return unit_last_error(h); }
 
-int sbe_assoc_create(sbe_assoc** out, int device) {
-    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
-    *out = nullptr;
-    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
-    sbe_assoc* h = nullptr;
-    const int rc = unit_open(h, device, "sbe_assoc_create", "");
-    if (rc) return rc;
-    *out = h;
-    return SBE_OK;
-}
+int sbe_assoc_create(sbe_assoc** out, int device) { return unit_create_on_device(out, device, "sbe_assoc_create"); }
 
 int sbe_assoc_destroy(sbe_assoc* h) { return unit_destroy(h, kNullHandle); }
 
@@ -416,22 +406,21 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
     HIPCHK(h, hipMemcpyAsync(h->d_xt, xt.data(), xt.size(), hipMemcpyHostToDevice, h->stream));
     k_assoc_diagonal<<<div_up(F, 256), 256, 0, h->stream>>>((int)F, d_stat, d_p, d_dof, d_n, d_valid);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     int64_t launches = 0;
-    for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch, ++launches) {          // one wave per tile pair
-        const int64_t t_end = std::min(tile_pairs, t0 + per_launch);
-        const PairArgs args{h->d_xt, n_pad, (int)F, log_s, t0, t_end, d_stat, d_p, d_dof, d_n, d_valid};
-        k_assoc_pairs<<<(unsigned)(t_end - t0), 64, pair_lds_bytes(sub), h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipMemcpyAsync(statistic, d_stat, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(pvalue, d_p, ff * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dof, d_dof, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(n, d_n, ff * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(valid, d_valid, ff, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    rc = unit_timed(h, [&] {
+        for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch, ++launches) {      // one wave per tile pair
+            const int64_t t_end = std::min(tile_pairs, t0 + per_launch);
+            const PairArgs args{h->d_xt, n_pad, (int)F, log_s, t0, t_end, d_stat, d_p, d_dof, d_n, d_valid};
+            k_assoc_pairs<<<(unsigned)(t_end - t0), 64, pair_lds_bytes(sub), h->stream>>>(args);
+            HIPCHK(h, hipGetLastError());
+        }
+        return SBE_OK;
+    });
+    if (!rc) rc = unit_copy_back(h, (const double*)d_stat, ff, {statistic, pvalue});
+    if (!rc) rc = unit_copy_back(h, (const int32_t*)d_dof, ff, {dof, n});
+    if (!rc) rc = unit_copy_back(h, (const uint8_t*)d_valid, ff, {valid});
+    if (!rc) rc = unit_sync_timed(h);
+    if (rc) return rc;
     h->N = N;
     h->n_pad = n_pad;
     h->F = F;

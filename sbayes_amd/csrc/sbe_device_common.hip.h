@@ -247,6 +247,9 @@ __device__ float np_pairwise_sum_f32_x8(Get get, int n, int j) {
 
 // ------------------------------------------------------------------------------------------
 // wave64 / block reductions (fixed order => run-to-run deterministic)
+// NOT the side units' unit_wave_reduce / unit_block_reduce (sbe_unit_device.hip.h: xor exchanges, then the waves added in
+// index order, valid in every thread).  The two families add in different orders, so their results differ in the last
+// bits: they are not interchangeable.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

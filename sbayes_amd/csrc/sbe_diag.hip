@@ -32,10 +32,7 @@ constexpr int kLagsPerLane = 8;                      // lags a lane keeps in reg
 constexpr int kLagBlock = kDiagWaves * kLagsPerLane; // lags evaluated between two walks of the positive-sequence rule
 constexpr int kMaxSplitChains = 2 * SBE_DIAG_MAX_CHAINS;
 constexpr int kRhoLds = 2048;                        // rho_t entries kept in LDS; later ones go to the column's scratch
-constexpr size_t kLdsBudget = (size_t)160 << 10;     // LDS per CU on MI355X
 constexpr size_t kStaticLds = 4096;                  // headroom for the kernel's static LDS (chain means, lag block, reductions)
-// workgroups per launch: an AQL dispatch holds its grid in work-items as a uint32 ("Column count")
-constexpr int64_t kMaxGridBlocks = ((int64_t)1 << 24) - 1;
 // launch rule: multiply-adds of a launch whose columns all run to the n - 3 bound (M * n * n / 2 each) stay below this,
 // but a launch holds at least one column per CU
 constexpr double kLaunchWork = 4398046511104.0;      // 2^42
@@ -43,42 +40,6 @@ constexpr int64_t kMinLaunchColumns = 256;
 constexpr size_t kScratchBytes = (size_t)256 << 20;  // rho_t scratch of one launch (columns with n > kRhoLds)
 
 constexpr int64_t kLdsMaxDraws = (int64_t)((kLdsBudget - kStaticLds - (size_t)kRhoLds * sizeof(double)) / sizeof(double));
-
-// ---- reductions (fixed tree: lanes by xor exchanges, then the waves in order) -------------------------------------
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ inline double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // (red may still be read by the previous reduction)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < kDiagWaves; ++w) t += red[w];
-    return t;
-}
-
-__device__ inline double block_min(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < kDiagWaves; ++w) t = fmin(t, red[w]);
-    return t;
-}
-
-__device__ inline int block_or(int v, int* red) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = red[0];
-    for (int w = 1; w < kDiagWaves; ++w) t |= red[w];
-    return t;
-}
 
 struct DiagArgs {
     const double* x;          // store: [chains][P][cap]
@@ -124,7 +85,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
             nhi = fmin(nhi, -v);
         }
     }
-    bad = block_or(bad, ired);
+    bad = unit_block_reduce<kDiagWaves>(bad, ired, unit_or{});
     if (bad) {                                               // (uniform over the block)
         if (tid == 0) {
             for (int q = 0; q < 5; ++q) a.out[q * a.P + j] = NAN;
@@ -133,8 +94,8 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
         }
         return;
     }
-    lo = block_min(lo, red);
-    nhi = block_min(nhi, red);
+    lo = unit_block_reduce<kDiagWaves>(lo, red, unit_min{});
+    nhi = unit_block_reduce<kDiagWaves>(nhi, red, unit_min{});
     const bool constant = (-nhi) - lo < 1e-15;
 
     // chain means: one wave per chain; the sum, then the sum of the residuals added back
@@ -142,10 +103,10 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
         const double* xm = col + a.off[m];
         double s = 0.0;
         for (int i = lane; i < n; i += 64) s += xm[i];
-        const double mu0 = wave_sum(s) / n;
+        const double mu0 = unit_wave_reduce(s, unit_sum{}) / n;
         double r = 0.0;
         for (int i = lane; i < n; i += 64) r += xm[i] - mu0;
-        const double mu1 = mu0 + wave_sum(r) / n;
+        const double mu1 = mu0 + unit_wave_reduce(r, unit_sum{}) / n;
         if (lane == 0) mu[m] = mu1;
     }
     __syncthreads();
@@ -176,7 +137,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
             ssq += v * v;
         }
     }
-    ssq = block_sum(ssq, red);
+    ssq = unit_block_reduce<kDiagWaves>(ssq, red, unit_sum{});
     const double total = (double)M * (double)n;
     const double sd = sqrt(ssq / (total - 1.0));
     if (constant) {
@@ -215,7 +176,7 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
         }
 #pragma unroll
         for (int r = 0; r < kLagsPerLane; ++r) {
-            const double g = wave_sum(acc[r]);
+            const double g = unit_wave_reduce(acc[r], unit_sum{});
             if (lane == 0) gblk[wave * kLagsPerLane + r] = g / n / M;
         }
         __syncthreads();
@@ -272,34 +233,15 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_column(DiagArgs a) {
     }
 }
 
-// host rows [n][P] (staging) -> one chain's columns [P][cap] at row offset r0: 32 x 32 tiles through LDS
-__global__ __launch_bounds__(256) void k_diag_transpose(const double* rows, int64_t n, int64_t P, double* x, int64_t cap, int64_t r0,
-                                                        int64_t pt0) {
-    __shared__ double tile[32][33];
-    const int64_t p0 = (pt0 + blockIdx.x) * 32, n0 = (int64_t)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        const int64_t row = n0 + r, c = p0 + tx;
-        if (row < n && c < P) tile[r][tx] = rows[row * P + c];
-    }
-    __syncthreads();
-    for (int c = ty; c < 32; c += 8) {
-        const int64_t cc = p0 + c, row = n0 + tx;
-        if (row < n && cc < P) x[cc * cap + r0 + row] = tile[tx][c];
-    }
-}
-
 }  // namespace
 
 struct sbe_diag : sbe_unit_handle {            // (sbe_unit.hip.h; ev: around the column kernel of the last compute call)
-    int chains = 0;
-    int64_t P = 0, cap = 0;
-    std::vector<int64_t> rows;          // [chains]
+    unit_lanes chains;                  // (empty: no shape yet)
+    int64_t P = 0;
     double* d_x = nullptr;              // [chains][P][cap]
     size_t x_bytes = 0;
-    double* d_stage = nullptr;          // host rows in flight
+    void* d_stage = nullptr;            // host rows in flight
     size_t stage_bytes = 0;
-    int64_t stage_rows = 0;
     double* d_out = nullptr;            // [5][P]
     size_t out_bytes = 0;
     int32_t* d_lags = nullptr;          // [P]
@@ -317,9 +259,8 @@ struct sbe_diag : sbe_unit_handle {            // (sbe_unit.hip.h; ev: around th
 
 namespace {
 
-constexpr sbe_diag* kNone = nullptr;                  // (fail without a handle: the type names the unit)
 constexpr char kNullHandle[] = "null handle";
-constexpr int64_t kStageBytes = (int64_t)64 << 20;    // host rows are moved in pieces of at most 64 MiB
+constexpr char kLane[] = "chain", kReset[] = "sbe_diag_reset";
 
 int64_t default_launch_columns(int M, int64_t n) {
     const double per_column = 0.5 * (double)M * (double)n * (double)n;
@@ -338,16 +279,7 @@ const char* sbe_diag_last_error(const sbe_diag* h) { return unit_last_error(h); 
 
 int64_t sbe_diag_lds_max_draws(void) { return kLdsMaxDraws; }
 
-int sbe_diag_create(sbe_diag** out, int device) {
-    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
-    *out = nullptr;
-    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
-    sbe_diag* h = nullptr;
-    const int rc = unit_open(h, device, "sbe_diag_create", "");
-    if (rc) return rc;
-    *out = h;
-    return SBE_OK;
-}
+int sbe_diag_create(sbe_diag** out, int device) { return unit_create_on_device(out, device, "sbe_diag_create"); }
 
 int sbe_diag_destroy(sbe_diag* h) { return unit_destroy(h, kNullHandle); }
 
@@ -371,8 +303,7 @@ int sbe_diag_reset(sbe_diag* h, int n_chains, int64_t n_columns, int64_t capacit
     const double bytes = (double)n_chains * (double)n_columns * (double)capacity_rows * sizeof(double);
     if (bytes > 1.0e15) return fail(h, SBE_ERR_ARG, "a store of %d x %lld x %lld float64 values is out of range", n_chains,
                                      (long long)n_columns, (long long)capacity_rows);
-    h->chains = 0;                                        // (a failed allocation leaves an unshaped store)
-    h->rows.clear();
+    h->chains.rows.clear();                               // (a failed allocation leaves an unshaped store)
     HIPCHK(h, hipSetDevice(h->device));
     int rc = unit_ensure(h, h->d_x, h->x_bytes, (size_t)n_chains * (size_t)n_columns * (size_t)capacity_rows * sizeof(double));
     if (!rc) rc = unit_ensure(h, h->d_out, h->out_bytes, (size_t)n_columns * 5 * sizeof(double));
@@ -380,69 +311,56 @@ int sbe_diag_reset(sbe_diag* h, int n_chains, int64_t n_columns, int64_t capacit
     if (!rc) rc = unit_ensure(h, h->d_flag, h->flag_bytes, (size_t)n_columns);
     if (!rc) rc = unit_ensure(h, h->d_off, (size_t)kMaxSplitChains * sizeof(int64_t));
     if (rc) return rc;
-    h->chains = n_chains;
     h->P = n_columns;
-    h->cap = capacity_rows;
-    h->rows.assign((size_t)n_chains, 0);
+    h->chains.cap = capacity_rows;
+    h->chains.rows.assign((size_t)n_chains, 0);
     return SBE_OK;
 }
 
 int sbe_diag_rows(const sbe_diag* h, int chain, int64_t* n_rows_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!n_rows_out) return fail(h, SBE_ERR_ARG, "null pointer argument: n_rows_out");
-    if (chain < 0 || chain >= h->chains) return fail(h, SBE_ERR_ARG, "chain %d out of range [0,%d)", chain, h->chains);
-    *n_rows_out = h->rows[(size_t)chain];
-    return SBE_OK;
+    return h->chains.get(h, kLane, chain, n_rows_out);
 }
 
 int sbe_diag_append_rows(sbe_diag* h, int chain, const double* rows, int64_t n_rows) {
     CHECK_HANDLE(h, kNullHandle);
-    if (h->chains == 0) return fail(h, SBE_ERR_STATE, "the store has no shape yet (sbe_diag_reset)");
-    if (chain < 0 || chain >= h->chains) return fail(h, SBE_ERR_ARG, "chain %d out of range [0,%d)", chain, h->chains);
-    if (n_rows < 0) return fail(h, SBE_ERR_ARG, "n_rows=%lld is negative", (long long)n_rows);
-    if (n_rows > 0 && !rows) return fail(h, SBE_ERR_ARG, "null pointer argument: rows");
-    const int64_t have = h->rows[(size_t)chain];
-    if (have + n_rows > h->cap)
-        return fail(h, SBE_ERR_ARG, "store overflow: chain %d holds %lld rows, %lld more exceed the capacity of %lld rows", chain,
-                    (long long)have, (long long)n_rows, (long long)h->cap);
-    if (n_rows == 0) return SBE_OK;
+    int rc = h->chains.check_append(h, kLane, kReset, chain, rows, n_rows);
+    if (rc || n_rows == 0) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    h->stage_rows = std::max<int64_t>(1, std::min<int64_t>(h->cap, kStageBytes / ((int64_t)sizeof(double) * h->P)));
-    const int rc = unit_ensure(h, h->d_stage, h->stage_bytes, (size_t)h->stage_rows * (size_t)h->P * sizeof(double));
-    if (rc) return rc;
-    double* x = h->d_x + (int64_t)chain * h->P * h->cap;
-    for (int64_t r = 0; r < n_rows; r += h->stage_rows) {
-        const int64_t k = std::min(h->stage_rows, n_rows - r);
-        HIPCHK(h, hipMemcpyAsync(h->d_stage, rows + r * h->P, (size_t)k * (size_t)h->P * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const int64_t tiles = (h->P + 31) / 32;
-        for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
-            const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
-            k_diag_transpose<<<grid, 256, 0, h->stream>>>(h->d_stage, k, h->P, x, h->cap, have + r, t0);
+    const int64_t P = h->P, cap = h->chains.cap, have = h->chains.rows[(size_t)chain];
+    double* x = h->d_x + (int64_t)chain * P * cap;
+    rc = unit_append_pieces(h, h->d_stage, h->stage_bytes, rows, n_rows, (int64_t)sizeof(double) * P, cap, [&](int64_t k, int64_t r) {
+        return unit_for_grid_chunks((P + 31) / 32, [&](int64_t t0, int64_t tiles) {
+            k_unit_transpose<<<dim3((unsigned)tiles, (unsigned)((k + 31) / 32)), 256, 0, h->stream>>>((const double*)h->d_stage, k, P, x, cap,
+                                                                                                     have + r, t0);
             HIPCHK(h, hipGetLastError());
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));      // (the staging buffer is reused by the next piece)
-    }
-    h->rows[(size_t)chain] = have + n_rows;
+            return SBE_OK;
+        });
+    });
+    if (rc) return rc;
+    h->chains.rows[(size_t)chain] = have + n_rows;
     return SBE_OK;
 }
 
 int sbe_diag_compute(sbe_diag* h, const int64_t* burn_rows, int split, int64_t max_lag, double* mean_out, double* sd_out,
                      double* ess_out, double* rhat_out, double* mcse_mean_out, int32_t* n_lags_out, uint8_t* flag_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (h->chains == 0) return fail(h, SBE_ERR_STATE, "the store has no shape yet (sbe_diag_reset)");
+    if (const int rc = h->chains.check_shaped(h, kReset)) return rc;
     if (!burn_rows) return fail(h, SBE_ERR_ARG, "null pointer argument: burn_rows");
     if (!mean_out || !sd_out || !ess_out || !rhat_out || !mcse_mean_out || !n_lags_out || !flag_out)
         return fail(h, SBE_ERR_ARG, "null pointer argument: output");
     if (max_lag < 0 || max_lag > INT32_MAX) return fail(h, SBE_ERR_ARG, "max_lag=%lld out of range [0, %d] (0: none)", (long long)max_lag, INT32_MAX);
+    const int chains = h->chains.count();
+    const int64_t cap = h->chains.cap;
     int64_t len = INT64_MAX;
-    for (int c = 0; c < h->chains; ++c) {
-        const int64_t have = h->rows[(size_t)c];
+    for (int c = 0; c < chains; ++c) {
+        const int64_t have = h->chains.rows[(size_t)c];
         if (burn_rows[c] < 0 || burn_rows[c] > have)
             return fail(h, SBE_ERR_ARG, "burn_rows[%d]=%lld out of range [0, %lld] (rows stored for the chain)", c, (long long)burn_rows[c],
                         (long long)have);
         len = std::min(len, have - burn_rows[c]);
     }
-    const int M = split ? 2 * h->chains : h->chains;
+    const int M = split ? 2 * chains : chains;
     const int64_t n = split ? len / 2 : len;
     if (n < SBE_DIAG_MIN_DRAWS)
         return fail(h, SBE_ERR_ARG, "%lld draws per chain after burn-in%s; at least %d are needed", (long long)n,
@@ -451,8 +369,8 @@ int sbe_diag_compute(sbe_diag* h, const int64_t* burn_rows, int split, int64_t m
         return fail(h, SBE_ERR_ARG, "%d chains x %lld draws after burn-in%s exceed %d (2^20) draws per column", M, (long long)n,
                     split ? " and split" : "", SBE_DIAG_MAX_DRAWS);
     std::vector<int64_t> off((size_t)M);
-    for (int c = 0; c < h->chains; ++c) {
-        const int64_t base = (int64_t)c * h->P * h->cap + burn_rows[c];
+    for (int c = 0; c < chains; ++c) {
+        const int64_t base = (int64_t)c * h->P * cap + burn_rows[c];
         if (split) {
             off[(size_t)(2 * c)] = base;                     // x[:h]
             off[(size_t)(2 * c + 1)] = base + len - n;       // x[-h:]
@@ -475,22 +393,22 @@ int sbe_diag_compute(sbe_diag* h, const int64_t* burn_rows, int split, int64_t m
     auto kernel = staged ? k_diag_column<true> : k_diag_column<false>;
     HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
     HIPCHK(h, hipMemcpyAsync(h->d_off, off.data(), (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     int64_t launches = 0;
-    for (int64_t j0 = 0; j0 < h->P; j0 += per_launch, ++launches) {
-        const DiagArgs args{h->d_x, h->d_off, h->cap, M, (int)n, (int)max_lag, rho_lds, spill ? h->d_scratch : nullptr,
-                            h->d_out, h->d_lags, h->d_flag, h->P, j0};
-        kernel<<<(unsigned)std::min(per_launch, h->P - j0), kDiagBlock, lds, h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    double* outs[5] = {mean_out, sd_out, ess_out, rhat_out, mcse_mean_out};
-    for (int q = 0; q < 5; ++q)
-        HIPCHK(h, hipMemcpyAsync(outs[q], h->d_out + q * h->P, (size_t)h->P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(n_lags_out, h->d_lags, (size_t)h->P * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(flag_out, h->d_flag, (size_t)h->P, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    int rc = unit_timed(h, [&] {
+        for (int64_t j0 = 0; j0 < h->P; j0 += per_launch, ++launches) {
+            const DiagArgs args{h->d_x, h->d_off, cap, M, (int)n, (int)max_lag, rho_lds, spill ? h->d_scratch : nullptr,
+                                h->d_out, h->d_lags, h->d_flag, h->P, j0};
+            kernel<<<(unsigned)std::min(per_launch, h->P - j0), kDiagBlock, lds, h->stream>>>(args);
+            HIPCHK(h, hipGetLastError());
+        }
+        return SBE_OK;
+    });
+    const size_t P = (size_t)h->P;
+    if (!rc) rc = unit_copy_back(h, (const double*)h->d_out, P, {mean_out, sd_out, ess_out, rhat_out, mcse_mean_out});
+    if (!rc) rc = unit_copy_back(h, (const int32_t*)h->d_lags, P, {n_lags_out});
+    if (!rc) rc = unit_copy_back(h, (const uint8_t*)h->d_flag, P, {flag_out});
+    if (!rc) rc = unit_sync_timed(h);
+    if (rc) return rc;
     h->last_M = M;
     h->last_n = n;
     h->last_path = staged ? SBE_DIAG_PATH_LDS : SBE_DIAG_PATH_GLOBAL;

@@ -29,14 +29,9 @@ namespace {
 constexpr int kElpdBlock = 256;                      // 4 waves per column
 constexpr int kElpdWaves = kElpdBlock / 64;
 constexpr int kMaxM = 96;                            // _gpdfit candidates: 30 + sqrt(T) <= 85 for S <= 2^20 (T <= 3072)
-constexpr size_t kLdsBudget = (size_t)160 << 10;     // LDS per CU on MI355X (MI355X_MICROARCH.md)
 constexpr size_t kStaticLds = 8192;                  // headroom for the kernel's static LDS (histogram, reductions, fit)
-// workgroups per launch along x: an AQL dispatch holds its grid in work-items as a uint32, so every launch below stays
-// under 2^32 work-items and longer ranges are launched in chunks, each with its offset
-constexpr int64_t kMaxGridBlocks = ((int64_t)1 << 24) - 1;
 
 inline int tail_count(int64_t s) { return (int)std::ceil(std::min(0.2 * (double)s, 3.0 * std::sqrt((double)s))); }
-inline int pow2_at_least(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 // dynamic LDS of a column of S samples: [tail exceedances Tp x f64][tail keys Tp x u32][staged column S x u32]
 inline size_t tail_lds_bytes(int64_t s) { return (size_t)pow2_at_least(std::max(tail_count(s), 1)) * (sizeof(uint32_t) + sizeof(double)); }
 inline size_t staged_lds_bytes(int64_t s) { return (size_t)s * sizeof(uint32_t) + tail_lds_bytes(s); }
@@ -46,43 +41,6 @@ int64_t lds_max_samples() {
     int64_t s = 2;
     while (column_staged(s + 1)) ++s;
     return s;
-}
-
-// ---- block reductions (fixed tree: lanes by xor shuffles, then the waves in order) --------------------------------
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ inline double block_sum(double v, double* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                   // (red may still be read by the previous reduction)
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < kElpdWaves; ++w) t += red[w];
-    return t;
-}
-
-__device__ inline uint32_t block_min_u32(uint32_t v, uint32_t* red) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = red[0];
-    for (int w = 1; w < kElpdWaves; ++w) t = min(t, red[w]);
-    return t;
-}
-
-__device__ inline uint32_t block_max_u32(uint32_t v, uint32_t* red) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = red[0];
-    for (int w = 1; w < kElpdWaves; ++w) t = max(t, red[w]);
-    return t;
 }
 
 __device__ inline double ll_of(uint32_t bits) { return log((double)__uint_as_float(bits)); }
@@ -155,8 +113,8 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
         bad |= (u == 0u || u >= 0x7F800000u);        // zero, negative (sign bit), inf, NaN
         umin = min(umin, u);
     }
-    umin = block_min_u32(umin, ured);
-    bad = block_max_u32(bad, ured);
+    umin = unit_block_reduce<kElpdWaves>(umin, ured, unit_min{});
+    bad = unit_block_reduce<kElpdWaves>(bad, ured, unit_max{});
     const uint32_t* v = a.staged ? staged : g;
     if (bad) {                                       // (uniform over the block)
         if (tid == 0) {
@@ -174,8 +132,8 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
         sum_ll += ll_of(u);
         sum_lh += (double)__uint_as_float(u);
     }
-    sum_ll = block_sum(sum_ll, red);
-    sum_lh = block_sum(sum_lh, red);
+    sum_ll = unit_block_reduce<kElpdWaves>(sum_ll, red, unit_sum{});
+    sum_lh = unit_block_reduce<kElpdWaves>(sum_lh, red, unit_sum{});
     const double mean = sum_ll / s;
     const double lppd = log(sum_lh) - log((double)s);        // logsumexp(ll) - log S: float32 lh neither over- nor underflows
 
@@ -211,7 +169,7 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
     // x-ascending position t of candidate keys[nc - 1 - t]; the tail is the x > xcutoff suffix (all candidates here)
     double in_tail = 0.0;
     for (int t = tid; t < nc; t += kElpdBlock) in_tail += (-ll_of(keys[nc - 1 - t]) + ll_min) > xcutoff;
-    const int tail_len = (int)block_sum(in_tail, red);
+    const int tail_len = (int)unit_block_reduce<kElpdWaves>(in_tail, red, unit_sum{});
     const int t0 = nc - tail_len;                            // x-ascending index of the first tail element
 
     // 5. _gpdfit on the exceedances exp(x) - exp(cutoff), ascending
@@ -232,7 +190,7 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
             b += inv_last;
             double acc = 0.0;
             for (int i = lane; i < n; i += 64) acc += log1p(-b * ary[i]);
-            acc = wave_sum(acc);
+            acc = unit_wave_reduce(acc, unit_sum{});
             if (lane == 0) { fit_b[c] = b; fit_k[c] = acc / n; }
         }
         __syncthreads();
@@ -255,7 +213,7 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
         const double b_post = fit_post[0];
         double acc = 0.0;
         for (int i = tid; i < n; i += kElpdBlock) acc += log1p(-b_post * ary[i]);
-        const double k_post = block_sum(acc, red) / n;
+        const double k_post = unit_block_reduce<kElpdWaves>(acc, red, unit_sum{}) / n;
         sigma = -k_post / b_post;
         k_hat = (n * k_post + 10 * 0.5) / (n + 10);
     }
@@ -298,9 +256,9 @@ __global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
         a_body += exp(x);
         b_body += exp(x + ll);
     }
-    var = block_sum(var, red) / s;
-    const double a_all = block_sum(a_body + a_tail, red);
-    const double b_all = block_sum(b_body + b_tail, red);
+    var = unit_block_reduce<kElpdWaves>(var, red, unit_sum{}) / s;
+    const double a_all = unit_block_reduce<kElpdWaves>(a_body + a_tail, red, unit_sum{});
+    const double b_all = unit_block_reduce<kElpdWaves>(b_body + b_tail, red, unit_sum{});
     if (tid == 0) {
         a.out[j] = log(b_all) - log(a_all);                   // logsumexp(x' - logsumexp(x') + ll)
         a.out[a.n_kept + j] = k_hat;
@@ -317,28 +275,11 @@ __global__ __launch_bounds__(256) void k_elpd_isclose(const float* lh, int64_t c
     const float* c = lh + col * cap;
     int far = 0;
     for (int64_t i = threadIdx.x & 63; i < n_rows; i += 64) far |= !(fabs((double)c[i] - 1.0) <= 1e-8 + 1e-5 * 1.0);
-    for (int o = 32; o > 0; o >>= 1) far |= __shfl_xor(far, o, 64);
+    far = unit_wave_reduce(far, unit_or{});
     if ((threadIdx.x & 63) == 0) keep[col] = (uint8_t)far;
 }
 
-// host rows [n][M] (staging) -> store columns [M][cap] at row offset r0: 32 x 32 tiles through LDS
-__global__ __launch_bounds__(256) void k_elpd_transpose(const float* rows, int64_t n, int64_t M, float* lh, int64_t cap, int64_t r0,
-                                                        int64_t mt0) {
-    __shared__ float tile[32][33];
-    const int64_t m0 = (mt0 + blockIdx.x) * 32, n0 = (int64_t)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        const int64_t row = n0 + r, col = m0 + tx;
-        if (row < n && col < M) tile[r][tx] = rows[row * M + col];
-    }
-    __syncthreads();
-    for (int c = ty; c < 32; c += 8) {
-        const int64_t col = m0 + c, row = n0 + tx;
-        if (row < n && col < M) lh[col * cap + r0 + row] = tile[tx][c];
-    }
-}
-
-// store columns -> host row order [n][M] (rows read back)
+// store columns -> host row order [n][M] (rows read back): the reverse of k_unit_transpose
 __global__ __launch_bounds__(256) void k_elpd_untranspose(const float* lh, int64_t cap, int64_t r0, int64_t n, int64_t M, float* rows,
                                                           int64_t mt0) {
     __shared__ float tile[32][33];
@@ -366,12 +307,12 @@ __global__ __launch_bounds__(256) void k_elpd_store_row(const double* row, int64
 struct sbe_elpd_store : sbe_unit_handle {     // (sbe_unit.hip.h; ev: around the column kernel of the last compute call)
     int64_t M = 0, cap = 0, n = 0;
     float* d_lh = nullptr;              // [M][cap]
-    float* d_stage = nullptr;           // host rows in flight / rows read back: up to kStageRows rows
+    void* d_stage = nullptr;            // host rows in flight / rows read back: one piece (unit_piece_rows)
+    size_t stage_bytes = 0;
     int32_t* d_cols = nullptr;          // [M]
     uint8_t* d_keep = nullptr;          // [M]
     double* d_out = nullptr;            // [4][M]
     int* d_bad = nullptr;
-    int64_t stage_rows = 0;
     std::vector<void*> buffers() const { return {d_lh, d_stage, d_cols, d_keep, d_out, d_bad}; }
 };
 
@@ -379,13 +320,6 @@ namespace {
 
 constexpr sbe_elpd_store* kNone = nullptr;           // (fail without a handle: the type names the unit)
 constexpr char kNullHandle[] = "null store handle";
-
-constexpr int64_t kStageBytes = (int64_t)64 << 20;    // host rows are moved in pieces of at most 64 MiB
-
-int ensure_stage(sbe_elpd_store* st) {
-    st->stage_rows = std::max<int64_t>(1, std::min<int64_t>(st->cap, kStageBytes / ((int64_t)sizeof(float) * st->M)));
-    return unit_ensure(st, st->d_stage, (size_t)st->stage_rows * st->M * sizeof(float));
-}
 
 }  // namespace
 
@@ -451,19 +385,16 @@ int sbe_elpd_append_rows(sbe_elpd_store* st, const float* rows, int64_t n_rows) 
                      (long long)n_rows, (long long)st->cap);
     if (n_rows == 0) return SBE_OK;
     HIPCHK(st, hipSetDevice(st->device));
-    int rc = ensure_stage(st);
-    if (rc) return rc;
-    for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
-        const int64_t k = std::min(st->stage_rows, n_rows - r);
-        HIPCHK(st, hipMemcpyAsync(st->d_stage, rows + r * st->M, (size_t)k * st->M * sizeof(float), hipMemcpyHostToDevice, st->stream));
-        const int64_t tiles = (st->M + 31) / 32;
-        for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
-            const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
-            k_elpd_transpose<<<grid, 256, 0, st->stream>>>(st->d_stage, k, st->M, st->d_lh, st->cap, st->n + r, t0);
+    const int64_t M = st->M;
+    const int rc = unit_append_pieces(st, st->d_stage, st->stage_bytes, rows, n_rows, (int64_t)sizeof(float) * M, st->cap, [&](int64_t k, int64_t r) {
+        return unit_for_grid_chunks((M + 31) / 32, [&](int64_t t0, int64_t tiles) {
+            k_unit_transpose<<<dim3((unsigned)tiles, (unsigned)((k + 31) / 32)), 256, 0, st->stream>>>((const float*)st->d_stage, k, M, st->d_lh,
+                                                                                                      st->cap, st->n + r, t0);
             HIPCHK(st, hipGetLastError());
-        }
-    }
-    HIPCHK(st, hipStreamSynchronize(st->stream));
+            return SBE_OK;
+        });
+    });
+    if (rc) return rc;
     st->n += n_rows;
     return SBE_OK;
 }
@@ -498,20 +429,21 @@ int sbe_elpd_get_rows(sbe_elpd_store* st, int64_t row0, int64_t n_rows, float* o
     if (n_rows > 0 && !out) return fail(st, SBE_ERR_ARG, "null pointer argument: out");
     if (n_rows == 0) return SBE_OK;
     HIPCHK(st, hipSetDevice(st->device));
-    int rc = ensure_stage(st);
-    if (rc) return rc;
-    for (int64_t r = 0; r < n_rows; r += st->stage_rows) {
-        const int64_t k = std::min(st->stage_rows, n_rows - r);
-        const int64_t tiles = (st->M + 31) / 32;
-        for (int64_t t0 = 0; t0 < tiles; t0 += kMaxGridBlocks) {
-            const dim3 grid((unsigned)std::min(kMaxGridBlocks, tiles - t0), (unsigned)((k + 31) / 32));
-            k_elpd_untranspose<<<grid, 256, 0, st->stream>>>(st->d_lh, st->cap, row0 + r, k, st->M, st->d_stage, t0);
+    const int64_t M = st->M, piece = unit_piece_rows((int64_t)sizeof(float) * M, st->cap);
+    int rc = unit_ensure(st, st->d_stage, st->stage_bytes, (size_t)piece * M * sizeof(float));
+    for (int64_t r = 0; !rc && r < n_rows; r += piece) {
+        const int64_t k = std::min(piece, n_rows - r);
+        rc = unit_for_grid_chunks((M + 31) / 32, [&](int64_t t0, int64_t tiles) {
+            k_elpd_untranspose<<<dim3((unsigned)tiles, (unsigned)((k + 31) / 32)), 256, 0, st->stream>>>(st->d_lh, st->cap, row0 + r, k, M,
+                                                                                                        (float*)st->d_stage, t0);
             HIPCHK(st, hipGetLastError());
-        }
-        HIPCHK(st, hipMemcpyAsync(out + r * st->M, st->d_stage, (size_t)k * st->M * sizeof(float), hipMemcpyDeviceToHost, st->stream));
+            return SBE_OK;
+        });
+        if (rc) break;
+        HIPCHK(st, hipMemcpyAsync(out + r * M, st->d_stage, (size_t)k * M * sizeof(float), hipMemcpyDeviceToHost, st->stream));
         HIPCHK(st, hipStreamSynchronize(st->stream));
     }
-    return SBE_OK;
+    return rc;
 }
 
 int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_values, int na_isclose,
@@ -531,12 +463,12 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
     if (na_values) {
         for (int64_t m = 0; m < st->M; ++m) keep[m] = na_values[m] == 0;
     } else if (na_isclose) {
-        const int64_t blocks = div_up(st->M, 4);
-        for (int64_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-            k_elpd_isclose<<<(unsigned)std::min(kMaxGridBlocks, blocks - b0), 256, 0, st->stream>>>(st->d_lh, st->cap, st->n, st->M,
-                                                                                                 st->d_keep, b0 * 4);
+        const int rc = unit_for_grid_chunks(div_up(st->M, 4), [&](int64_t b0, int64_t blocks) {
+            k_elpd_isclose<<<(unsigned)blocks, 256, 0, st->stream>>>(st->d_lh, st->cap, st->n, st->M, st->d_keep, b0 * 4);
             HIPCHK(st, hipGetLastError());
-        }
+            return SBE_OK;
+        });
+        if (rc) return rc;
         HIPCHK(st, hipMemcpyAsync(keep.data(), st->d_keep, (size_t)st->M, hipMemcpyDeviceToHost, st->stream));
         HIPCHK(st, hipStreamSynchronize(st->stream));
     }
@@ -552,20 +484,19 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
     HIPCHK(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
     HIPCHK(st, hipMemcpyAsync(st->d_cols, cols.data(), (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st->stream));
     HIPCHK(st, hipMemsetAsync(st->d_bad, 0, sizeof(int), st->stream));
-    HIPCHK(st, hipEventRecord(st->ev[0], st->stream));
-    for (int64_t j0 = 0; j0 < nk; j0 += kMaxGridBlocks) {                  // one workgroup per kept column
-        const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, j0, st->d_bad};
-        k_elpd_column<<<(unsigned)std::min(kMaxGridBlocks, nk - j0), kElpdBlock, lds, st->stream>>>(args);
-        HIPCHK(st, hipGetLastError());
-    }
-    HIPCHK(st, hipEventRecord(st->ev[1], st->stream));
+    int rc = unit_timed(st, [&] {
+        return unit_for_grid_chunks(nk, [&](int64_t j0, int64_t columns) {   // one workgroup per kept column
+            const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, j0, st->d_bad};
+            k_elpd_column<<<(unsigned)columns, kElpdBlock, lds, st->stream>>>(args);
+            HIPCHK(st, hipGetLastError());
+            return SBE_OK;
+        });
+    });
     int bad = 0;
-    HIPCHK(st, hipMemcpyAsync(&bad, st->d_bad, sizeof(int), hipMemcpyDeviceToHost, st->stream));
-    double* outs[4] = {loo_i, k_i, lppd_i, v_i};
-    for (int q = 0; q < 4; ++q)
-        HIPCHK(st, hipMemcpyAsync(outs[q], st->d_out + q * nk, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, st->stream));
-    HIPCHK(st, hipStreamSynchronize(st->stream));
-    HIPCHK(st, hipEventElapsedTime(&st->last_kernel_ms, st->ev[0], st->ev[1]));
+    if (!rc) rc = unit_copy_back(st, (const int*)st->d_bad, 1, {&bad});
+    if (!rc) rc = unit_copy_back(st, (const double*)st->d_out, (size_t)nk, {loo_i, k_i, lppd_i, v_i});
+    if (!rc) rc = unit_sync_timed(st);
+    if (rc) return rc;
     if (bad) return fail(st, SBE_ERR_DATA, "%d observation column%s hold likelihood values that are not positive and finite "
                           "in rows [%lld, %lld)", bad, bad == 1 ? "" : "s", (long long)burn_rows, (long long)st->n);
     *n_kept_out = nk;

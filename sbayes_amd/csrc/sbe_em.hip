@@ -22,31 +22,9 @@
 namespace {
 
 constexpr int kEmBlock = 256;
+constexpr int kEmWaves = kEmBlock / 64;                // (the block reductions: every kernel that reduces is launched with kEmBlock)
 constexpr int kEmTableThreads = 64;                  // one wave per (feature, group): thread s sums the objects of state s
 constexpr int kEmGeoRows = 8;                        // cluster rows per thread of k_em_geo (one read of a cost column each)
-
-// ---- block reductions (fixed tree: lanes by xor shuffles, then the waves in order) --------------------------------
-__device__ inline double em_block_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                   // (red may still be read by the previous reduction)
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    return t;
-}
-
-__device__ inline double em_block_max(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t = fmax(t, red[w]);
-    return t;
-}
 
 // counts, p and logp of one (feature f = blockIdx.x, group g = blockIdx.y); logp: [G][F][S+1]
 __global__ __launch_bounds__(kEmTableThreads) void k_em_table(const double* __restrict__ z, const int32_t* __restrict__ perm,
@@ -89,15 +67,15 @@ __global__ __launch_bounds__(kEmBlock) void k_em_ll(const double* __restrict__ l
 
 // zp[k] = softmax(N z[k]) over the objects, one block per cluster row k
 __global__ __launch_bounds__(kEmBlock) void k_em_peaky(const double* __restrict__ z, int64_t n, double* __restrict__ zp) {
-    __shared__ double red[kEmBlock / 64];
+    __shared__ double red[kEmWaves];
     const double* zk = z + (int64_t)blockIdx.x * n;
     const double dn = (double)n;
     double m = -INFINITY;
     for (int64_t i = threadIdx.x; i < n; i += kEmBlock) m = fmax(m, dn * zk[i]);
-    m = em_block_max(m, red);
+    m = unit_block_reduce<kEmWaves>(m, red, unit_max{});
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kEmBlock) s += exp(dn * zk[i] - m);
-    s = em_block_sum(s, red);
+    s = unit_block_reduce<kEmWaves>(s, red, unit_sum{});
     double* out = zp + (int64_t)blockIdx.x * n;
     for (int64_t i = threadIdx.x; i < n; i += kEmBlock) out[i] = exp(dn * zk[i] - m) / s;
 }
@@ -125,13 +103,13 @@ __global__ __launch_bounds__(kEmBlock) void k_em_geo(const double* __restrict__ 
 
 // fill = logsumexp(geo[:K]) - log(K N): the value of every row g >= K (one block)
 __global__ __launch_bounds__(kEmBlock) void k_em_fill(const double* __restrict__ geo, int64_t kn, double* __restrict__ fill) {
-    __shared__ double red[kEmBlock / 64];
+    __shared__ double red[kEmWaves];
     double m = -INFINITY;
     for (int64_t i = threadIdx.x; i < kn; i += kEmBlock) m = fmax(m, geo[i]);
-    m = em_block_max(m, red);
+    m = unit_block_reduce<kEmWaves>(m, red, unit_max{});
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < kn; i += kEmBlock) s += exp(geo[i] - m);
-    s = em_block_sum(s, red);
+    s = unit_block_reduce<kEmWaves>(s, red, unit_sum{});
     if (threadIdx.x == 0) fill[0] = (log(s) + m) - log((double)kn);
 }
 
@@ -355,20 +333,19 @@ int sbe_em_run(sbe_em* h, const double* z_in, int64_t n_steps, const double* tem
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemcpyAsync(h->d_z, z_in, (size_t)(G * N) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_status, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    for (int64_t i = 0; i < n_steps; ++i) {
-        const int rc = enqueue_step(h, temperatures[i]);
-        if (rc) {
-            (void)hipStreamSynchronize(h->stream);
-            return rc;
-        }
-    }
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    int rc = unit_timed(h, [&] {
+        for (int64_t i = 0; i < n_steps; ++i)
+            if (const int step_rc = enqueue_step(h, temperatures[i])) {
+                (void)hipStreamSynchronize(h->stream);
+                return step_rc;
+            }
+        return SBE_OK;
+    });
     int status = 0;
-    HIPCHK(h, hipMemcpyAsync(&status, h->d_status, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(z_out, h->d_z, (size_t)(G * N) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    if (!rc) rc = unit_copy_back(h, (const int*)h->d_status, 1, {&status});
+    if (!rc) rc = unit_copy_back(h, (const double*)h->d_z, (size_t)(G * N), {z_out});
+    if (!rc) rc = unit_sync_timed(h);
+    if (rc) return rc;
     if (status) return fail(h, SBE_ERR_DATA, "an EM step produced a non-finite z (an object whose available groups all have "
                              "likelihood 0, or a non-finite geo prior)");
     return SBE_OK;

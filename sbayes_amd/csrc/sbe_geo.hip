@@ -89,7 +89,8 @@ struct SkeletonArgs {
 };
 
 // lexicographic minimum of (key, member) over the wave, a butterfly in which every lane ends with the result (the
-// comparison is symmetric, so both lanes of an exchange keep the same pair)
+// comparison is symmetric, so both lanes of an exchange keep the same pair).  Not unit_wave_reduce (sbe_unit_device.hip.h):
+// that one exchanges a single value, this one a pair, and the waves meet through a double-buffered LDS exchange
 __device__ inline void keep_smaller(double& k, int& v, double ok, int ov) {
     if (ok < k || (ok == k && ov < v)) { k = ok; v = ov; }
 }
@@ -303,7 +304,6 @@ struct sbe_geo : sbe_unit_handle {              // (sbe_unit.hip.h; ev: around t
 
 namespace {
 
-constexpr sbe_geo* kNone = nullptr;                 // (fail without a handle: the type names the unit)
 constexpr char kNullHandle[] = "null handle";
 
 int check_function(sbe_geo* h, int aggregation, int probability_function, double scale, double x0) {
@@ -383,8 +383,7 @@ int run_skeleton(sbe_geo* h, const uint8_t* masks, int64_t n_masks, int skeleton
     h->lds_masks = lds_masks;
     if (close_events) {
         HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+        if ((rc = unit_sync_timed(h))) return rc;
         h->ran = true;
     }
     return SBE_OK;
@@ -406,16 +405,7 @@ int sbe_geo_abi_version(void) { return SBE_GEO_ABI_VERSION; }
 
 const char* sbe_geo_last_error(const sbe_geo* h) { return unit_last_error(h); }
 
-int sbe_geo_create(sbe_geo** out, int device) {
-    if (!out) return fail(kNone, SBE_ERR_ARG, "null pointer argument: out");
-    *out = nullptr;
-    if (device < 0) return fail(kNone, SBE_ERR_ARG, "device %d out of range", device);
-    sbe_geo* h = nullptr;
-    const int rc = unit_open(h, device, "sbe_geo_create", "");
-    if (rc) return rc;
-    *out = h;
-    return SBE_OK;
-}
+int sbe_geo_create(sbe_geo** out, int device) { return unit_create_on_device(out, device, "sbe_geo_create"); }
 
 int sbe_geo_destroy(sbe_geo* h) { return unit_destroy(h, kNullHandle); }
 
@@ -513,8 +503,7 @@ int sbe_geo_costs_per_object(sbe_geo* h, const uint8_t* mask, int aggregation, i
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     if (ctc_out) HIPCHK(h, hipMemcpyAsync(ctc_out, d_ctc, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(out, d_res, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    if ((rc = unit_sync_timed(h))) return rc;
     h->ran = true;
     return SBE_OK;
 }

@@ -1,17 +1,22 @@
 #pragma once
 // sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip, sbe_align.hip: each an opaque
-// handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check, the
-// device part of create, destroy, and device buffers that only grow.  Host code only and nothing of the engine: a unit
-// that includes this header alone compiles no kernels but its own.  sbe_engine_internal.hip.h takes HIPCHK and div_up
-// from here.  The helpers live in an unnamed namespace, as the engine's do: every unit compiles its own copy.
+// handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check,
+// create, destroy, device buffers that only grow, launches in grid chunks, the row store's lanes and its piece loop, the
+// timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes
+// this header compiles no kernels but its own (the device side is sbe_unit_device.hip.h, taken from here for its launch
+// limit).  sbe_engine_internal.hip.h takes HIPCHK and div_up from here.  The helpers live in an unnamed namespace, as the
+// engine's do: every unit compiles its own copy.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
 
+#include "sbe_unit_device.hip.h"
 #include "../../include/sbe_engine.h"
 
 // What every unit's handle starts with.  The unit's struct derives from it and adds `std::vector<void*> buffers() const`,
@@ -120,6 +125,16 @@ int unit_open(H*& h, int device, const char* who, const char* shape) {
     return SBE_OK;
 }
 
+// The whole body of a create that takes only a device.  `who`: "sbe_<unit>_create".
+template <class H>
+int unit_create_on_device(H** out, int device, const char* who) {
+    constexpr H* none = nullptr;
+    if (!out) return fail(none, SBE_ERR_ARG, "null pointer argument: out");
+    *out = nullptr;
+    if (device < 0) return fail(none, SBE_ERR_ARG, "device %d out of range", device);
+    return unit_open(*out, device, who, "");
+}
+
 // A device buffer that only grows: afterwards p holds at least `want` bytes (what it held before is not kept).  A failure
 // leaves p null and `have` 0, so the next call tries again.
 template <class H, class T>
@@ -138,6 +153,101 @@ template <class H, class T>
 int unit_ensure(H* h, T*& p, size_t bytes) {
     size_t have = p ? bytes : 0;
     return unit_ensure(h, p, have, bytes);
+}
+
+// fn(first, count) for consecutive chunks of [0, total) with count <= kMaxGridBlocks (one launch each, `first` its offset);
+// returns the first non-zero code
+template <class Fn>
+int unit_for_grid_chunks(int64_t total, Fn fn) {
+    for (int64_t first = 0; first < total; first += kMaxGridBlocks) {
+        const int rc = fn(first, std::min(kMaxGridBlocks, total - first));
+        if (rc) return rc;
+    }
+    return SBE_OK;
+}
+
+// ---- the row store: host rows go to the device in pieces through a staging buffer -------------------------------------
+constexpr int64_t kStageBytes = (int64_t)64 << 20;    // host rows are moved in pieces of at most 64 MiB
+
+// rows per piece: at most kStageBytes, at most the store's capacity, at least one row
+inline int64_t unit_piece_rows(int64_t row_bytes, int64_t cap) {
+    return std::max<int64_t>(1, std::min<int64_t>(cap, kStageBytes / row_bytes));
+}
+
+// n_rows > 0 host rows of row_bytes each into a store of `cap` rows: per piece the copy into `stage` (grown to one piece),
+// the unit's launch(piece rows, row offset of the piece within `rows`) and a wait for the stream
+template <class H, class Launch>
+int unit_append_pieces(H* h, void*& stage, size_t& stage_bytes, const void* rows, int64_t n_rows, int64_t row_bytes, int64_t cap,
+                       Launch launch) {
+    const int64_t piece = unit_piece_rows(row_bytes, cap);
+    int rc = unit_ensure(h, stage, stage_bytes, (size_t)piece * (size_t)row_bytes);
+    for (int64_t r = 0; !rc && r < n_rows; r += piece) {
+        const int64_t k = std::min(piece, n_rows - r);
+        HIPCHK(h, hipMemcpyAsync(stage, (const char*)rows + r * row_bytes, (size_t)k * (size_t)row_bytes, hipMemcpyHostToDevice, h->stream));
+        if ((rc = launch(k, r))) break;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return rc;
+}
+
+// The lanes of a row store (the chains of sbe_diag, the runs of sbe_align): rows held per lane and the capacity of each.
+// No lane: the store has no shape yet.  `noun` names a lane in the messages, `reset`: the call that shapes the store.
+struct unit_lanes {
+    std::vector<int64_t> rows;
+    int64_t cap = 0;
+    int count() const { return (int)rows.size(); }
+
+    template <class H>
+    int check_shaped(H* h, const char* reset) const {
+        return rows.empty() ? fail(h, SBE_ERR_STATE, "the store has no shape yet (%s)", reset) : SBE_OK;
+    }
+    // <prefix>_rows
+    template <class H>
+    int get(H* h, const char* noun, int lane, int64_t* n_rows_out) const {
+        if (!n_rows_out) return fail(h, SBE_ERR_ARG, "null pointer argument: n_rows_out");
+        if (lane < 0 || lane >= count()) return fail(h, SBE_ERR_ARG, "%s %d out of range [0,%d)", noun, lane, count());
+        *n_rows_out = rows[(size_t)lane];
+        return SBE_OK;
+    }
+    // the argument checks of <prefix>_append_rows
+    template <class H>
+    int check_append(H* h, const char* noun, const char* reset, int lane, const void* src, int64_t n_rows) const {
+        if (const int rc = check_shaped(h, reset)) return rc;
+        if (lane < 0 || lane >= count()) return fail(h, SBE_ERR_ARG, "%s %d out of range [0,%d)", noun, lane, count());
+        if (n_rows < 0) return fail(h, SBE_ERR_ARG, "n_rows=%lld is negative", (long long)n_rows);
+        if (n_rows > 0 && !src) return fail(h, SBE_ERR_ARG, "null pointer argument: rows");
+        if (rows[(size_t)lane] + n_rows > cap)
+            return fail(h, SBE_ERR_ARG, "store overflow: %s %d holds %lld rows, %lld more exceed the capacity of %lld rows", noun, lane,
+                        (long long)rows[(size_t)lane], (long long)n_rows, (long long)cap);
+        return SBE_OK;
+    }
+};
+
+// ---- a compute call: the launches between the handle's two events, the copies back, then the wait -----------------------
+template <class H, class Fn>
+int unit_timed(H* h, Fn launches) {
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    if (const int rc = launches()) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    return SBE_OK;
+}
+
+// outs[q] <- d[q * n .. (q + 1) * n), on the handle's stream
+template <class H, class T>
+int unit_copy_back(H* h, const T* d, size_t n, std::initializer_list<T*> outs) {
+    for (T* out : outs) {
+        HIPCHK(h, hipMemcpyAsync(out, d, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+        d += n;
+    }
+    return SBE_OK;
+}
+
+// the wait for the stream (the copies back have arrived), then last_kernel_ms from the events
+template <class H>
+int unit_sync_timed(H* h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev[0], h->ev[1]));
+    return SBE_OK;
 }
 
 }  // namespace

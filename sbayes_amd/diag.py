@@ -32,7 +32,8 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _fast, _handle
+from . import _handle
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_DIAG_ABI_VERSION of include/sbe_diag.h
 MAX_CHAINS = 64                          # SBE_DIAG_MAX_CHAINS
@@ -42,15 +43,11 @@ MAX_COLUMNS = 2 ** 31 - 1                # the int32 of the ABI
 FLAG_CONSTANT, FLAG_NONFINITE, FLAG_TRUNCATED = 1, 2, 4
 PATHS = {0: "lds", 1: "global"}          # SBE_DIAG_PATH_*
 
-c_handle_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_diag.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    "sbe_diag_abi_version": (ct.c_int, []),
-    "sbe_diag_last_error": (ct.c_char_p, [c_handle_p]),
+    **_handle.unit_prototypes("sbe_diag"),
     "sbe_diag_lds_max_draws": (ct.c_int64, []),
     "sbe_diag_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_diag_destroy": (ct.c_int, [c_handle_p]),
     "sbe_diag_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int64, ct.c_int64]),
     "sbe_diag_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
     "sbe_diag_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
@@ -59,10 +56,7 @@ PROTOTYPES = {
                                     ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p]),
     "sbe_diag_last_shape": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int),
                                        ct.POINTER(ct.c_int64)]),
-    "sbe_diag_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 INDEX_COLUMNS = ("Sample", "sample_id")  # columns of a stats file that count samples or name the run: no parameters
 
@@ -209,12 +203,8 @@ class DiagHandle(_handle.UnitHandle):
     _prefix, _noun = "sbe_diag", "a diagnostics handle"
 
     def __init__(self, device=None):
-        if device is None:
-            from .registry import default_device
-            device = default_device()
-        self.device = int(device)
         self.n_chains = self.n_columns = self.capacity = 0
-        self._create(load, self.device)
+        self._create_on(load, device)
 
     def reset(self, n_chains, n_columns, capacity):
         """Shape the store: n_chains empty chains of up to `capacity` rows of n_columns values."""

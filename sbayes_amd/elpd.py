@@ -26,32 +26,26 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _fast, _handle
+from . import _handle
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_ELPD_ABI_VERSION of include/sbe_elpd.h
 MAX_SAMPLES = 1 << 20                    # SBE_ELPD_MAX_SAMPLES
 
-c_store_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_elpd.h one to one (the engine's own table, _lib.PROTOTYPES, covers
 # the three engine headers and is not extended)
 PROTOTYPES = {
-    "sbe_elpd_abi_version": (ct.c_int, []),
-    "sbe_elpd_last_error": (ct.c_char_p, [c_store_p]),
+    **_handle.unit_prototypes("sbe_elpd"),
     "sbe_elpd_lds_max_samples": (ct.c_int64, []),
-    "sbe_elpd_create": (ct.c_int, [ct.POINTER(c_store_p), ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_elpd_destroy": (ct.c_int, [c_store_p]),
-    "sbe_elpd_n_rows": (ct.c_int, [c_store_p, ct.POINTER(ct.c_int64)]),
-    "sbe_elpd_reset": (ct.c_int, [c_store_p]),
-    "sbe_elpd_last_kernel_ms": (ct.c_int, [c_store_p, ct.POINTER(ct.c_float)]),
-    "sbe_elpd_append_rows": (ct.c_int, [c_store_p, ct.c_void_p, ct.c_int64]),
-    "sbe_elpd_append_engine": (ct.c_int, [c_store_p, ct.c_void_p, ct.c_int]),
-    "sbe_elpd_get_rows": (ct.c_int, [c_store_p, ct.c_int64, ct.c_int64, ct.c_void_p]),
-    "sbe_elpd_compute": (ct.c_int, [c_store_p, ct.c_int64, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p,
+    "sbe_elpd_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int, ct.c_int64, ct.c_int64]),
+    "sbe_elpd_n_rows": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int64)]),
+    "sbe_elpd_reset": (ct.c_int, [c_handle_p]),
+    "sbe_elpd_append_rows": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64]),
+    "sbe_elpd_append_engine": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int]),
+    "sbe_elpd_get_rows": (ct.c_int, [c_handle_p, ct.c_int64, ct.c_int64, ct.c_void_p]),
+    "sbe_elpd_compute": (ct.c_int, [c_handle_p, ct.c_int64, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                     ct.c_void_p, ct.POINTER(ct.c_int64)]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (engine.py: every array argument is c_void_p)
 
 
 def load():
@@ -100,8 +94,8 @@ class _Store(_handle.UnitHandle):
     _prefix, _noun = "sbe_elpd", "an ELPD likelihood store"
 
     def __init__(self, device, n_columns, capacity):
-        self.device, self.n_columns, self.capacity = int(device), int(n_columns), int(capacity)
-        self._create(load, self.device, self.n_columns, self.capacity)
+        self.n_columns, self.capacity = int(n_columns), int(capacity)
+        self._create_on(load, device, self.n_columns, self.capacity)
 
     @property
     def n_rows(self) -> int:

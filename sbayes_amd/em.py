@@ -23,7 +23,8 @@ import weakref
 
 import numpy as np
 
-from . import _fast, _handle, _proc
+from . import _handle, _proc
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_EM_ABI_VERSION of include/sbe_em.h
 MAX_STATES = 254                         # SBE_EM_MAX_STATES
@@ -33,21 +34,14 @@ MAX_FEATURES = 1 << 16                   # SBE_EM_MAX_FEATURES
 MAX_COST_BYTES = 8 << 30                 # SBE_EM_MAX_COST_BYTES
 LOG_EVERY = 5                            # the reference logs the discretized z after every 5th step (i_step % 5 == 0)
 
-c_em_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_em.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    "sbe_em_abi_version": (ct.c_int, []),
-    "sbe_em_last_error": (ct.c_char_p, [c_em_p]),
-    "sbe_em_create": (ct.c_int, [ct.POINTER(c_em_p), ct.c_int, ct.c_int64, ct.c_int64, ct.c_int64, ct.c_void_p, ct.c_void_p,
+    **_handle.unit_prototypes("sbe_em"),
+    "sbe_em_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int, ct.c_int64, ct.c_int64, ct.c_int64, ct.c_void_p, ct.c_void_p,
                                  ct.c_int64, ct.c_int64, ct.c_void_p]),
-    "sbe_em_destroy": (ct.c_int, [c_em_p]),
-    "sbe_em_set_geo_cost": (ct.c_int, [c_em_p, ct.c_void_p, ct.c_double]),
-    "sbe_em_run": (ct.c_int, [c_em_p, ct.c_void_p, ct.c_int64, ct.c_void_p, ct.c_void_p]),
-    "sbe_em_last_kernel_ms": (ct.c_int, [c_em_p, ct.POINTER(ct.c_float)]),
+    "sbe_em_set_geo_cost": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_double]),
+    "sbe_em_run": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64, ct.c_void_p, ct.c_void_p]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 
 def load():
@@ -83,17 +77,13 @@ class EmHandle(_handle.UnitHandle):
 
     def __init__(self, x, applicable, groups_available, n_clusters, device=None):
         x, applicable, groups_available = _check_data(x, applicable, groups_available, n_clusters)
-        if device is None:
-            from .registry import default_device
-            device = default_device()
-        self.device = int(device)
         self.n_objects, self.n_features = x.shape
         self.n_states = applicable.shape[1]
         self.n_groups, self.n_clusters = groups_available.shape[0], int(n_clusters)
         self.geo_key = None
         xa, aa, ga = x, applicable.view(np.uint8), groups_available.view(np.uint8)
-        self._create(load, self.device, self.n_objects, self.n_features, self.n_states, _ptr(xa), _ptr(aa), self.n_groups,
-                     self.n_clusters, _ptr(ga))
+        self._create_on(load, device, self.n_objects, self.n_features, self.n_states, _ptr(xa), _ptr(aa), self.n_groups,
+                        self.n_clusters, _ptr(ga))
 
     def set_geo_cost(self, cost, scale, key=None):
         """Cost-based geo prior on (cost float64 [N, N]) or off (cost None).  `key`: an identity under which the upload

@@ -39,7 +39,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _fast, _handle, _proc
+from . import _handle
+from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_GEO_ABI_VERSION of include/sbe_geo.h
 MAX_OBJECTS = 32768                      # SBE_GEO_MAX_OBJECTS
@@ -51,14 +52,10 @@ AGGREGATIONS = {"mean": 0, "sum": 1, "max": 2}
 PROBABILITY_FUNCTIONS = {"exponential": 0, "sigmoid": 1}
 HOST_BELOW_MEMBERS = 0                   # (module docstring)
 
-c_handle_p = ct.c_void_p
-
 # name -> (restype, argtypes); mirrors include/sbe_geo.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    "sbe_geo_abi_version": (ct.c_int, []),
-    "sbe_geo_last_error": (ct.c_char_p, [c_handle_p]),
+    **_handle.unit_prototypes("sbe_geo"),
     "sbe_geo_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_geo_destroy": (ct.c_int, [c_handle_p]),
     "sbe_geo_set_launch_masks": (ct.c_int, [c_handle_p, ct.c_int64]),
     "sbe_geo_set_cost": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64]),
     "sbe_geo_skeleton": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p,
@@ -69,10 +66,7 @@ PROTOTYPES = {
                                             ct.c_void_p]),
     "sbe_geo_log_expit": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int64, ct.c_void_p]),
     "sbe_geo_last_shape": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]),
-    "sbe_geo_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
 }
-
-_ptr = _fast.addr                        # buffer address as a plain int (every array argument is c_void_p)
 
 
 def load():
@@ -143,10 +137,9 @@ class GeoHandle(_handle.UnitHandle):
     _prefix, _noun = "sbe_geo", "a geo-prior handle"
 
     def __init__(self, device=0):
-        self.device = int(device)
         self.n_objects = 0
         self.cost_key = None
-        self._create(load, self.device)
+        self._create_on(load, device)
 
     def set_launch_masks(self, masks):
         """Masks per launch of the skeleton kernel (0: the default).  Results do not depend on it."""
@@ -219,26 +212,16 @@ class GeoHandle(_handle.UnitHandle):
         return launches.value, lds_masks.value
 
 
-_HANDLES: dict = {}          # device -> GeoHandle; per process, emptied in a fork()ed child
-
-
-@_proc.on_fork_clear
-def _forget_inherited():
-    _HANDLES.clear()
+_HANDLES = _handle.device_cache()          # device -> GeoHandle
 
 
 def release_all():
-    for h in list(_HANDLES.values()):
-        h.close()
-    _HANDLES.clear()
+    _handle.release_cached(_HANDLES)
 
 
 def handle_for(device=0) -> GeoHandle:
     """The process's handle on `device`, created on first use."""
-    h = _HANDLES.get(int(device))
-    if h is None or not h._h:
-        h = _HANDLES[int(device)] = GeoHandle(device)
-    return h
+    return _handle.cached_handle(_HANDLES, GeoHandle, device)
 
 
 # ---- plain functions over the handle of a device (its cost matrix set by handle_for(device).set_cost) ------------------

@@ -4,7 +4,6 @@ import ast
 import ctypes as ct
 import inspect
 import pickle
-import re
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -12,19 +11,15 @@ import numpy as np
 import pytest
 
 from sbayes_amd import _lib, align
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_align.h").read_text()
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = align.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 12
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_align.h but not exported"
@@ -34,14 +29,12 @@ def test_every_symbol_of_the_header_is_exported_and_bound():
 
 
 def test_limits_agree_with_the_header():
-    def macro(name):
-        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
-    assert macro("SBE_ALIGN_MAX_CLUSTERS") == str(align.MAX_CLUSTERS) == "8"
-    assert macro("SBE_ALIGN_MAX_RUNS") == str(align.MAX_RUNS) == "64"
-    assert macro("SBE_ALIGN_MAX_ROWS") == "(1 << 20)" and align.MAX_ROWS == 1 << 20
-    assert macro("SBE_ALIGN_MAX_SEED_ROWS") == str(align.MAX_SEED_ROWS) == "1024"
-    assert macro("SBE_ALIGN_LDS_BYTES") == "(160 * 1024)" and align.LDS_BYTES == 160 * 1024
-    assert macro("SBE_ALIGN_STATIC_LDS") == str(align.STATIC_LDS)
+    assert macro(HEADER, "SBE_ALIGN_MAX_CLUSTERS") == str(align.MAX_CLUSTERS) == "8"
+    assert macro(HEADER, "SBE_ALIGN_MAX_RUNS") == str(align.MAX_RUNS) == "64"
+    assert macro(HEADER, "SBE_ALIGN_MAX_ROWS") == "(1 << 20)" and align.MAX_ROWS == 1 << 20
+    assert macro(HEADER, "SBE_ALIGN_MAX_SEED_ROWS") == str(align.MAX_SEED_ROWS) == "1024"
+    assert macro(HEADER, "SBE_ALIGN_LDS_BYTES") == "(160 * 1024)" and align.LDS_BYTES == 160 * 1024
+    assert macro(HEADER, "SBE_ALIGN_STATIC_LDS") == str(align.STATIC_LDS)
     assert max(align.MAX_SEED_ROWS, 1) * align.MAX_ROWS + align.MAX_SEED_ROWS < 2 ** 31      # the int32 running sums
     lib = align.load()
     for k in range(1, 9):

@@ -3,26 +3,21 @@ bound by the module's own prototype table, and bad arguments are refused before 
 import ast
 import ctypes as ct
 import inspect
-import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from sbayes_amd import _lib, assoc
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_assoc.h").read_text()
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = assoc.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 9
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_assoc.h but not exported"
@@ -32,13 +27,11 @@ def test_every_symbol_of_the_header_is_exported_and_bound():
 
 
 def test_limits_agree_with_the_header():
-    def macro(name):
-        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
-    assert macro("SBE_ASSOC_NA") == str(assoc.NA)
-    assert macro("SBE_ASSOC_MAX_OBJECTS") == "(1 << 24)" and assoc.MAX_OBJECTS == 1 << 24
-    assert macro("SBE_ASSOC_MAX_STATES") == str(assoc.MAX_STATES)
-    assert macro("SBE_ASSOC_MAX_FEATURES") == str(assoc.MAX_FEATURES)
-    assert macro("SBE_ASSOC_MAX_CODES") == "((int64_t)1 << 31)" and assoc.MAX_CODES == 1 << 31
+    assert macro(HEADER, "SBE_ASSOC_NA") == str(assoc.NA)
+    assert macro(HEADER, "SBE_ASSOC_MAX_OBJECTS") == "(1 << 24)" and assoc.MAX_OBJECTS == 1 << 24
+    assert macro(HEADER, "SBE_ASSOC_MAX_STATES") == str(assoc.MAX_STATES)
+    assert macro(HEADER, "SBE_ASSOC_MAX_FEATURES") == str(assoc.MAX_FEATURES)
+    assert macro(HEADER, "SBE_ASSOC_MAX_CODES") == "((int64_t)1 << 31)" and assoc.MAX_CODES == 1 << 31
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():

@@ -4,7 +4,6 @@ import ast
 import ctypes as ct
 import inspect
 import pickle
-import re
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -12,19 +11,15 @@ import numpy as np
 import pytest
 
 from sbayes_amd import _lib, diag
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_diag.h").read_text()
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = diag.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 12
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_diag.h but not exported"
@@ -34,15 +29,13 @@ def test_every_symbol_of_the_header_is_exported_and_bound():
 
 
 def test_limits_and_codes_agree_with_the_header():
-    def macro(name):
-        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
-    assert macro("SBE_DIAG_MAX_CHAINS") == str(diag.MAX_CHAINS) == "64"
-    assert macro("SBE_DIAG_MIN_DRAWS") == str(diag.MIN_DRAWS) == "4"
-    assert macro("SBE_DIAG_MAX_DRAWS") == "(1 << 20)" and diag.MAX_DRAWS == 1 << 20
+    assert macro(HEADER, "SBE_DIAG_MAX_CHAINS") == str(diag.MAX_CHAINS) == "64"
+    assert macro(HEADER, "SBE_DIAG_MIN_DRAWS") == str(diag.MIN_DRAWS) == "4"
+    assert macro(HEADER, "SBE_DIAG_MAX_DRAWS") == "(1 << 20)" and diag.MAX_DRAWS == 1 << 20
     assert diag.MAX_COLUMNS == 2 ** 31 - 1
-    assert (macro("SBE_DIAG_FLAG_CONSTANT"), macro("SBE_DIAG_FLAG_NONFINITE"), macro("SBE_DIAG_FLAG_TRUNCATED")) == \
+    assert (macro(HEADER, "SBE_DIAG_FLAG_CONSTANT"), macro(HEADER, "SBE_DIAG_FLAG_NONFINITE"), macro(HEADER, "SBE_DIAG_FLAG_TRUNCATED")) == \
         (str(diag.FLAG_CONSTANT), str(diag.FLAG_NONFINITE), str(diag.FLAG_TRUNCATED))
-    assert {int(macro("SBE_DIAG_PATH_LDS")): "lds", int(macro("SBE_DIAG_PATH_GLOBAL")): "global"} == diag.PATHS
+    assert {int(macro(HEADER, "SBE_DIAG_PATH_LDS")): "lds", int(macro(HEADER, "SBE_DIAG_PATH_GLOBAL")): "global"} == diag.PATHS
     # the staged column, the rho_t entries kept in LDS and the kernel's static LDS fit the 160 KiB of a CU
     limit = diag.lds_max_draws()
     assert 8192 <= limit and (limit + 2048) * 8 + 4096 <= 160 * 1024 < (limit + 1 + 2048) * 8 + 4096

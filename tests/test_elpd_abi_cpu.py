@@ -3,25 +3,21 @@ module's own prototype table, and bad arguments are refused before the device is
 import ast
 import ctypes as ct
 import inspect
-import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from sbayes_amd import _lib, elpd
+from tests._abi_header import declared
 
 REPO = Path(__file__).resolve().parent.parent
-
-
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", (REPO / "include" / "sbe_elpd.h").read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
+HEADER = (REPO / "include" / "sbe_elpd.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = elpd.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 12
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_elpd.h but not exported"

@@ -3,30 +3,25 @@ by the module's own prototype table, and bad shapes, limits and data are refused
 import ast
 import ctypes as ct
 import inspect
-import re
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from sbayes_amd import _lib, em
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
-
-
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", (REPO / "include" / "sbe_em.h").read_text(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
+HEADER = (REPO / "include" / "sbe_em.h").read_text()
 
 
 def _header_define(name):
-    m = re.search(rf"#define {name} (.+?)\s*(/\*|$)", (REPO / "include" / "sbe_em.h").read_text(), flags=re.M)
-    return eval(m.group(1).replace("(int64_t)", ""))
+    return eval(macro(HEADER, name).replace("(int64_t)", ""))
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = em.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 7
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_em.h but not exported"

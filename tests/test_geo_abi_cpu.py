@@ -4,7 +4,6 @@ import ast
 import ctypes as ct
 import inspect
 import pickle
-import re
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -12,19 +11,15 @@ import numpy as np
 import pytest
 
 from sbayes_amd import _lib, geo
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_geo.h").read_text()
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = geo.load()
-    names = _declared()
+    names = declared(HEADER)
     assert len(names) == 12
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_geo.h but not exported"
@@ -34,17 +29,15 @@ def test_every_symbol_of_the_header_is_exported_and_bound():
 
 
 def test_limits_and_codes_agree_with_the_header():
-    def macro(name):
-        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
-    assert macro("SBE_GEO_MAX_OBJECTS") == str(geo.MAX_OBJECTS)
-    assert macro("SBE_GEO_MAX_MASKS") == "(1 << 20)" and geo.MAX_MASKS == 1 << 20
-    assert macro("SBE_GEO_MAX_LAUNCH_MASKS") == "(1 << 16)" and geo.MAX_LAUNCH_MASKS == 1 << 16
-    assert macro("SBE_GEO_LDS_MEMBERS") == str(geo.LDS_MEMBERS)
+    assert macro(HEADER, "SBE_GEO_MAX_OBJECTS") == str(geo.MAX_OBJECTS)
+    assert macro(HEADER, "SBE_GEO_MAX_MASKS") == "(1 << 20)" and geo.MAX_MASKS == 1 << 20
+    assert macro(HEADER, "SBE_GEO_MAX_LAUNCH_MASKS") == "(1 << 16)" and geo.MAX_LAUNCH_MASKS == 1 << 16
+    assert macro(HEADER, "SBE_GEO_LDS_MEMBERS") == str(geo.LDS_MEMBERS)
     assert geo.MAX_OBJECTS ** 2 * 8 == 8 << 30             # the cost matrix at the limit: 8 GiB, as SBE_EM_MAX_COST_BYTES
     assert (geo.LDS_MEMBERS ** 2 + geo.LDS_MEMBERS) * 8 + 8192 <= 160 * 1024       # the staged sub-matrix fits a workgroup's LDS
     for table, prefix in ((geo.SKELETONS, "SBE_GEO_SKELETON_"), (geo.AGGREGATIONS, "SBE_GEO_AGG_"), (geo.PROBABILITY_FUNCTIONS, "SBE_GEO_PROB_")):
         for name, code in table.items():
-            assert macro(prefix + {"complete_graph": "COMPLETE"}.get(name, name.upper())) == str(code)
+            assert macro(HEADER, prefix + {"complete_graph": "COMPLETE"}.get(name, name.upper())) == str(code)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():

@@ -152,6 +152,32 @@ def test_bits_do_not_depend_on_appends_capacity_position_or_company():
         assert np.array_equal(got[1], base) and np.array_equal(got[0], orc.within(other, seed))
 
 
+def test_long_rows_go_through_the_staging_buffer_in_pieces_at_any_offset():
+    """At K = 2 and the most objects the store takes a sample is close to 40 KB, so the 64 MiB staging buffer holds about
+    1 600 of them: 2 pieces + 3 samples appended in one call go in three pieces, and batches of piece - 1, 1, piece + 1, 4
+    straddle the pieces at offsets that are not 0 (the run ends 2 samples into the last batch, which holds what is left).
+    The counts as stored are the column sums of the host array, and both stores give the same permutations."""
+    k, n = 2, align.max_objects(2)
+    piece = (64 << 20) // (k * n)
+    s = 2 * piece + 3
+    c = np.random.default_rng(3600).integers(0, 2, (s, k, n), dtype=np.uint8)
+    perms = []
+    for batches in ((s,), (piece - 1, 1, piece + 1, 4)):
+        h = align.AlignHandle()
+        try:
+            h.reset(1, k, n, s)
+            at = 0
+            for size in batches:
+                h.append(0, c[at:at + size])
+                at += size
+            assert at >= s and h.rows(0) == s
+            assert np.array_equal(h.counts(aligned=False)[0], c.sum(axis=0, dtype=np.int32))
+            perms.append(h.within()[0])
+        finally:
+            h.close()
+    assert perms[0].shape == (s, k) and np.array_equal(perms[0], perms[1])
+
+
 def test_counts_aligned_and_as_logged_with_and_without_burn_in():
     lengths = [48, 20, 33]
     runs = [cases.planted(4, 65, s, seed=3800 + r)[0] for r, s in enumerate(lengths)]

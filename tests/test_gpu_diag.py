@@ -4,6 +4,7 @@ launch chunking, the store's capacity, the way rows were appended and the column
 LDS limit; the recorded two-run reference output."""
 import math
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -129,6 +130,36 @@ def test_rows_appended_in_pieces_to_two_chains_of_unequal_length(monkeypatch):
         assert s["n_columns"] == 5 and s["ess_min"] == res.ess.min() and s["n_ess_below"] == int((res.ess < 200).sum())
     finally:
         h.close()
+
+
+def test_wide_rows_go_through_the_staging_buffer_in_pieces_at_any_offset():
+    """A row of P = 200 003 float64 columns leaves the 64 MiB staging buffer 41 rows: 100 rows appended in one call go in
+    pieces of 41 + 41 + 18, and batches of 1, 40, 41, 18 straddle the pieces at row offsets that are not 0.  Both stores
+    give the same bits, and those meet the checker on 64 columns spread over the width, the last one included (P is no
+    multiple of 32: the transpose's edge tile)."""
+    p, s = 200_003, 100
+    assert (64 << 20) // (8 * p) == 41
+    x = orc.ar1(np.random.default_rng(33), 0.6, 1, s, p)[0]
+    results = []
+    for batches in ((s,), (1, 40, 41, 18)):
+        h = diag.DiagHandle()
+        try:
+            h.reset(1, p, s)
+            lo = 0
+            for n in batches:
+                h.append(0, x[lo:lo + n])
+                lo += n
+            assert h.rows(0) == s
+            results.append(h.compute())
+        finally:
+            h.close()
+    one, many = results
+    assert _same_bits(one, many)
+    cols = np.linspace(0, p - 1, 64).astype(np.int64)
+    want = orc.diagnose([x[:, cols]])
+    assert cols[-1] == p - 1 and want["margin"].min() >= cases.MIN_MARGIN
+    part = SimpleNamespace(n_chains=one.n_chains, n_draws=one.n_draws, **{k: getattr(one, k)[cols] for k in OUTPUTS})
+    _check(part, want, "wide rows")
 
 
 def test_bad_calls_on_a_live_handle_are_refused_with_the_limit_named():

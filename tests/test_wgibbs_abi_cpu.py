@@ -9,19 +9,15 @@ import numpy as np
 import pytest
 
 from sbayes_amd import _lib, wgibbs
+from tests._abi_header import declared, macro
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_wgibbs.h").read_text()
 
 
-def _declared():
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    return sorted(set(re.findall(r"\b(sbe_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_every_symbol_of_the_header_is_exported_and_bound():
     lib = wgibbs.load()
-    names = _declared()
+    names = declared(HEADER)
     assert names == ["sbe_wgibbs_abi_version", "sbe_wgibbs_pair_counts", "sbe_wgibbs_step"]
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/sbe_wgibbs.h but not exported"
@@ -34,10 +30,8 @@ def test_every_symbol_of_the_header_is_exported_and_bound():
 
 
 def test_constants_agree_with_the_header():
-    def macro(name):
-        return re.search(rf"#define {name}\s+(.+?)\s*(?:/\*|$)", HEADER, flags=re.M).group(1)
-    assert macro("SBE_WGIBBS_ABI_VERSION") == str(wgibbs.ABI_VERSION)
-    assert macro("SBE_WGIBBS_FEATURE_TILE") == str(wgibbs.FEATURE_TILE)
+    assert macro(HEADER, "SBE_WGIBBS_ABI_VERSION") == str(wgibbs.ABI_VERSION)
+    assert macro(HEADER, "SBE_WGIBBS_FEATURE_TILE") == str(wgibbs.FEATURE_TILE)
     # the step kernel's tile at the engine's limits (64 patterns, 8 components): the float64 table of log differences and
     # the lane sums fit a workgroup's LDS
     assert wgibbs.FEATURE_TILE * 64 * 8 * 8 + 64 * wgibbs.FEATURE_TILE * 8 <= 160 * 1024
