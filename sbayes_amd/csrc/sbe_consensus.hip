@@ -1,0 +1,466 @@
+// sbe_consensus.hip -- posterior similarity of objects and the consensus clustering on the device (include/sbe_consensus.h):
+// the store of R runs of cluster samples in two forms, its pack kernels, the similarity kernel on the matrix pipe, the
+// score kernel and the comparison of two matrices.  The contract is tests/_consensus_oracle.py; DESIGN.md section 19 has
+// the layout, the structure of the kernels and the limits.
+//
+// With Z the 0/1 matrix of all cluster rows of the selected runs, [T K][N], the similarity counts are Z^T Z.
+// k_consensus_similarity computes one 32 x 32 tile of it per wave, for the tile pairs I <= J, as sbe_assoc.hip computes
+// its contingency tables: contraction in steps of 64 elements with v_mfma_f32_32x32x64_f8f6f4 and FP4 operands (0 = 0x0
+// and 1 = 0x2 in e2m1 are exact, and so are the counts in the f32 accumulator while T K <= 2^24).  Unlike there the
+// operands are not built in registers: the pack kernel has written them, so the loop is loads and MFMAs only.
+//   image: [N_pad objects][n_runs segments][seg_bytes]; element e = s K + k of a run is nibble e & 7 of dword e >> 3 of
+//   the run's segment; a segment is zero behind the run's last element and padded to whole rounds of 256 elements.
+//   A lane owns one object (lane & 31) and one half of a step (lane >> 5): 32 elements, one 16-byte load.  Both MFMA
+//   operands are read from this one image with the same (lane half, nibble) placement, so the instruction's internal
+//   order of the 64 products does not matter: the same element of the two objects always meets.
+// k_consensus_scores takes one (sample, cluster) row per workgroup from the bit rows, k_consensus_compare one matrix row.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "sbe_unit.hip.h"
+#include "../../include/sbe_consensus.h"
+
+namespace {
+
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+constexpr int kMaxK = SBE_CONSENSUS_MAX_CLUSTERS;
+constexpr int kMaxRuns = SBE_CONSENSUS_MAX_RUNS;
+constexpr int kTile = 32;                            // objects per tile edge
+constexpr int kStep = 64;                            // contraction elements per MFMA
+constexpr int kRound = 4;                            // steps per round: a round's loads are issued together
+constexpr int kRoundElems = kRound * kStep;          // = SBE_CONSENSUS_ROUND
+constexpr int kRoundBytes = kRoundElems / 2;         // of one object's image
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+// contraction steps per launch of the similarity kernel: a launch of one full wave per SIMD then stays in the milliseconds
+// at any T K (a tile pair at T K = 2^24 takes 2^18 steps: 16 tile pairs per launch)
+constexpr int64_t kStepsPerLaunch = (int64_t)1 << 22;
+constexpr int64_t kMaxLaunchTiles = (int64_t)1 << 16;
+// the score kernel's launches are bounded the same way: a row gathers at most N^2 entries, (N / 64)^2 units of 64 x 64, and
+// a launch holds at most 2^26 units (1024 rows at N = 16384, every row at N <= 512)
+constexpr int64_t kScoreUnitsPerLaunch = (int64_t)1 << 26;
+static_assert(kRoundElems == SBE_CONSENSUS_ROUND, "the header states the round length");
+
+// ---- pack 1: host bytes [n][K][N] (staging) -> the operand image of one run's segment ----------------------------------
+// A thread owns one (object, dword): the elements [8 d, 8 d + 8) of the segment that this piece holds.  A piece may start
+// and end inside a dword; that dword then already holds the elements of the piece before (or zeros), which are kept.
+// blockIdx.x: four dwords from d_first on, blockIdx.y: 64 objects.
+__global__ __launch_bounds__(kBlock) void k_consensus_pack(const uint8_t* rows, int64_t e0, int64_t n_elems, int N, uint8_t* seg, int64_t stride,
+                                                          int64_t d_first) {
+    const int n = blockIdx.y * 64 + (threadIdx.x & 63);
+    const int64_t d = d_first + (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+    const int64_t lo = 8 * d > e0 ? 8 * d : e0, hi = 8 * d + 8 < e0 + n_elems ? 8 * d + 8 : e0 + n_elems;
+    if (n >= N || lo >= hi) return;
+    uint32_t bits = 0;
+    for (int64_t e = lo; e < hi; ++e)
+        if (rows[(e - e0) * N + n]) bits |= 2u << (4 * (int)(e & 7));
+    uint32_t* out = reinterpret_cast<uint32_t*>(seg + (int64_t)n * stride) + d;
+    if (hi - lo == 8) *out = bits;
+    else *out |= bits;
+}
+
+// ---- pack 2: the same bytes -> bit words [n][K][W]; a wave takes 64 objects of one (row, cluster) ------------------------
+__global__ __launch_bounds__(kBlock) void k_consensus_pack_bits(const uint8_t* rows, int64_t n_lines, int N, int W, uint32_t* out, int64_t line0) {
+    const int64_t line = line0 + blockIdx.x;                   // row * K + cluster, within this piece
+    const int n = blockIdx.y * kBlock + threadIdx.x;
+    const bool bit = line < n_lines && n < N && rows[line * N + n] != 0;
+    const unsigned long long both = __ballot(bit);
+    const int w = n >> 5;
+    if ((threadIdx.x & 63) == 0 && line < n_lines) {
+        if (w < W) out[line * W + w] = (uint32_t)both;
+        if (w + 1 < W) out[line * W + w + 1] = (uint32_t)(both >> 32);
+    }
+}
+
+// ---- the similarity kernel ------------------------------------------------------------------------------------------
+struct SimArgs {
+    const uint8_t* img;       // [N_pad][stride]
+    int64_t stride;           // bytes of one object's image
+    int32_t* counts;          // [N][N]
+    int N;
+    int n_seg;                // selected runs that hold rows
+    int64_t t0, t_end;        // tile pairs [t0, t_end) of the enumeration t = J (J + 1) / 2 + I, I <= J
+    int64_t seg_off[kMaxRuns];   // byte offset of the segment within an object's image
+    int32_t seg_rounds[kMaxRuns];
+};
+
+// one round of a lane: four steps of 32 elements each
+struct LaneRound {
+    uint4 q[kRound];
+};
+
+__device__ inline LaneRound load_round(const uint8_t* p) {
+    LaneRound c;
+#pragma unroll
+    for (int u = 0; u < kRound; ++u) c.q[u] = *reinterpret_cast<const uint4*>(p + u * (kStep / 2));
+    return c;
+}
+
+__device__ inline v8i fp4_operand(const uint4 q) {
+    v8i v = {};
+    v[0] = (int)q.x;
+    v[1] = (int)q.y;
+    v[2] = (int)q.z;
+    v[3] = (int)q.w;
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_consensus_similarity(const SimArgs g) {
+    const int64_t t = g.t0 + blockIdx.x;
+    if (t >= g.t_end) return;
+    int64_t J = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (J * (J + 1) / 2 > t) --J;
+    while ((J + 1) * (J + 2) / 2 <= t) ++J;
+    const int64_t I = t - J * (J + 1) / 2;
+    const int lane = threadIdx.x, half = lane >> 5;
+    // (the image has whole tiles of objects: the rows behind N are zero)
+    const uint8_t* pa = g.img + (I * kTile + (lane & 31)) * g.stride + (kStep / 4) * half;
+    const uint8_t* pb = g.img + (J * kTile + (lane & 31)) * g.stride + (kStep / 4) * half;
+    v16f acc = {};
+    for (int q = 0; q < g.n_seg; ++q) {
+        const uint8_t* a = pa + g.seg_off[q];
+        const uint8_t* b = pb + g.seg_off[q];
+        for (int r = 0; r < g.seg_rounds[q]; ++r, a += kRoundBytes, b += kRoundBytes) {
+            const LaneRound ca = load_round(a), cb = load_round(b);
+#pragma unroll
+            for (int u = 0; u < kRound; ++u)
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_operand(ca.q[u]), fp4_operand(cb.q[u]), acc, 4, 4, 0, 0, 0, 0);
+        }
+    }
+    // register reg of a lane is row (reg & 3) + 8 (reg >> 2) + 4 half (an object of tile I), column lane & 31 (of tile J)
+    const int64_t j = J * kTile + (lane & 31);
+    if (j >= g.N) return;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int64_t i = I * kTile + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        if (i >= g.N) continue;
+        const int32_t c = (int32_t)acc[reg];
+        g.counts[i * g.N + j] = c;
+        if (I != J) g.counts[j * g.N + i] = c;               // (a diagonal tile holds both triangles itself)
+    }
+}
+
+// ---- the score kernel: one workgroup per (sample, cluster) row ---------------------------------------------------------
+// score of the row = sum_{i,j in row} (T - 2 C[i][j]) = T m^2 - 2 sum_{i,j in row} C[i][j], m the row's size.  The member
+// list goes to LDS (its order does not matter: the sums are integers); the waves take members i, the lanes members j.
+__global__ __launch_bounds__(kBlock) void k_consensus_scores(const uint32_t* bits, int64_t line0, int K, int N, int W, const int32_t* counts,
+                                                            long long T, unsigned long long* score) {
+    extern __shared__ uint16_t members[];                      // [32 W]
+    __shared__ long long red[kWaves];
+    __shared__ int n_members;
+    const int64_t line = line0 + blockIdx.x;                   // sample * K + cluster, within the run
+    const uint32_t* row = bits + line * W;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) n_members = 0;
+    __syncthreads();
+    for (int w = tid; w < W; w += kBlock) {
+        uint32_t word = row[w];
+        if (!word) continue;
+        int at = atomicAdd(&n_members, __popc(word));
+        while (word) {
+            members[at++] = (uint16_t)(32 * w + __ffs(word) - 1);
+            word &= word - 1;
+        }
+    }
+    __syncthreads();
+    const int m = n_members;
+    if (m == 0) return;                                        // (an empty cluster adds 0; uniform for the block)
+    long long sum = 0;
+    for (int a = wave; a < m; a += kWaves) {
+        const int32_t* crow = counts + (int64_t)members[a] * N;
+        for (int b = lane; b < m; b += 64) sum += crow[members[b]];
+    }
+    sum = unit_block_reduce<kWaves>(sum, red, unit_sum());
+    if (tid == 0) atomicAdd(&score[line / K], (unsigned long long)(T * m * m - 2 * sum));
+}
+
+// ---- the comparison: one workgroup per row ------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_consensus_compare(const int32_t* ca, long long Ta, const int32_t* cb, long long Tb, int N,
+                                                             long long* row_max, long long* row_sum) {
+    __shared__ long long red[kWaves];
+    const int i = blockIdx.x;
+    long long mx = 0, sum = 0;
+    for (int j = threadIdx.x; j < N; j += kBlock) {
+        const long long v = ca[(int64_t)i * N + j] * Tb - cb[(int64_t)i * N + j] * Ta;
+        const long long d = v < 0 ? -v : v;
+        mx = d > mx ? d : mx;
+        sum += d;
+    }
+    mx = unit_block_reduce<kWaves>(mx, red, unit_max());
+    sum = unit_block_reduce<kWaves>(sum, red, unit_sum());
+    if (threadIdx.x == 0) {
+        row_max[i] = mx;
+        row_sum[i] = sum;
+    }
+}
+
+struct Slot {
+    int32_t* d_counts = nullptr;        // [N][N]
+    size_t bytes = 0;
+    int64_t T = 0;
+    uint64_t version = 0;               // of the store when it was computed (0: empty)
+};
+
+}  // namespace
+
+struct sbe_consensus : sbe_unit_handle {       // (sbe_unit.hip.h; ev: around the kernels of the last similarity, scores or compare)
+    unit_lanes runs;                    // (empty: no shape yet)
+    int K = 0;
+    int64_t N = 0, W = 0, seg_bytes = 0, stride = 0;
+    uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
+    int64_t launch_tiles = 0;           // 0: the default
+    Slot slot[2];
+    uint8_t* d_img = nullptr;           // [32 W][n_runs][seg_bytes]
+    size_t img_bytes = 0;
+    uint32_t* d_bits = nullptr;         // [n_runs][cap][K][W]
+    size_t bits_bytes = 0;
+    void* d_stage = nullptr;            // host rows in flight
+    size_t stage_bytes = 0;
+    unsigned long long* d_score = nullptr;   // [cap]
+    size_t score_bytes = 0;
+    long long* d_cmp = nullptr;         // [2][N]
+    size_t cmp_bytes = 0;
+    std::vector<void*> buffers() const { return {slot[0].d_counts, slot[1].d_counts, d_img, d_bits, d_stage, d_score, d_cmp}; }
+};
+
+namespace {
+
+constexpr char kNullHandle[] = "null handle";
+constexpr char kLane[] = "run", kReset[] = "sbe_consensus_reset";
+
+int64_t segment_bytes(int K, int64_t cap) { return (cap * K + kRoundElems - 1) / kRoundElems * kRoundBytes; }
+
+bool shape_ok(int n_runs, int K, int64_t N, int64_t cap) {
+    return n_runs >= 1 && n_runs <= kMaxRuns && K >= 1 && K <= kMaxK && N >= 1 && N <= SBE_CONSENSUS_MAX_OBJECTS && cap >= 1 &&
+           cap <= SBE_CONSENSUS_MAX_ROWS;
+}
+
+int64_t store_bytes(int n_runs, int K, int64_t N, int64_t cap) {
+    const int64_t W = (N + 31) / 32;
+    return 32 * W * n_runs * segment_bytes(K, cap) + (int64_t)n_runs * cap * K * W * (int64_t)sizeof(uint32_t);
+}
+
+int check_slot_index(sbe_consensus* h, int slot) {
+    return slot == 0 || slot == 1 ? SBE_OK : fail(h, SBE_ERR_ARG, "slot=%d is neither 0 nor 1", slot);
+}
+
+// a slot a later call reads: computed, and on the store as it is now
+int check_slot_current(sbe_consensus* h, int slot) {
+    if (h->slot[slot].version == 0) return fail(h, SBE_ERR_STATE, "slot %d is empty (sbe_consensus_similarity comes first)", slot);
+    if (h->slot[slot].version != h->version)
+        return fail(h, SBE_ERR_STATE, "slot %d was computed before the store last changed (sbe_consensus_similarity again)", slot);
+    return SBE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbe_consensus_abi_version(void) { return SBE_CONSENSUS_ABI_VERSION; }
+
+const char* sbe_consensus_last_error(const sbe_consensus* h) { return unit_last_error(h); }
+
+int64_t sbe_consensus_image_bytes(int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows) {
+    return shape_ok(n_runs, n_clusters, n_objects, capacity_rows) ? store_bytes(n_runs, n_clusters, n_objects, capacity_rows) : 0;
+}
+
+int sbe_consensus_create(sbe_consensus** out, int device) { return unit_create_on_device(out, device, "sbe_consensus_create"); }
+
+int sbe_consensus_destroy(sbe_consensus* h) { return unit_destroy(h, kNullHandle); }
+
+int sbe_consensus_last_kernel_ms(const sbe_consensus* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
+
+int sbe_consensus_set_launch_tiles(sbe_consensus* h, int64_t tile_pairs) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (tile_pairs < 0 || tile_pairs > kMaxLaunchTiles)
+        return fail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
+    h->launch_tiles = tile_pairs;
+    return SBE_OK;
+}
+
+int sbe_consensus_reset(sbe_consensus* h, int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (n_runs < 1 || n_runs > kMaxRuns) return fail(h, SBE_ERR_ARG, "n_runs=%d out of range [1, %d]", n_runs, kMaxRuns);
+    if (n_clusters < 1 || n_clusters > kMaxK) return fail(h, SBE_ERR_ARG, "n_clusters=%d out of range [1, %d]", n_clusters, kMaxK);
+    if (n_objects < 1 || n_objects > SBE_CONSENSUS_MAX_OBJECTS)
+        return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (an int32 matrix [N][N] of at most 1 GiB)", (long long)n_objects,
+                    SBE_CONSENSUS_MAX_OBJECTS);
+    if (capacity_rows < 1 || capacity_rows > SBE_CONSENSUS_MAX_ROWS)
+        return fail(h, SBE_ERR_ARG, "capacity_rows=%lld out of range [1, %d]", (long long)capacity_rows, SBE_CONSENSUS_MAX_ROWS);
+    const int64_t bytes = store_bytes(n_runs, n_clusters, n_objects, capacity_rows);
+    if (bytes > SBE_CONSENSUS_MAX_IMAGE_BYTES)
+        return fail(h, SBE_ERR_ARG, "a store of %d runs x %lld rows x %d clusters x %lld objects takes %lld bytes on the device, the limit is %lld",
+                    n_runs, (long long)capacity_rows, n_clusters, (long long)n_objects, (long long)bytes, (long long)SBE_CONSENSUS_MAX_IMAGE_BYTES);
+    const int64_t W = (n_objects + 31) / 32, seg = segment_bytes(n_clusters, capacity_rows);
+    const size_t img = (size_t)(32 * W * n_runs * seg);
+    h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
+    h->slot[0].version = h->slot[1].version = 0;
+    ++h->version;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = unit_ensure(h, h->d_img, h->img_bytes, img);
+    if (!rc) rc = unit_ensure(h, h->d_bits, h->bits_bytes, (size_t)bytes - img);
+    if (!rc) rc = unit_ensure(h, h->d_score, h->score_bytes, (size_t)capacity_rows * sizeof(unsigned long long));
+    if (!rc) rc = unit_ensure(h, h->d_cmp, h->cmp_bytes, (size_t)2 * (size_t)n_objects * sizeof(long long));
+    if (rc) return rc;
+    // the image is zero wherever no element was appended: the padding of every segment and the objects behind N
+    HIPCHK(h, hipMemsetAsync(h->d_img, 0, img, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->K = n_clusters;
+    h->N = n_objects;
+    h->W = W;
+    h->seg_bytes = seg;
+    h->stride = n_runs * seg;
+    h->runs.cap = capacity_rows;
+    h->runs.rows.assign((size_t)n_runs, 0);
+    return SBE_OK;
+}
+
+int sbe_consensus_rows(const sbe_consensus* h, int run, int64_t* n_rows_out) {
+    CHECK_HANDLE(h, kNullHandle);
+    return h->runs.get(h, kLane, run, n_rows_out);
+}
+
+int sbe_consensus_append_rows(sbe_consensus* h, int run, const uint8_t* rows, int64_t n_rows) {
+    CHECK_HANDLE(h, kNullHandle);
+    int rc = h->runs.check_append(h, kLane, kReset, run, rows, n_rows);
+    if (rc || n_rows == 0) return rc;
+    const int64_t row_bytes = (int64_t)h->K * h->N;
+    for (int64_t q0 = 0; q0 < n_rows * row_bytes; q0 += 4096) {      // (blocks: the common case is one OR per byte)
+        const int64_t q1 = std::min(n_rows * row_bytes, q0 + 4096);
+        uint8_t any = 0;
+        for (int64_t q = q0; q < q1; ++q) any |= rows[q];
+        if (any <= 1) continue;
+        int64_t q = q0;
+        while (rows[q] <= 1) ++q;
+        return fail(h, SBE_ERR_DATA, "rows[%lld][%lld][%lld]=%d is neither 0 nor 1", (long long)(q / row_bytes), (long long)(q % row_bytes / h->N),
+                    (long long)(q % h->N), (int)rows[q]);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t have = h->runs.rows[(size_t)run];
+    uint8_t* seg = h->d_img + (int64_t)run * h->seg_bytes;
+    rc = unit_append_pieces(h, h->d_stage, h->stage_bytes, rows, n_rows, row_bytes, h->runs.cap, [&](int64_t k, int64_t r) {
+        ++h->version;                                     // (the store changes from the first piece on)
+        const int64_t e0 = (have + r) * h->K, n_elems = k * h->K;
+        const int64_t d_first = e0 / 8, dwords = (e0 + n_elems - 1) / 8 - d_first + 1;
+        k_consensus_pack<<<dim3((unsigned)div_up(dwords, kWaves), (unsigned)div_up(h->N, 64)), kBlock, 0, h->stream>>>(
+            (const uint8_t*)h->d_stage, e0, n_elems, (int)h->N, seg, h->stride, d_first);
+        HIPCHK(h, hipGetLastError());
+        uint32_t* out = h->d_bits + ((int64_t)run * h->runs.cap + have + r) * h->K * h->W;
+        return unit_for_grid_chunks(n_elems, [&](int64_t l0, int64_t n) {
+            k_consensus_pack_bits<<<dim3((unsigned)n, (unsigned)div_up(h->N, kBlock)), kBlock, 0, h->stream>>>((const uint8_t*)h->d_stage, n_elems,
+                                                                                                             (int)h->N, (int)h->W, out, l0);
+            HIPCHK(h, hipGetLastError());
+            return SBE_OK;
+        });
+    });
+    if (rc) {
+        // a piece may be in the image already while the run's row count is not: the next append would OR new elements onto
+        // it.  The store is unshaped instead (sbe_consensus_reset comes next), as after a failed allocation
+        h->runs.rows.clear();
+        return rc;
+    }
+    h->runs.rows[(size_t)run] = have + n_rows;
+    return SBE_OK;
+}
+
+int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot, int32_t* counts_out) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
+    if (!run_mask) return fail(h, SBE_ERR_ARG, "null pointer argument: run_mask");
+    if (const int rc = check_slot_index(h, slot)) return rc;
+    SimArgs args{};
+    int64_t T = 0, steps = 0;
+    for (int r = 0; r < h->runs.count(); ++r) {
+        const int64_t rows = h->runs.rows[(size_t)r];
+        if (!run_mask[r] || rows == 0) continue;
+        T += rows;
+        args.seg_off[args.n_seg] = (int64_t)r * h->seg_bytes;
+        args.seg_rounds[args.n_seg] = (int32_t)((rows * h->K + kRoundElems - 1) / kRoundElems);
+        steps += (int64_t)args.seg_rounds[args.n_seg] * kRound;
+        ++args.n_seg;
+    }
+    if (T == 0) return fail(h, SBE_ERR_STATE, "the selected runs hold no rows");
+    if (T * h->K > SBE_CONSENSUS_MAX_ELEMENTS)
+        return fail(h, SBE_ERR_ARG, "the selection holds %lld rows x %d clusters = %lld elements, the limit is %d (2^24: the counts are exact in the f32 accumulator up to there)",
+                    (long long)T, h->K, (long long)(T * h->K), SBE_CONSENSUS_MAX_ELEMENTS);
+    Slot& s = h->slot[slot];
+    const size_t nn = (size_t)h->N * (size_t)h->N;
+    HIPCHK(h, hipSetDevice(h->device));
+    s.version = 0;                                        // (until the new matrix is in place)
+    int rc = unit_ensure(h, s.d_counts, s.bytes, nn * sizeof(int32_t));
+    if (rc) return rc;
+    const int64_t tiles = (h->N + kTile - 1) / kTile, tile_pairs = tiles * (tiles + 1) / 2;
+    const int64_t per_launch = h->launch_tiles > 0 ? h->launch_tiles : std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / steps));
+    args.img = h->d_img;
+    args.stride = h->stride;
+    args.counts = s.d_counts;
+    args.N = (int)h->N;
+    rc = unit_timed(h, [&] {
+        for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch) {      // one wave per tile pair
+            args.t0 = t0;
+            args.t_end = std::min(tile_pairs, t0 + per_launch);
+            k_consensus_similarity<<<(unsigned)(args.t_end - t0), 64, 0, h->stream>>>(args);
+            HIPCHK(h, hipGetLastError());
+        }
+        return SBE_OK;
+    });
+    if (!rc && counts_out) rc = unit_copy_back(h, (const int32_t*)s.d_counts, nn, {counts_out});
+    if (!rc) rc = unit_sync_timed(h);
+    if (rc) return rc;
+    s.T = T;
+    s.version = h->version;
+    return SBE_OK;
+}
+
+int sbe_consensus_scores(sbe_consensus* h, int slot, int run, int64_t* score_out) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
+    if (const int rc = check_slot_index(h, slot)) return rc;
+    if (run < 0 || run >= h->runs.count()) return fail(h, SBE_ERR_ARG, "run %d out of range [0,%d)", run, h->runs.count());
+    if (!score_out) return fail(h, SBE_ERR_ARG, "null pointer argument: score_out");
+    if (const int rc = check_slot_current(h, slot)) return rc;
+    const int64_t rows = h->runs.rows[(size_t)run];
+    HIPCHK(h, hipSetDevice(h->device));
+    const Slot& s = h->slot[slot];
+    const uint32_t* bits = h->d_bits + (int64_t)run * h->runs.cap * h->K * h->W;
+    int rc = unit_timed(h, [&] {
+        if (rows == 0) return (int)SBE_OK;
+        HIPCHK(h, hipMemsetAsync(h->d_score, 0, (size_t)rows * sizeof(unsigned long long), h->stream));
+        const int64_t side = (h->N + 63) / 64, lines = rows * h->K;
+        const int64_t per_launch = std::max<int64_t>(1, std::min(kMaxGridBlocks, kScoreUnitsPerLaunch / (side * side)));
+        for (int64_t l0 = 0; l0 < lines; l0 += per_launch) {
+            k_consensus_scores<<<(unsigned)std::min(per_launch, lines - l0), kBlock, (size_t)(32 * h->W) * sizeof(uint16_t), h->stream>>>(
+                bits, l0, h->K, (int)h->N, (int)h->W, s.d_counts, (long long)s.T, h->d_score);
+            HIPCHK(h, hipGetLastError());
+        }
+        return (int)SBE_OK;
+    });
+    if (!rc && rows) rc = unit_copy_back(h, (const int64_t*)h->d_score, (size_t)rows, {score_out});
+    if (!rc) rc = unit_sync_timed(h);
+    return rc;
+}
+
+int sbe_consensus_compare(sbe_consensus* h, int64_t* row_max, int64_t* row_sum) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
+    if (!row_max || !row_sum) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !row_max ? "row_max" : "row_sum");
+    for (int slot = 0; slot < 2; ++slot)
+        if (const int rc = check_slot_current(h, slot)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = unit_timed(h, [&] {
+        k_consensus_compare<<<(unsigned)h->N, kBlock, 0, h->stream>>>(h->slot[0].d_counts, (long long)h->slot[0].T, h->slot[1].d_counts,
+                                                                    (long long)h->slot[1].T, (int)h->N, h->d_cmp, h->d_cmp + h->N);
+        HIPCHK(h, hipGetLastError());
+        return SBE_OK;
+    });
+    if (!rc) rc = unit_copy_back(h, (const int64_t*)h->d_cmp, (size_t)h->N, {row_max, row_sum});
+    if (!rc) rc = unit_sync_timed(h);
+    return rc;
+}
+
+}  // extern "C"
