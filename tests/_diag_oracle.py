@@ -136,12 +136,14 @@ def column(x, max_lag=0, exact=True):
     if even > 0:
         rho_t[max_t + 1] = even
     t = 1
+    replaced = []                                                          # the first entry (t + 1) of every pair the second loop replaces
     while t <= max_t - 2:
         diff = (rho_t[t + 1] + rho_t[t + 2]) - (rho_t[t - 1] + rho_t[t])
         margin = min(margin, abs(diff))
         if diff > 0:
             rho_t[t + 1] = (rho_t[t - 1] + rho_t[t]) / 2
             rho_t[t + 2] = rho_t[t + 1]
+            replaced.append(t + 1)
         t += 2
     if mean_var == 0:
         # every d is exactly zero here and on the device (the chain sums of such a column must be exact: asserted), so
@@ -157,7 +159,7 @@ def column(x, max_lag=0, exact=True):
     aux.update(G0=G(0), mean_var=mean_var, var_plus=var_plus, between=between, qmax=qmax, K=max_t + 2, floor=floor,
                abs_rho=float(np.abs(rho_t[:max_t + 2]).sum()), tau=tau)
     return dict(mean=mean, sd=sd, ess=ess, rhat=rhat, mcse_mean=sd / math.sqrt(ess), n_lags=max_t + 2, flag=flag, margin=margin,
-                tau=tau, aux=aux)
+                tau=tau, replaced=tuple(replaced), aux=aux)
 
 
 def column_bounds(c):
@@ -195,8 +197,8 @@ def column_bounds(c):
 
 
 def diagnose(chains, burnin=0.1, split=True, max_lag=0):
-    """The outputs as arrays over the columns, with `margin`, `bound` (a dict of arrays like the outputs), `cut`,
-    `n_chains` and `n_draws`."""
+    """The outputs as arrays over the columns, with `margin`, `bound` (a dict of arrays like the outputs), `rho_bound`,
+    `replaced` (per column the first entries of the pairs the monotone pass replaced), `cut`, `n_chains` and `n_draws`."""
     x, cut = prepare(chains, burnin, split)
     M, n, P = x.shape
     cols = [column(np.ascontiguousarray(x[:, :, j]), max_lag) for j in range(P)]
@@ -207,6 +209,7 @@ def diagnose(chains, burnin=0.1, split=True, max_lag=0):
     res["margin"] = np.array([c["margin"] for c in cols])
     res["bound"] = {k: np.array([b[k] for b in bnds]) for k in FIELDS}
     res["rho_bound"] = np.array([b.get("rho", 0.0) for b in bnds])
+    res["replaced"] = [c.get("replaced", ()) for c in cols]
     res.update(cut=cut, n_chains=M, n_draws=n)
     return res
 

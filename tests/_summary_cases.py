@@ -2,7 +2,9 @@
 derived column of every case has a decision margin >= 1e-9 and above twice its rho bound under the checker alone) and
 tests/test_gpu_summary.py (device against checker).  The checker's result of a case is computed once and shared; nothing
 changes it.  Each shape is the smallest at which its mechanism can go wrong: the wave (64), the block (256) and the sorting
-network's padding (a power of two, one below, one above), the LDS limit and one past it, more columns than a launch."""
+network's padding (a power of two, one below, one above), the LDS limit and one past it, more columns than a launch, the
+smallest n at which a derived column writes rho_t past the 2048 entries kept in LDS (the spill_* cases: the shifted chains of
+tests/_diag_range_cases.py, whose ranks walk to the n - 3 bound as the values do)."""
 from __future__ import annotations
 
 import functools
@@ -11,6 +13,7 @@ import numpy as np
 
 from tests import _diag_cases as dcases
 from tests import _diag_oracle as orc
+from tests import _diag_range_cases as rcases
 from tests import _summary_oracle as sorc
 
 MIN_MARGIN = 1e-9
@@ -94,7 +97,11 @@ CASES = {
     "hdi_clips_low": (lambda: orc.ar1(np.random.default_rng(61), 0.3, 1, 10, 2), dict(burnin=0.0, hdi_prob=0.01)),      # floor(hdi_prob N) = 0: clipped to 1
     "chain_constant": (lambda: _chain_constant(np.random.default_rng(62)), dict()),                             # W = 0: rhat_rank = +inf
     "max_lag_hit": (lambda: orc.ar1(np.random.default_rng(53), 0.9, 4, 1000, 2, loc=2.0), dict(max_lag=10)),
+    "spill_2x2051": (rcases.spill_edge, _FLAT),                                                                 # entries 2048 and 2049, no more
+    "spill_2x2400": (rcases.spill_table, _FLAT),                                                                # 3 columns: 12 derived ones
+    "spill_global_8x2300": (rcases.spill_global, _FLAT),
 }
+SPILL = ("spill_2x2051", "spill_2x2400", "spill_global_8x2300")
 
 
 @functools.lru_cache(maxsize=None)

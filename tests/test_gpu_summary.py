@@ -81,6 +81,13 @@ def test_the_cases_cover_what_they_are_there_for():
     assert cases.case("hdi_widest")[1]["hdi_prob"] < 1.0 and sorc.hdi_span(cases.case("hdi_widest")[1]["hdi_prob"], n) == n - 1
     assert math.floor(cases.case("hdi_clips_low")[1]["hdi_prob"] * n) == 0 and sorc.hdi_span(cases.case("hdi_clips_low")[1]["hdi_prob"], n) == 1
     assert cases.case("wide_257")[0].shape[2] == 257 and cases.case("one_column")[0].shape[2] == 1
+    # rho_t past the 2048 entries kept in LDS, in the store's own pass and in a derived one
+    for name, path in (("spill_2x2051", "lds"), ("spill_2x2400", "lds"), ("spill_global_8x2300", "global")):
+        x, kw, want = cases.case(name)
+        assert want["n_draws"] > 2048 and want["n_lags"].max() > 2048
+        assert max(p["col"]["n_lags"] for c in want["columns"] for p in c["parts"].values()) > 2048
+        assert summary.summarize(list(x), **kw).path == path
+    assert (cases.case("spill_global_8x2300")[2]["n_chains"] * 2300 > limit) and cases.case("spill_2x2400")[0].shape[2] == 3
 
 
 def _mp_ndtri(p):
@@ -184,6 +191,28 @@ def test_bits_do_not_depend_on_launch_size_capacity_appends_or_position():
         for c in range(m):
             h.append(c, x[c])
         assert _same_bits(h.compute(), ref)
+    finally:
+        h.close()
+
+
+def test_spilled_bits_do_not_depend_on_the_launch_size():
+    """2 x 2400 x 3, rho_t past entry 2048 in the store's pass and in the derived ones.  With C = 1, 2 or 3 columns per launch of
+    the rank kernel the derived store is laid out [M][4 C][n] anew, the derived pass needs 4 C scratch slices and the store's own
+    pass C of the same scratch."""
+    x, kw, want = cases.case("spill_2x2400")
+    m, s, p = x.shape
+    ref = summary.summarize(list(x), **kw)
+    _check(ref, want, "spill_2x2400 (reference of the launch sizes)")
+    h = summary.SummaryHandle()
+    try:
+        for launch, shape in ((1, (3, 1)), (2, (2, 2)), (0, (1, 3))):
+            h.set_launch_columns(launch)
+            h.reset(m, p, s)
+            for c in range(m):
+                h.append(c, x[c])
+            res = h.compute(**kw)
+            assert _same_bits(res, ref), launch
+            assert (res.launches, res.launch_columns) == shape
     finally:
         h.close()
 
