@@ -1,5 +1,5 @@
 """What the owners of a device handle share: Engine (prefix `sbe`) and the side units' `_Store` (`sbe_elpd`), `EmHandle`
-(`sbe_em`), `AssocHandle` (`sbe_assoc`), `GeoHandle` (`sbe_geo`), `DiagHandle` (`sbe_diag`), `AlignHandle` (`sbe_align`), `SummaryHandle` (`sbe_summary`), `ConsensusHandle` (`sbe_consensus`).  Every handle type of the C ABI has <prefix>_create, <prefix>_destroy and
+(`sbe_em`), `AssocHandle` (`sbe_assoc`), `GeoHandle` (`sbe_geo`), `DiagHandle` (`sbe_diag`), `AlignHandle` (`sbe_align`), `SummaryHandle` (`sbe_summary`), `ConsensusHandle` (`sbe_consensus`), `CompareHandle` (`sbe_compare`).  Every handle type of the C ABI has <prefix>_create, <prefix>_destroy and
 <prefix>_last_error with the same conventions (include/sbe_engine.h, "Errors"), and every owner follows the package's
 process model (sbayes_amd/_proc.py): created in the process that uses it, registered there, never pickled, forgotten --
 not destroyed -- in a fork()ed child."""

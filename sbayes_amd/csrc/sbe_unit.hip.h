@@ -1,5 +1,5 @@
 #pragma once
-// sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip, sbe_align.hip, sbe_summary.hip, sbe_consensus.hip: each an opaque
+// sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip, sbe_align.hip, sbe_summary.hip, sbe_consensus.hip, sbe_compare.hip: each an opaque
 // handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check,
 // create, destroy, device buffers that only grow, launches in grid chunks, the row store's lanes and its piece loop, the
 // timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes

@@ -1,6 +1,6 @@
 #pragma once
 // sbe_unit_device.hip.h -- what the device code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_diag.hip,
-// sbe_summary.hip, sbe_align.hip, sbe_consensus.hip; sbe_unit.hip.h has the host side): the fixed-tree reductions, the 32 x 32 transpose that fills a row store and
+// sbe_summary.hip, sbe_align.hip, sbe_consensus.hip, sbe_compare.hip; sbe_unit.hip.h has the host side): the fixed-tree reductions, the 32 x 32 transpose that fills a row store and
 // the launch limits.  Device code only and nothing of the engine: a unit that includes this header compiles no kernels
 // but its own.  Everything lives in an unnamed namespace: every unit compiles its own copy.
 #include <hip/hip_runtime.h>
