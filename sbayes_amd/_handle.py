@@ -1,5 +1,5 @@
-"""What the owners of a device handle share: Engine (prefix `sbe`) and the side units' `_Store` (`sbe_elpd`), `EmHandle`
-(`sbe_em`), `AssocHandle` (`sbe_assoc`), `GeoHandle` (`sbe_geo`), `DiagHandle` (`sbe_diag`), `AlignHandle` (`sbe_align`), `SummaryHandle` (`sbe_summary`), `ConsensusHandle` (`sbe_consensus`), `CompareHandle` (`sbe_compare`).  Every handle type of the C ABI has <prefix>_create, <prefix>_destroy and
+"""What the owners of a device handle share: Engine (prefix `sbe`) and the handle classes of the side units (prefix
+`sbe_<unit>`).  Every handle type of the C ABI has <prefix>_create, <prefix>_destroy and
 <prefix>_last_error with the same conventions (include/sbe_engine.h, "Errors"), and every owner follows the package's
 process model (sbayes_amd/_proc.py): created in the process that uses it, registered there, never pickled, forgotten --
 not destroyed -- in a fork()ed child."""
@@ -46,6 +46,18 @@ def unit_prototypes(prefix):
         f"{prefix}_last_error": (ct.c_char_p, [c_handle_p]),
         f"{prefix}_destroy": (ct.c_int, [c_handle_p]),
         f"{prefix}_last_kernel_ms": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_float)]),
+    }
+
+
+def store_prototypes(prefix, shape):
+    """unit_prototypes and the rows every unit with a row store adds: create on a device, reset (`shape`: its argument types
+    behind the lane count), append_rows and rows of a lane."""
+    return {
+        **unit_prototypes(prefix),
+        f"{prefix}_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
+        f"{prefix}_reset": (ct.c_int, [c_handle_p, ct.c_int, *shape]),
+        f"{prefix}_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
+        f"{prefix}_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
     }
 
 
@@ -123,6 +135,43 @@ class UnitHandle(DeviceHandle):
         ms = ct.c_float(0)
         self._check(self._fn("last_kernel_ms")(self._h, ct.byref(ms)))
         return float(ms.value)
+
+
+class RowStoreHandle(UnitHandle):
+    """Owner of a unit handle that stores rows per lane (the chains of a column store, the runs of a sample store).  A
+    subclass names a lane in the messages (_lane), counts its lanes (_lane_count()) and has reset(*shape) and
+    append(lane, rows)."""
+
+    _lane = "lane"
+
+    def rows(self, lane) -> int:
+        n = ct.c_int64(0)
+        self._check(self._fn("rows")(self._h, int(lane), ct.byref(n)))
+        return n.value
+
+    def _check_lane(self, lane):
+        lane, count = int(lane), self._lane_count()
+        if not 0 <= lane < count:
+            raise ValueError(f"{self._lane} {lane} out of range [0, {count})")
+        return lane
+
+    def _append_rows(self, lane, block):
+        """<prefix>_append_rows of a checked block (rows along its first axis); returns the library's code."""
+        return self._fn("append_rows")(self._h, lane, _ptr(block), block.shape[0])
+
+    @classmethod
+    def filled(cls, device, shape, blocks):
+        """A new handle on `device`, reset to `shape`, with blocks[lane] appended to every lane.  The caller closes it; it is
+        closed here if any of that raises."""
+        h = cls(device)
+        try:
+            h.reset(*shape)
+            for lane, block in enumerate(blocks):
+                h.append(lane, block)
+        except BaseException:
+            h.close()
+            raise
+        return h
 
 
 # ---- one handle per device, created lazily (assoc.py, geo.py): device -> handle; per process, emptied in a fork()ed child --

@@ -46,12 +46,8 @@ STATIC_LDS = 4096                        # SBE_ALIGN_STATIC_LDS
 
 # name -> (restype, argtypes); mirrors include/sbe_align.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    **_handle.unit_prototypes("sbe_align"),
+    **_handle.store_prototypes("sbe_align", [ct.c_int, ct.c_int64, ct.c_int64]),
     "sbe_align_max_objects": (ct.c_int64, [ct.c_int]),
-    "sbe_align_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_align_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_align_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
-    "sbe_align_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
     "sbe_align_within": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p]),
     "sbe_align_counts": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_void_p]),
     "sbe_align_runs": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p]),
@@ -115,7 +111,7 @@ def _check_runs(runs):
     if len({b.shape[1:] for b in blocks}) != 1:
         raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
     k, n = blocks[0].shape[1:]
-    _check_shape(len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1))
+    _check_shape(*_store_shape(blocks, k, n))
     return blocks, k, n
 
 
@@ -126,45 +122,53 @@ def _burn_rows(lengths, burnin):
     return [int(burnin * int(s)) for s in lengths]                          # Results.drop_burnin
 
 
-class AlignHandle(_handle.UnitHandle):
-    """Owner of one sbe_align handle: the bit store of several runs of cluster samples on one device.
-    last_kernel_ms(): the within-run kernel of the last within() call."""
-    _prefix, _noun = "sbe_align", "an alignment handle"
+class SampleStoreHandle(_handle.RowStoreHandle):
+    """Owner of a handle with the store of several runs of cluster samples on one device (AlignHandle, ConsensusHandle).  A
+    subclass gives its module's load() and shape check."""
+    _lane = "run"
+    _load = staticmethod(load)
+    _check_shape = staticmethod(_check_shape)
 
     def __init__(self, device=None):
+        self._unshape()
+        self._create_on(self._load, device)
+
+    def _lane_count(self):
+        return self.n_runs
+
+    def _unshape(self):
         self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
         self._stored = []
-        self._create_on(load, device)
 
     def reset(self, n_runs, n_clusters, n_objects, capacity):
         """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits."""
         n_runs, n_clusters, n_objects, capacity = int(n_runs), int(n_clusters), int(n_objects), int(capacity)
-        _check_shape(n_runs, n_clusters, n_objects, capacity)
-        self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
-        self._check(self._lib.sbe_align_reset(self._h, n_runs, n_clusters, n_objects, capacity))
+        self._check_shape(n_runs, n_clusters, n_objects, capacity)
+        self._unshape()
+        self._check(self._fn("reset")(self._h, n_runs, n_clusters, n_objects, capacity))
         self.n_runs, self.n_clusters, self.n_objects, self.capacity = n_runs, n_clusters, n_objects, capacity
         self._stored = [0] * n_runs
 
-    def rows(self, run) -> int:
-        n = ct.c_int64(0)
-        self._check(self._lib.sbe_align_rows(self._h, int(run), ct.byref(n)))
-        return n.value
-
-    def _check_run(self, run):
-        run = int(run)
-        if not 0 <= run < self.n_runs:
-            raise ValueError(f"run {run} out of range [0, {self.n_runs})")
-        return run
-
-    def append(self, run, clusters):
-        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run."""
-        run = self._check_run(run)
+    def _checked_block(self, run, clusters):
+        """(run, samples uint8 [n, K, N]) of an append, refused here where the run would overflow."""
+        run = self._check_lane(run)
         block = _check_samples(clusters, (self.n_clusters, self.n_objects))
         if self._stored[run] + block.shape[0] > self.capacity:
             raise ValueError(f"store overflow: run {run} holds {self._stored[run]} samples, {block.shape[0]} more exceed the capacity "
                              f"of {self.capacity}")
-        self._check(self._lib.sbe_align_append_rows(self._h, run, _ptr(block), block.shape[0]))
+        return run, block
+
+    def append(self, run, clusters):
+        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run."""
+        run, block = self._checked_block(run, clusters)
+        self._check(self._append_rows(run, block))
         self._stored[run] += block.shape[0]
+
+
+class AlignHandle(SampleStoreHandle):
+    """Owner of one sbe_align handle: the bit store of several runs of cluster samples on one device.
+    last_kernel_ms(): the within-run kernel of the last within() call."""
+    _prefix, _noun = "sbe_align", "an alignment handle"
 
     def within(self, seed=0):
         """One permutation per stored sample of every run: a list of int8 [S_r, K] arrays."""
@@ -194,7 +198,7 @@ class AlignHandle(_handle.UnitHandle):
     def runs(self, pivot=0, aligned=True, burn_rows=None):
         """(run permutations int8 [R, K], agreement matrices int64 [R, K, K]) of every run against run `pivot`."""
         burn = self._burn(burn_rows)
-        pivot = self._check_run(pivot)
+        pivot = self._check_lane(pivot)
         run_perms = np.empty((self.n_runs, self.n_clusters), dtype=np.int8)
         agreement = np.empty((self.n_runs, self.n_clusters, self.n_clusters), dtype=np.int64)
         self._check(self._lib.sbe_align_runs(self._h, pivot, int(bool(aligned)), _ptr(burn), _ptr(run_perms), _ptr(agreement)))
@@ -227,12 +231,14 @@ class AlignResult:
         return int(self.agreement[r][np.arange(k), self.run_perms[r]].sum())
 
 
+def _store_shape(blocks, k, n):
+    """The shape of a store that holds these runs: the capacity is the longest run's, and at least one sample."""
+    return len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1)
+
+
 def _within(blocks, k, n, seed, device):
-    h = AlignHandle(device)
+    h = AlignHandle.filled(device, _store_shape(blocks, k, n), blocks)
     try:
-        h.reset(len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1))
-        for r, block in enumerate(blocks):
-            h.append(r, block)
         return h.within(seed)
     finally:
         h.close()
@@ -261,11 +267,8 @@ def align_runs(runs, pivot=0, within=None, burnin=0.0, device=None) -> AlignResu
         raise ValueError(f"pivot {pivot} out of range [0, {len(blocks)})")
     seed = None if within is None else _check_seed(within)
     burn = _burn_rows([b.shape[0] for b in blocks], burnin)
-    h = AlignHandle(device)
+    h = AlignHandle.filled(device, _store_shape(blocks, k, n), blocks)
     try:
-        h.reset(len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1))
-        for r, block in enumerate(blocks):
-            h.append(r, block)
         if seed is None:
             perms = [np.tile(np.arange(k, dtype=np.int8), (b.shape[0], 1)) for b in blocks]
             kernel_ms = 0.0

@@ -46,12 +46,8 @@ MAX_IMAGE_BYTES = 1 << 34                # SBE_CONSENSUS_MAX_IMAGE_BYTES
 
 # name -> (restype, argtypes); mirrors include/sbe_consensus.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    **_handle.unit_prototypes("sbe_consensus"),
+    **_handle.store_prototypes("sbe_consensus", [ct.c_int, ct.c_int64, ct.c_int64]),
     "sbe_consensus_image_bytes": (ct.c_int64, [ct.c_int, ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_consensus_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_consensus_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_consensus_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
-    "sbe_consensus_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
     "sbe_consensus_similarity": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int, ct.c_void_p]),
     "sbe_consensus_scores": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int, ct.c_void_p]),
     "sbe_consensus_compare": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_void_p]),
@@ -111,57 +107,31 @@ def _check_runs(runs, burnin):
     if len({b.shape[1:] for b in blocks}) != 1:
         raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
     k, n = blocks[0].shape[1:]
-    _check_shape(len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1))
+    _check_shape(*align._store_shape(blocks, k, n))
     burn = align._burn_rows([b.shape[0] for b in blocks], burnin)
     return [b[at:] for b, at in zip(blocks, burn)], k, n
 
 
-class ConsensusHandle(_handle.UnitHandle):
+class ConsensusHandle(align.SampleStoreHandle):
     """Owner of one sbe_consensus handle: the store of several runs of cluster samples on one device and two similarity
     matrices (slots 0 and 1).  last_kernel_ms(): the kernels of the last similarity(), scores() or compare()."""
     _prefix, _noun = "sbe_consensus", "a consensus handle"
+    _load = staticmethod(load)
+    _check_shape = staticmethod(_check_shape)
 
-    def __init__(self, device=None):
-        self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
-        self._stored = []
+    def _unshape(self):
+        super()._unshape()
         self.slot_samples = [0, 0]                  # T of the matrix in each slot (0: empty or out of date)
-        self._create_on(load, device)
-
-    def reset(self, n_runs, n_clusters, n_objects, capacity):
-        """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits."""
-        n_runs, n_clusters, n_objects, capacity = int(n_runs), int(n_clusters), int(n_objects), int(capacity)
-        _check_shape(n_runs, n_clusters, n_objects, capacity)
-        self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
-        self.slot_samples = [0, 0]
-        self._check(self._lib.sbe_consensus_reset(self._h, n_runs, n_clusters, n_objects, capacity))
-        self.n_runs, self.n_clusters, self.n_objects, self.capacity = n_runs, n_clusters, n_objects, capacity
-        self._stored = [0] * n_runs
-
-    def rows(self, run) -> int:
-        n = ct.c_int64(0)
-        self._check(self._lib.sbe_consensus_rows(self._h, int(run), ct.byref(n)))
-        return n.value
-
-    def _check_run(self, run):
-        run = int(run)
-        if not 0 <= run < self.n_runs:
-            raise ValueError(f"run {run} out of range [0, {self.n_runs})")
-        return run
 
     def append(self, run, clusters):
         """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run.  Both slots are out of date afterwards."""
-        run = self._check_run(run)
-        block = align._check_samples(clusters, (self.n_clusters, self.n_objects))
-        if self._stored[run] + block.shape[0] > self.capacity:
-            raise ValueError(f"store overflow: run {run} holds {self._stored[run]} samples, {block.shape[0]} more exceed the capacity "
-                             f"of {self.capacity}")
+        run, block = self._checked_block(run, clusters)
         if block.shape[0]:
             self.slot_samples = [0, 0]
-        rc = self._lib.sbe_consensus_append_rows(self._h, run, _ptr(block), block.shape[0])
+        rc = self._append_rows(run, block)
         if rc == 2:                                 # SBE_ERR_HIP: the library has unshaped the store, and so does this object
             message = self._last_error()
-            self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
-            self._stored = []
+            self._unshape()
             raise _handle.EngineError(rc, message)
         self._check(rc)
         self._stored[run] += block.shape[0]
@@ -178,7 +148,7 @@ class ConsensusHandle(_handle.UnitHandle):
         slot = _check_slot(slot)
         mask = np.zeros(self.n_runs, dtype=np.uint8)
         for run in (range(self.n_runs) if runs is None else runs):
-            mask[self._check_run(run)] = 1
+            mask[self._check_lane(run)] = 1
         total = sum(s for s, m in zip(self._stored, mask) if m)
         _check_elements(total, self.n_clusters)
         counts = np.empty((self.n_objects, self.n_objects), dtype=np.int32) if copy else None
@@ -189,7 +159,7 @@ class ConsensusHandle(_handle.UnitHandle):
 
     def scores(self, run, slot=0):
         """int64 [rows(run)]: the score of every stored sample of `run` against the matrix in `slot`."""
-        run, slot = self._check_run(run), _check_slot(slot)
+        run, slot = self._check_lane(run), _check_slot(slot)
         scores = np.empty(self._stored[run], dtype=np.int64)
         self._check(self._lib.sbe_consensus_scores(self._h, slot, run, _ptr(scores)))
         return scores
@@ -237,23 +207,11 @@ class RunComparison:
     n_samples: tuple
 
 
-def _filled(blocks, k, n, device):
-    h = ConsensusHandle(device)
-    try:
-        h.reset(len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1))
-        for r, block in enumerate(blocks):
-            h.append(r, block)
-    except BaseException:
-        h.close()
-        raise
-    return h
-
-
 def similarity(runs, burnin=0.0, device=None) -> Similarity:
     """The similarity of the objects over all samples of `runs` (a list of 0/1 [S_r, K, N] arrays) after burn-in."""
     blocks, k, n = _check_runs(runs, burnin)
     _check_elements(sum(b.shape[0] for b in blocks), k)
-    h = _filled(blocks, k, n, device)
+    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
     try:
         counts = h.similarity()
         return Similarity(counts, h.slot_samples[0], h.last_kernel_ms())
@@ -278,7 +236,7 @@ def point_estimate(runs, burnin=0.0, device=None) -> PointEstimate:
     """The consensus clustering: the sample of `runs` (after burn-in) with the smallest score against the pooled matrix."""
     blocks, k, n = _check_runs(runs, burnin)
     _check_elements(sum(b.shape[0] for b in blocks), k)
-    h = _filled(blocks, k, n, device)
+    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
     try:
         h.similarity(copy=False)
         kernel_ms = h.last_kernel_ms()
@@ -306,7 +264,7 @@ def compare_runs(runs, burnin=0.0, device=None) -> RunComparison:
         _check_elements(b.shape[0], k)
     r_n = len(blocks)
     max_abs, mean_abs = np.zeros((r_n, r_n)), np.zeros((r_n, r_n))
-    h = _filled(blocks, k, n, device)
+    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
     try:
         for a in range(r_n - 1):
             h.similarity([a], slot=0, copy=False)
@@ -356,7 +314,7 @@ def main(argv=None):
     _check_elements(sum(lengths), k)
     r_n = len(blocks)
     max_abs, mean_abs = np.zeros((r_n, r_n)), np.zeros((r_n, r_n))
-    h = _filled(blocks, k, n, args.device)                  # one store serves the three questions
+    h = ConsensusHandle.filled(args.device, align._store_shape(blocks, k, n), blocks)      # one store serves the three questions
     try:
         counts = h.similarity()                             # the pooled matrix, slot 0
         total = h.slot_samples[0]

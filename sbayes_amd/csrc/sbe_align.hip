@@ -1,5 +1,5 @@
 // sbe_align.hip -- alignment of cluster labels within a run and across runs on the device (include/sbe_align.h): the bit
-// store of R runs of cluster samples, its pack kernel, the within-run kernel (one permutation per sample against the
+// store of R runs of cluster samples (sbe_unit.hip.h has it), the within-run kernel (one permutation per sample against the
 // running sum of the aligned samples so far), the counts kernel and the across-run kernel.  The contract is
 // tests/_align_oracle.py; DESIGN.md section 17 has the layout, the structure of the kernels and the limits.
 //
@@ -296,32 +296,12 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_runs(const int32_t* cnt, 
     }
 }
 
-// ---- pack: host bytes [n][K][N] (staging) -> bit words [n][K][W]; a wave takes 64 objects of one (row, cluster) ------
-__global__ __launch_bounds__(kAlignBlock) void k_align_pack(const uint8_t* rows, int64_t n_lines, int N, int W, uint32_t* out, int64_t line0) {
-    const int64_t line = line0 + blockIdx.x;                   // row * K + cluster, within this piece
-    const int n = blockIdx.y * kAlignBlock + threadIdx.x;
-    const bool bit = line < n_lines && n < N && rows[line * N + n] != 0;
-    const unsigned long long both = __ballot(bit);
-    const int w = n >> 5;
-    if ((threadIdx.x & 63) == 0 && line < n_lines) {
-        if (w < W) out[line * W + w] = (uint32_t)both;
-        if (w + 1 < W) out[line * W + w + 1] = (uint32_t)(both >> 32);
-    }
-}
-
 }  // namespace
 
-struct sbe_align : sbe_unit_handle {           // (sbe_unit.hip.h; ev: around the within-run kernel of the last sbe_align_within)
-    unit_lanes runs;                    // (empty: no shape yet)
-    int K = 0;
-    int64_t N = 0, W = 0;
+struct sbe_align : sbe_unit_handle, unit_bit_store {   // (sbe_unit.hip.h; ev: around the within-run kernel of the last sbe_align_within)
     bool perm_valid = false;
-    uint32_t* d_bits = nullptr;         // [runs][cap][K][W]
-    size_t bits_bytes = 0;
     int8_t* d_perm = nullptr;           // [runs][cap][K]
     size_t perm_bytes = 0;
-    void* d_stage = nullptr;            // host rows in flight
-    size_t stage_bytes = 0;
     int32_t* d_cnt = nullptr;           // [runs][K][N]
     size_t cnt_bytes = 0;
     int32_t* d_rows = nullptr;          // [SBE_ALIGN_MAX_RUNS]
@@ -363,6 +343,21 @@ int launch_runs(sbe_align* h, int pivot) {
     k_align_runs<K><<<(unsigned)h->runs.count(), kAlignBlock, 0, h->stream>>>(h->d_cnt, pivot, (int)h->N, h->d_run_perm, h->d_agree);
     HIPCHK(h, hipGetLastError());
     return SBE_OK;
+}
+
+// fn(std::integral_constant<int, K>()) for the store's K in 1 .. kMaxK: the kernels are compiled per K
+template <class Fn>
+int for_clusters(int K, Fn fn) {
+    switch (K) {
+        case 1: return fn(std::integral_constant<int, 1>());
+        case 2: return fn(std::integral_constant<int, 2>());
+        case 3: return fn(std::integral_constant<int, 3>());
+        case 4: return fn(std::integral_constant<int, 4>());
+        case 5: return fn(std::integral_constant<int, 5>());
+        case 6: return fn(std::integral_constant<int, 6>());
+        case 7: return fn(std::integral_constant<int, 7>());
+        default: return fn(std::integral_constant<int, 8>());
+    }
 }
 
 // the counts of every run into d_cnt (arguments checked by the caller)
@@ -416,11 +411,10 @@ int sbe_align_reset(sbe_align* h, int n_runs, int n_clusters, int64_t n_objects,
                     (long long)max_objects(n_clusters), n_clusters);
     if (capacity_rows < 1 || capacity_rows > SBE_ALIGN_MAX_ROWS)
         return fail(h, SBE_ERR_ARG, "capacity_rows=%lld out of range [1, %d]", (long long)capacity_rows, SBE_ALIGN_MAX_ROWS);
-    const int64_t W = (n_objects + 31) / 32;
     h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
     h->perm_valid = false;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_bits, h->bits_bytes, (size_t)n_runs * (size_t)capacity_rows * (size_t)n_clusters * (size_t)W * sizeof(uint32_t));
+    int rc = h->alloc_bits(h, n_runs, n_clusters, n_objects, capacity_rows);
     if (!rc) rc = unit_ensure(h, h->d_perm, h->perm_bytes, (size_t)n_runs * (size_t)capacity_rows * (size_t)n_clusters);
     if (!rc) rc = unit_ensure(h, h->d_cnt, h->cnt_bytes, (size_t)n_runs * (size_t)n_clusters * (size_t)n_objects * sizeof(int32_t));
     if (!rc) rc = unit_ensure(h, h->d_rows, (size_t)SBE_ALIGN_MAX_RUNS * sizeof(int32_t));
@@ -428,11 +422,7 @@ int sbe_align_reset(sbe_align* h, int n_runs, int n_clusters, int64_t n_objects,
     if (!rc) rc = unit_ensure(h, h->d_run_perm, (size_t)SBE_ALIGN_MAX_RUNS * kMaxK);
     if (!rc) rc = unit_ensure(h, h->d_agree, (size_t)SBE_ALIGN_MAX_RUNS * kMaxK * kMaxK * sizeof(long long));
     if (rc) return rc;
-    h->K = n_clusters;
-    h->N = n_objects;
-    h->W = W;
-    h->runs.cap = capacity_rows;
-    h->runs.rows.assign((size_t)n_runs, 0);
+    h->set_shape(n_runs, n_clusters, n_objects, capacity_rows);
     return SBE_OK;
 }
 
@@ -443,24 +433,10 @@ int sbe_align_rows(const sbe_align* h, int run, int64_t* n_rows_out) {
 
 int sbe_align_append_rows(sbe_align* h, int run, const uint8_t* rows, int64_t n_rows) {
     CHECK_HANDLE(h, kNullHandle);
-    int rc = h->runs.check_append(h, kLane, kReset, run, rows, n_rows);
-    if (rc || n_rows == 0) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int64_t have = h->runs.rows[(size_t)run];
-    rc = unit_append_pieces(h, h->d_stage, h->stage_bytes, rows, n_rows, (int64_t)h->K * h->N, h->runs.cap, [&](int64_t k, int64_t r) {
+    return h->append(h, kLane, kReset, run, rows, n_rows, [&](int64_t, int64_t) {
         h->perm_valid = false;                            // (the store changes from the first piece on)
-        const int64_t lines = k * h->K;
-        uint32_t* out = h->d_bits + ((int64_t)run * h->runs.cap + have + r) * h->K * h->W;
-        return unit_for_grid_chunks(lines, [&](int64_t l0, int64_t n) {
-            k_align_pack<<<dim3((unsigned)n, (unsigned)div_up(h->N, kAlignBlock)), kAlignBlock, 0, h->stream>>>((const uint8_t*)h->d_stage, lines,
-                                                                                                             (int)h->N, (int)h->W, out, l0);
-            HIPCHK(h, hipGetLastError());
-            return SBE_OK;
-        });
+        return SBE_OK;
     });
-    if (rc) return rc;
-    h->runs.rows[(size_t)run] = have + n_rows;
-    return SBE_OK;
 }
 
 int sbe_align_within(sbe_align* h, int seed_rows, int8_t* perm_out) {
@@ -476,18 +452,7 @@ int sbe_align_within(sbe_align* h, int seed_rows, int8_t* perm_out) {
     while (G < 32 && h->W * G * 2 <= kAlignBlock) G *= 2;
     const WithinArgs args{h->d_bits, h->d_rows, h->d_perm, h->runs.cap, (int)h->N, (int)h->W, G, seed_rows};
     const size_t lds = (size_t)h->K * 32 * (size_t)h->W * sizeof(int32_t);
-    rc = unit_timed(h, [&] {
-        switch (h->K) {
-            case 1: return launch_within<1>(h, args, lds);
-            case 2: return launch_within<2>(h, args, lds);
-            case 3: return launch_within<3>(h, args, lds);
-            case 4: return launch_within<4>(h, args, lds);
-            case 5: return launch_within<5>(h, args, lds);
-            case 6: return launch_within<6>(h, args, lds);
-            case 7: return launch_within<7>(h, args, lds);
-            default: return launch_within<8>(h, args, lds);
-        }
-    });
+    rc = unit_timed(h, [&] { return for_clusters(h->K, [&](auto k) { return launch_within<k()>(h, args, lds); }); });
     if (rc) return rc;
     for (int r = 0; r < h->runs.count(); ++r) {
         const size_t bytes = (size_t)h->runs.rows[(size_t)r] * (size_t)h->K;
@@ -519,16 +484,7 @@ int sbe_align_runs(sbe_align* h, int pivot, int aligned, const int64_t* burn_row
     if (!run_perm_out || !agreement_out) return fail(h, SBE_ERR_ARG, "null pointer argument: output");
     rc = run_counts(h, aligned, burn_rows);
     if (rc) return rc;
-    switch (h->K) {
-        case 1: rc = launch_runs<1>(h, pivot); break;
-        case 2: rc = launch_runs<2>(h, pivot); break;
-        case 3: rc = launch_runs<3>(h, pivot); break;
-        case 4: rc = launch_runs<4>(h, pivot); break;
-        case 5: rc = launch_runs<5>(h, pivot); break;
-        case 6: rc = launch_runs<6>(h, pivot); break;
-        case 7: rc = launch_runs<7>(h, pivot); break;
-        default: rc = launch_runs<8>(h, pivot); break;
-    }
+    rc = for_clusters(h->K, [&](auto k) { return launch_runs<k()>(h, pivot); });
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(run_perm_out, h->d_run_perm, (size_t)h->runs.count() * (size_t)h->K, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(agreement_out, h->d_agree, (size_t)h->runs.count() * (size_t)h->K * (size_t)h->K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));

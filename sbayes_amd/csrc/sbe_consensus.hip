@@ -1,7 +1,7 @@
 // sbe_consensus.hip -- posterior similarity of objects and the consensus clustering on the device (include/sbe_consensus.h):
-// the store of R runs of cluster samples in two forms, its pack kernels, the similarity kernel on the matrix pipe, the
-// score kernel and the comparison of two matrices.  The contract is tests/_consensus_oracle.py; DESIGN.md section 19 has
-// the layout, the structure of the kernels and the limits.
+// the store of R runs of cluster samples in two forms (the bit rows are sbe_unit.hip.h's bit store), the pack kernel of the
+// operand image, the similarity kernel on the matrix pipe, the score kernel and the comparison of two matrices.  The
+// contract is tests/_consensus_oracle.py; DESIGN.md section 19 has the layout, the structure of the kernels and the limits.
 //
 // With Z the 0/1 matrix of all cluster rows of the selected runs, [T K][N], the similarity counts are Z^T Z.
 // k_consensus_similarity computes one 32 x 32 tile of it per wave, for the tile pairs I <= J, as sbe_assoc.hip computes
@@ -46,7 +46,7 @@ constexpr int64_t kMaxLaunchTiles = (int64_t)1 << 16;
 constexpr int64_t kScoreUnitsPerLaunch = (int64_t)1 << 26;
 static_assert(kRoundElems == SBE_CONSENSUS_ROUND, "the header states the round length");
 
-// ---- pack 1: host bytes [n][K][N] (staging) -> the operand image of one run's segment ----------------------------------
+// ---- pack: host bytes [n][K][N] (staging) -> the operand image of one run's segment ----------------------------------
 // A thread owns one (object, dword): the elements [8 d, 8 d + 8) of the segment that this piece holds.  A piece may start
 // and end inside a dword; that dword then already holds the elements of the piece before (or zeros), which are kept.
 // blockIdx.x: four dwords from d_first on, blockIdx.y: 64 objects.
@@ -62,19 +62,6 @@ __global__ __launch_bounds__(kBlock) void k_consensus_pack(const uint8_t* rows, 
     uint32_t* out = reinterpret_cast<uint32_t*>(seg + (int64_t)n * stride) + d;
     if (hi - lo == 8) *out = bits;
     else *out |= bits;
-}
-
-// ---- pack 2: the same bytes -> bit words [n][K][W]; a wave takes 64 objects of one (row, cluster) ------------------------
-__global__ __launch_bounds__(kBlock) void k_consensus_pack_bits(const uint8_t* rows, int64_t n_lines, int N, int W, uint32_t* out, int64_t line0) {
-    const int64_t line = line0 + blockIdx.x;                   // row * K + cluster, within this piece
-    const int n = blockIdx.y * kBlock + threadIdx.x;
-    const bool bit = line < n_lines && n < N && rows[line * N + n] != 0;
-    const unsigned long long both = __ballot(bit);
-    const int w = n >> 5;
-    if ((threadIdx.x & 63) == 0 && line < n_lines) {
-        if (w < W) out[line * W + w] = (uint32_t)both;
-        if (w + 1 < W) out[line * W + w + 1] = (uint32_t)(both >> 32);
-    }
 }
 
 // ---- the similarity kernel ------------------------------------------------------------------------------------------
@@ -208,19 +195,13 @@ struct Slot {
 
 }  // namespace
 
-struct sbe_consensus : sbe_unit_handle {       // (sbe_unit.hip.h; ev: around the kernels of the last similarity, scores or compare)
-    unit_lanes runs;                    // (empty: no shape yet)
-    int K = 0;
-    int64_t N = 0, W = 0, seg_bytes = 0, stride = 0;
+struct sbe_consensus : sbe_unit_handle, unit_bit_store {   // (sbe_unit.hip.h; ev: around the kernels of the last similarity, scores or compare)
+    int64_t seg_bytes = 0, stride = 0;
     uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
     int64_t launch_tiles = 0;           // 0: the default
     Slot slot[2];
     uint8_t* d_img = nullptr;           // [32 W][n_runs][seg_bytes]
     size_t img_bytes = 0;
-    uint32_t* d_bits = nullptr;         // [n_runs][cap][K][W]
-    size_t bits_bytes = 0;
-    void* d_stage = nullptr;            // host rows in flight
-    size_t stage_bytes = 0;
     unsigned long long* d_score = nullptr;   // [cap]
     size_t score_bytes = 0;
     long long* d_cmp = nullptr;         // [2][N]
@@ -303,20 +284,16 @@ int sbe_consensus_reset(sbe_consensus* h, int n_runs, int n_clusters, int64_t n_
     ++h->version;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = unit_ensure(h, h->d_img, h->img_bytes, img);
-    if (!rc) rc = unit_ensure(h, h->d_bits, h->bits_bytes, (size_t)bytes - img);
+    if (!rc) rc = h->alloc_bits(h, n_runs, n_clusters, n_objects, capacity_rows);
     if (!rc) rc = unit_ensure(h, h->d_score, h->score_bytes, (size_t)capacity_rows * sizeof(unsigned long long));
     if (!rc) rc = unit_ensure(h, h->d_cmp, h->cmp_bytes, (size_t)2 * (size_t)n_objects * sizeof(long long));
     if (rc) return rc;
     // the image is zero wherever no element was appended: the padding of every segment and the objects behind N
     HIPCHK(h, hipMemsetAsync(h->d_img, 0, img, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->K = n_clusters;
-    h->N = n_objects;
-    h->W = W;
     h->seg_bytes = seg;
     h->stride = n_runs * seg;
-    h->runs.cap = capacity_rows;
-    h->runs.rows.assign((size_t)n_runs, 0);
+    h->set_shape(n_runs, n_clusters, n_objects, capacity_rows);
     return SBE_OK;
 }
 
@@ -341,31 +318,20 @@ int sbe_consensus_append_rows(sbe_consensus* h, int run, const uint8_t* rows, in
                     (long long)(q % h->N), (int)rows[q]);
     }
     HIPCHK(h, hipSetDevice(h->device));
-    const int64_t have = h->runs.rows[(size_t)run];
     uint8_t* seg = h->d_img + (int64_t)run * h->seg_bytes;
-    rc = unit_append_pieces(h, h->d_stage, h->stage_bytes, rows, n_rows, row_bytes, h->runs.cap, [&](int64_t k, int64_t r) {
+    rc = h->append_pieces(h, run, rows, n_rows, [&](int64_t k, int64_t row) {
         ++h->version;                                     // (the store changes from the first piece on)
-        const int64_t e0 = (have + r) * h->K, n_elems = k * h->K;
+        const int64_t e0 = row * h->K, n_elems = k * h->K;
         const int64_t d_first = e0 / 8, dwords = (e0 + n_elems - 1) / 8 - d_first + 1;
         k_consensus_pack<<<dim3((unsigned)div_up(dwords, kWaves), (unsigned)div_up(h->N, 64)), kBlock, 0, h->stream>>>(
             (const uint8_t*)h->d_stage, e0, n_elems, (int)h->N, seg, h->stride, d_first);
         HIPCHK(h, hipGetLastError());
-        uint32_t* out = h->d_bits + ((int64_t)run * h->runs.cap + have + r) * h->K * h->W;
-        return unit_for_grid_chunks(n_elems, [&](int64_t l0, int64_t n) {
-            k_consensus_pack_bits<<<dim3((unsigned)n, (unsigned)div_up(h->N, kBlock)), kBlock, 0, h->stream>>>((const uint8_t*)h->d_stage, n_elems,
-                                                                                                             (int)h->N, (int)h->W, out, l0);
-            HIPCHK(h, hipGetLastError());
-            return SBE_OK;
-        });
+        return SBE_OK;
     });
-    if (rc) {
-        // a piece may be in the image already while the run's row count is not: the next append would OR new elements onto
-        // it.  The store is unshaped instead (sbe_consensus_reset comes next), as after a failed allocation
-        h->runs.rows.clear();
-        return rc;
-    }
-    h->runs.rows[(size_t)run] = have + n_rows;
-    return SBE_OK;
+    // a piece may be in the image already while the run's row count is not: the next append would OR new elements onto
+    // it.  The store is unshaped instead (sbe_consensus_reset comes next), as after a failed allocation
+    if (rc) h->runs.rows.clear();
+    return rc;
 }
 
 int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot, int32_t* counts_out) {

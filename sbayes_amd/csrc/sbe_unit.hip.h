@@ -1,8 +1,8 @@
 #pragma once
-// sbe_unit.hip.h -- what the host code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_assoc.hip, sbe_geo.hip, sbe_diag.hip, sbe_align.hip, sbe_summary.hip, sbe_consensus.hip, sbe_compare.hip: each an opaque
+// sbe_unit.hip.h -- what the host code of the side units shares (every .hip file that includes this header: each an opaque
 // handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check,
 // create, destroy, device buffers that only grow, launches in grid chunks, the row store's lanes and its piece loop, the
-// timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes
+// bit store, the timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes
 // this header compiles no kernels but its own (the device side is sbe_unit_device.hip.h, taken from here for its launch
 // limit).  sbe_engine_internal.hip.h takes HIPCHK and div_up from here.  The helpers live in an unnamed namespace, as the
 // engine's do: every unit compiles its own copy.
@@ -219,6 +219,65 @@ struct unit_lanes {
         if (rows[(size_t)lane] + n_rows > cap)
             return fail(h, SBE_ERR_ARG, "store overflow: %s %d holds %lld rows, %lld more exceed the capacity of %lld rows", noun, lane,
                         (long long)rows[(size_t)lane], (long long)n_rows, (long long)cap);
+        return SBE_OK;
+    }
+};
+
+// A bit store: runs of cluster samples, host rows [n][K][N] of 0 / 1 bytes, held as bit words [runs][cap][K][W] with
+// W = ceil(N / 32).  A unit's handle derives from it beside sbe_unit_handle and lists d_bits and d_stage in its buffers().
+struct unit_bit_store {
+    unit_lanes runs;                    // (empty: no shape yet)
+    int K = 0;
+    int64_t N = 0, W = 0;
+    uint32_t* d_bits = nullptr;         // [runs][cap][K][W]
+    size_t bits_bytes = 0;
+    void* d_stage = nullptr;            // host rows in flight
+    size_t stage_bytes = 0;
+    static constexpr int kPackBlock = 256;
+
+    // d_bits for a shape; set_shape follows once the unit's other allocations stand
+    template <class H>
+    int alloc_bits(H* h, int n_runs, int n_clusters, int64_t n_objects, int64_t cap) {
+        return unit_ensure(h, d_bits, bits_bytes, (size_t)n_runs * (size_t)cap * (size_t)n_clusters * (size_t)((n_objects + 31) / 32) * sizeof(uint32_t));
+    }
+    void set_shape(int n_runs, int n_clusters, int64_t n_objects, int64_t cap) {
+        K = n_clusters;
+        N = n_objects;
+        W = (n_objects + 31) / 32;
+        runs.cap = cap;
+        runs.rows.assign((size_t)n_runs, 0);
+    }
+    uint32_t* at(int run, int64_t row) const { return d_bits + ((int64_t)run * runs.cap + row) * K * W; }
+
+    // The whole of <prefix>_append_rows: the argument checks, the handle's device, the pieces.
+    template <class H, class Hook>
+    int append(H* h, const char* noun, const char* reset, int run, const uint8_t* rows, int64_t n_rows, Hook before_piece) {
+        const int rc = runs.check_append(h, noun, reset, run, rows, n_rows);
+        if (rc || n_rows == 0) return rc;
+        HIPCHK(h, hipSetDevice(h->device));
+        return append_pieces(h, run, rows, n_rows, before_piece);
+    }
+
+    // ... its device part, for a unit that has work of its own between the two: the arguments have passed check_append,
+    // n_rows > 0 and the handle's device is current.  Per piece of the host rows the unit's before_piece(piece rows, the row
+    // of the run where the piece goes) -- the store changes from there on, and a non-zero code ends the call -- and the pack
+    // kernel; the run's row count moves once every piece is in.  What a failed piece leaves behind is the unit's to say.
+    template <class H, class Hook>
+    int append_pieces(H* h, int run, const uint8_t* rows, int64_t n_rows, Hook before_piece) {
+        const int64_t have = runs.rows[(size_t)run];
+        const int rc = unit_append_pieces(h, d_stage, stage_bytes, rows, n_rows, (int64_t)K * N, runs.cap, [&](int64_t k, int64_t r) {
+            if (const int hooked = before_piece(k, have + r)) return hooked;
+            const int64_t lines = k * K;
+            uint32_t* out = at(run, have + r);
+            return unit_for_grid_chunks(lines, [&](int64_t l0, int64_t n) {
+                k_unit_pack_bits<kPackBlock><<<dim3((unsigned)n, (unsigned)div_up(N, kPackBlock)), kPackBlock, 0, h->stream>>>((const uint8_t*)d_stage, lines,
+                                                                                                                             (int)N, (int)W, out, l0);
+                HIPCHK(h, hipGetLastError());
+                return SBE_OK;
+            });
+        });
+        if (rc) return rc;
+        runs.rows[(size_t)run] = have + n_rows;
         return SBE_OK;
     }
 };

@@ -1,8 +1,8 @@
 #pragma once
-// sbe_unit_device.hip.h -- what the device code of the side units shares (sbe_elpd.hip, sbe_em.hip, sbe_diag.hip,
-// sbe_summary.hip, sbe_align.hip, sbe_consensus.hip, sbe_compare.hip; sbe_unit.hip.h has the host side): the fixed-tree reductions, the 32 x 32 transpose that fills a row store and
-// the launch limits.  Device code only and nothing of the engine: a unit that includes this header compiles no kernels
-// but its own.  Everything lives in an unnamed namespace: every unit compiles its own copy.
+// sbe_unit_device.hip.h -- what the device code of the side units shares (sbe_unit.hip.h has the host side): the fixed-tree
+// reductions, the 32 x 32 transpose that fills a row store, the pack kernel that fills a bit store and the launch limits.
+// Device code only and nothing of the engine: a unit that includes this header compiles no kernels but its own and the
+// fill kernels it launches.  Everything lives in an unnamed namespace: every unit compiles its own copy.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -68,6 +68,22 @@ __global__ __launch_bounds__(256) void k_unit_transpose(const T* rows, int64_t n
     for (int c = ty; c < 32; c += 8) {
         const int64_t col = c0 + c, row = n0 + tx;
         if (row < n && col < C) store[col * cap + r0 + row] = tile[tx][c];
+    }
+}
+
+// ---- a bit store's fill: host bytes [n][K][N] (staging) -> bit words [n][K][W]; a wave takes 64 objects of one (row, cluster);
+// blockIdx.x + line0: the line, blockIdx.y: kBlock objects.  (A template, as the transpose is: only a unit that launches it
+// compiles it.)
+template <int kBlock>
+__global__ __launch_bounds__(kBlock) void k_unit_pack_bits(const uint8_t* rows, int64_t n_lines, int N, int W, uint32_t* out, int64_t line0) {
+    const int64_t line = line0 + blockIdx.x;                   // row * K + cluster, within this piece
+    const int n = blockIdx.y * kBlock + threadIdx.x;
+    const bool bit = line < n_lines && n < N && rows[line * N + n] != 0;
+    const unsigned long long both = __ballot(bit);
+    const int w = n >> 5;
+    if ((threadIdx.x & 63) == 0 && line < n_lines) {
+        if (w < W) out[line * W + w] = (uint32_t)both;
+        if (w + 1 < W) out[line * W + w + 1] = (uint32_t)(both >> 32);
     }
 }
 

@@ -45,12 +45,8 @@ PATHS = {0: "lds", 1: "global"}          # SBE_DIAG_PATH_*
 
 # name -> (restype, argtypes); mirrors include/sbe_diag.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
-    **_handle.unit_prototypes("sbe_diag"),
+    **_handle.store_prototypes("sbe_diag", [ct.c_int64, ct.c_int64]),
     "sbe_diag_lds_max_draws": (ct.c_int64, []),
-    "sbe_diag_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_diag_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_diag_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
-    "sbe_diag_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
     "sbe_diag_set_launch_columns": (ct.c_int, [c_handle_p, ct.c_int64]),
     "sbe_diag_compute": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int, ct.c_int64, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                     ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p]),
@@ -197,44 +193,49 @@ def _warn_cut(cut):
                       "(reported as DiagResult.cut; this warning is given once)", stacklevel=3)
 
 
-class DiagHandle(_handle.UnitHandle):
-    """Owner of one sbe_diag handle: the float64 store of several chains on one device, for callers who append rows as
-    they are logged.  last_kernel_ms(): the column kernel of the last compute call."""
-    _prefix, _noun = "sbe_diag", "a diagnostics handle"
+class ColumnStoreHandle(_handle.RowStoreHandle):
+    """Owner of a handle with the float64 store of several chains on one device (DiagHandle, SummaryHandle), for callers
+    who append rows as they are logged.  A subclass says who takes the chains in the messages (_takes) and gives its
+    module's load()."""
+    _lane, _takes = "chain", "the diagnostics take"
+    _load = staticmethod(load)
 
     def __init__(self, device=None):
         self.n_chains = self.n_columns = self.capacity = 0
-        self._create_on(load, device)
+        self._create_on(self._load, device)
 
     def reset(self, n_chains, n_columns, capacity):
         """Shape the store: n_chains empty chains of up to `capacity` rows of n_columns values."""
         n_chains, n_columns, capacity = int(n_chains), int(n_columns), int(capacity)
         if not 1 <= n_chains <= MAX_CHAINS:
-            raise ValueError(f"{n_chains} chains; the diagnostics take 1 .. {MAX_CHAINS}")
+            raise ValueError(f"{n_chains} chains; {self._takes} 1 .. {MAX_CHAINS}")
         if not 1 <= n_columns <= MAX_COLUMNS:
-            raise ValueError(f"{n_columns} columns; the diagnostics take 1 .. {MAX_COLUMNS}")
+            raise ValueError(f"{n_columns} columns; {self._takes} 1 .. {MAX_COLUMNS}")
         if capacity < 1:
             raise ValueError(f"capacity={capacity} must be positive")
         self.n_chains = self.n_columns = self.capacity = 0
-        self._check(self._lib.sbe_diag_reset(self._h, n_chains, n_columns, capacity))
+        self._check(self._fn("reset")(self._h, n_chains, n_columns, capacity))
         self.n_chains, self.n_columns, self.capacity = n_chains, n_columns, capacity
 
-    def rows(self, chain) -> int:
-        n = ct.c_int64(0)
-        self._check(self._lib.sbe_diag_rows(self._h, int(chain), ct.byref(n)))
-        return n.value
+    def _lane_count(self):
+        return self.n_chains
 
     def append(self, chain, rows):
         """Append rows ([n, n_columns], or one row [n_columns]) to a chain."""
-        chain = int(chain)
-        if not 0 <= chain < self.n_chains:
-            raise ValueError(f"chain {chain} out of range [0, {self.n_chains})")
+        chain = self._check_lane(chain)
         block = _check_rows(rows, self.n_columns)
-        self._check(self._lib.sbe_diag_append_rows(self._h, chain, _ptr(block), block.shape[0]))
+        self._check(self._append_rows(chain, block))
 
     def set_launch_columns(self, columns):
-        """Columns per launch of the column kernel (0: the default).  Results do not depend on it."""
-        self._check(self._lib.sbe_diag_set_launch_columns(self._h, int(columns)))
+        """Columns per launch of the handle's first kernel (0: the default): the column kernel of the diagnostics, the rank
+        kernel of the summary (whose default comes from the scratch budget).  Results do not depend on it."""
+        self._check(self._fn("set_launch_columns")(self._h, int(columns)))
+
+
+class DiagHandle(ColumnStoreHandle):
+    """Owner of one sbe_diag handle: the float64 store of several chains on one device, for callers who append rows as
+    they are logged.  last_kernel_ms(): the column kernel of the last compute call."""
+    _prefix, _noun = "sbe_diag", "a diagnostics handle"
 
     def last_shape(self):
         """(M, n, path, launches) of the last compute call."""
@@ -267,11 +268,8 @@ def convergence(chains, burnin=0.1, split=True, max_lag=0, names=None, device=No
     names = _check_names(names, p)
     _plan(lengths, burnin, split)                                          # (refuses before the device is touched)
     blocks = [_check_rows(c) for c in chains]
-    h = DiagHandle(device)
+    h = DiagHandle.filled(device, (len(blocks), p, max(lengths)), blocks)
     try:
-        h.reset(len(blocks), p, max(lengths))
-        for c, block in enumerate(blocks):
-            h.append(c, block)
         return h.compute(burnin=burnin, split=split, max_lag=max_lag, names=names)
     finally:
         h.close()

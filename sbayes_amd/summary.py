@@ -46,11 +46,7 @@ DEFAULT_HDI_PROB = 0.94
 
 # name -> (restype, argtypes); mirrors include/sbe_summary.h one to one
 PROTOTYPES = {
-    **_handle.unit_prototypes("sbe_summary"),            # (last_kernel_ms fills float [2]: the rank kernel, the column passes)
-    "sbe_summary_create": (ct.c_int, [ct.POINTER(c_handle_p), ct.c_int]),
-    "sbe_summary_reset": (ct.c_int, [c_handle_p, ct.c_int, ct.c_int64, ct.c_int64]),
-    "sbe_summary_append_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.c_void_p, ct.c_int64]),
-    "sbe_summary_rows": (ct.c_int, [c_handle_p, ct.c_int, ct.POINTER(ct.c_int64)]),
+    **_handle.store_prototypes("sbe_summary", [ct.c_int64, ct.c_int64]),    # (last_kernel_ms fills float [2]: rank kernel, column passes)
     "sbe_summary_set_launch_columns": (ct.c_int, [c_handle_p, ct.c_int64]),
     "sbe_summary_compute": (ct.c_int, [c_handle_p, ct.c_void_p, ct.c_int, ct.c_int64, ct.c_int, ct.c_void_p, ct.c_double] + [ct.c_void_p] * 13),
     "sbe_summary_last_shape": (ct.c_int, [c_handle_p, ct.POINTER(ct.c_int), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int),
@@ -135,44 +131,11 @@ def _check_hdi_prob(hdi_prob):
     return hdi_prob
 
 
-class SummaryHandle(_handle.UnitHandle):
+class SummaryHandle(diag.ColumnStoreHandle):
     """Owner of one sbe_summary handle: the float64 store of several chains on one device, for callers who append rows as
     they are logged.  last_kernel_ms(): the rank kernel and the column passes of the last compute call, added."""
-    _prefix, _noun = "sbe_summary", "a summary handle"
-
-    def __init__(self, device=None):
-        self.n_chains = self.n_columns = self.capacity = 0
-        self._create_on(load, device)
-
-    def reset(self, n_chains, n_columns, capacity):
-        """Shape the store: n_chains empty chains of up to `capacity` rows of n_columns values."""
-        n_chains, n_columns, capacity = int(n_chains), int(n_columns), int(capacity)
-        if not 1 <= n_chains <= MAX_CHAINS:
-            raise ValueError(f"{n_chains} chains; the summary takes 1 .. {MAX_CHAINS}")
-        if not 1 <= n_columns <= MAX_COLUMNS:
-            raise ValueError(f"{n_columns} columns; the summary takes 1 .. {MAX_COLUMNS}")
-        if capacity < 1:
-            raise ValueError(f"capacity={capacity} must be positive")
-        self.n_chains = self.n_columns = self.capacity = 0
-        self._check(self._lib.sbe_summary_reset(self._h, n_chains, n_columns, capacity))
-        self.n_chains, self.n_columns, self.capacity = n_chains, n_columns, capacity
-
-    def rows(self, chain) -> int:
-        n = ct.c_int64(0)
-        self._check(self._lib.sbe_summary_rows(self._h, int(chain), ct.byref(n)))
-        return n.value
-
-    def append(self, chain, rows):
-        """Append rows ([n, n_columns], or one row [n_columns]) to a chain."""
-        chain = int(chain)
-        if not 0 <= chain < self.n_chains:
-            raise ValueError(f"chain {chain} out of range [0, {self.n_chains})")
-        block = diag._check_rows(rows, self.n_columns)
-        self._check(self._lib.sbe_summary_append_rows(self._h, chain, _ptr(block), block.shape[0]))
-
-    def set_launch_columns(self, columns):
-        """Columns per launch of the rank kernel (0: the default, from the scratch budget).  Results do not depend on it."""
-        self._check(self._lib.sbe_summary_set_launch_columns(self._h, int(columns)))
+    _prefix, _noun, _takes = "sbe_summary", "a summary handle", "the summary takes"
+    _load = staticmethod(load)
 
     def last_shape(self):
         """(M, n, path, launches of the rank kernel, columns of each) of the last compute call."""
@@ -236,11 +199,8 @@ def summarize(chains, burnin=0.1, split=True, max_lag=0, probs=DEFAULT_PROBS, hd
     names = diag._check_names(names, p)
     diag._plan(lengths, burnin, split)                                     # (refuses before the device is touched)
     blocks = [diag._check_rows(c) for c in chains]
-    h = SummaryHandle(device)
+    h = SummaryHandle.filled(device, (len(blocks), p, max(lengths)), blocks)
     try:
-        h.reset(len(blocks), p, max(lengths))
-        for c, block in enumerate(blocks):
-            h.append(c, block)
         return h.compute(burnin=burnin, split=split, max_lag=max_lag, probs=probs, hdi_prob=hdi_prob, names=names)
     finally:
         h.close()

@@ -1,40 +1,31 @@
 """CPU checks of the alignment boundary (include/sbe_align.h, sbayes_amd/align.py): the symbols are exported and bound by
 the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, align
-from tests._abi_header import declared, macro
+from sbayes_amd import align
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_align.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = align.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_align.h but not exported"
-    assert sorted(align.PROTOTYPES) == names
-    assert lib.sbe_align_abi_version() == align.ABI_VERSION == 1
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(align, HEADER, 12)
+    assert align.ABI_VERSION == 1
 
 
 def test_limits_agree_with_the_header():
-    assert macro(HEADER, "SBE_ALIGN_MAX_CLUSTERS") == str(align.MAX_CLUSTERS) == "8"
-    assert macro(HEADER, "SBE_ALIGN_MAX_RUNS") == str(align.MAX_RUNS) == "64"
-    assert macro(HEADER, "SBE_ALIGN_MAX_ROWS") == "(1 << 20)" and align.MAX_ROWS == 1 << 20
-    assert macro(HEADER, "SBE_ALIGN_MAX_SEED_ROWS") == str(align.MAX_SEED_ROWS) == "1024"
-    assert macro(HEADER, "SBE_ALIGN_LDS_BYTES") == "(160 * 1024)" and align.LDS_BYTES == 160 * 1024
-    assert macro(HEADER, "SBE_ALIGN_STATIC_LDS") == str(align.STATIC_LDS)
+    assert abi.macro(HEADER, "SBE_ALIGN_MAX_CLUSTERS") == str(align.MAX_CLUSTERS) == "8"
+    assert abi.macro(HEADER, "SBE_ALIGN_MAX_RUNS") == str(align.MAX_RUNS) == "64"
+    assert abi.macro(HEADER, "SBE_ALIGN_MAX_ROWS") == "(1 << 20)" and align.MAX_ROWS == 1 << 20
+    assert abi.macro(HEADER, "SBE_ALIGN_MAX_SEED_ROWS") == str(align.MAX_SEED_ROWS) == "1024"
+    assert abi.macro(HEADER, "SBE_ALIGN_LDS_BYTES") == "(160 * 1024)" and align.LDS_BYTES == 160 * 1024
+    assert abi.macro(HEADER, "SBE_ALIGN_STATIC_LDS") == str(align.STATIC_LDS)
     assert max(align.MAX_SEED_ROWS, 1) * align.MAX_ROWS + align.MAX_SEED_ROWS < 2 ** 31      # the int32 running sums
     lib = align.load()
     for k in range(1, 9):
@@ -53,12 +44,7 @@ def test_limits_agree_with_the_header():
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """align.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(align))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(align)
 
 
 @pytest.fixture
@@ -103,30 +89,11 @@ def test_the_one_run_forms_refuse_before_the_device(no_device):
 
 
 def test_c_abi_validates_before_the_device():
-    lib = align.load()
-    h = ct.c_void_p()
-    assert lib.sbe_align_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_align_last_error(None)
-    assert lib.sbe_align_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_align_last_error(None)
-    assert lib.sbe_align_reset(None, 1, 1, 1, 1) == 1
-    assert b"null handle" in lib.sbe_align_last_error(None)
-    assert lib.sbe_align_append_rows(None, 0, None, 0) == 1
-    n = ct.c_int64()
-    assert lib.sbe_align_rows(None, 0, ct.byref(n)) == 1
-    assert lib.sbe_align_within(None, 0, None) == 1
-    assert lib.sbe_align_counts(None, 1, None, None) == 1
-    assert lib.sbe_align_runs(None, 0, 1, None, None, None) == 1
-    assert lib.sbe_align_destroy(None) == 1
-    ms = ct.c_float()
-    assert lib.sbe_align_last_kernel_ms(None, ct.byref(ms)) == 1
+    assert sorted(abi.check_null_handles(align)) == sorted(set(align.PROTOTYPES) - {"sbe_align_abi_version", "sbe_align_last_error", "sbe_align_max_objects"})
 
 
 def test_handles_are_not_picklable():
-    h = object.__new__(align.AlignHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError, match="not picklable"):
-        pickle.dumps(h)
+    abi.check_not_picklable(align.AlignHandle)
 
 
 def test_a_handle_checks_its_own_arguments_before_the_library():

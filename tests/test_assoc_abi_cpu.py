@@ -1,46 +1,31 @@
 """CPU checks of the feature-screening boundary (include/sbe_assoc.h, sbayes_amd/assoc.py): the symbols are exported and
 bound by the module's own prototype table, and bad arguments are refused before the device is touched."""
-import ast
-import ctypes as ct
-import inspect
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, assoc
-from tests._abi_header import declared, macro
+from sbayes_amd import assoc
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_assoc.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = assoc.load()
-    names = declared(HEADER)
-    assert len(names) == 9
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_assoc.h but not exported"
-    assert sorted(assoc.PROTOTYPES) == names
-    assert lib.sbe_assoc_abi_version() == assoc.ABI_VERSION
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(assoc, HEADER, 9)
 
 
 def test_limits_agree_with_the_header():
-    assert macro(HEADER, "SBE_ASSOC_NA") == str(assoc.NA)
-    assert macro(HEADER, "SBE_ASSOC_MAX_OBJECTS") == "(1 << 24)" and assoc.MAX_OBJECTS == 1 << 24
-    assert macro(HEADER, "SBE_ASSOC_MAX_STATES") == str(assoc.MAX_STATES)
-    assert macro(HEADER, "SBE_ASSOC_MAX_FEATURES") == str(assoc.MAX_FEATURES)
-    assert macro(HEADER, "SBE_ASSOC_MAX_CODES") == "((int64_t)1 << 31)" and assoc.MAX_CODES == 1 << 31
+    assert abi.macro(HEADER, "SBE_ASSOC_NA") == str(assoc.NA)
+    assert abi.macro(HEADER, "SBE_ASSOC_MAX_OBJECTS") == "(1 << 24)" and assoc.MAX_OBJECTS == 1 << 24
+    assert abi.macro(HEADER, "SBE_ASSOC_MAX_STATES") == str(assoc.MAX_STATES)
+    assert abi.macro(HEADER, "SBE_ASSOC_MAX_FEATURES") == str(assoc.MAX_FEATURES)
+    assert abi.macro(HEADER, "SBE_ASSOC_MAX_CODES") == "((int64_t)1 << 31)" and assoc.MAX_CODES == 1 << 31
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """assoc.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(assoc))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(assoc)
 
 
 @pytest.fixture
@@ -85,19 +70,7 @@ def test_one_hot_features_become_codes():
 
 
 def test_c_abi_validates_before_the_device():
-    lib = assoc.load()
-    h = ct.c_void_p()
-    assert lib.sbe_assoc_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_assoc_last_error(None)
-    assert lib.sbe_assoc_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_assoc_last_error(None)
-    assert lib.sbe_assoc_compute(None, None, 1, 1, None, None, None, None, None, None) == 1
-    assert b"null handle" in lib.sbe_assoc_last_error(None)
-    assert lib.sbe_assoc_tables(None, None, 0, None) == 1
-    assert lib.sbe_assoc_destroy(None) == 1
-    assert lib.sbe_assoc_set_launch_tiles(None, 4) == 1
-    ms = ct.c_float()
-    assert lib.sbe_assoc_last_kernel_ms(None, ct.byref(ms)) == 1
+    assert sorted(abi.check_null_handles(assoc)) == sorted(set(assoc.PROTOTYPES) - {"sbe_assoc_abi_version", "sbe_assoc_last_error"})
 
 
 def test_frame_codes_number_states_in_sorted_order():
@@ -122,11 +95,7 @@ def test_csv_needs_the_metadata_columns(tmp_path):
 
 
 def test_handles_are_not_picklable_and_results_sort_like_the_tool():
-    import pickle
-    h = object.__new__(assoc.AssocHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError):
-        pickle.dumps(h)
+    abi.check_not_picklable(assoc.AssocHandle)
     p = np.array([[np.nan, 1e-9, 0.5], [1e-9, np.nan, 1e-12], [0.5, 1e-12, np.nan]])
     valid = ~np.isnan(p)
     res = assoc.AssociationResult(np.zeros((3, 3)), p, np.ones((3, 3), np.int32), np.ones((3, 3), np.int32), valid,

@@ -1,43 +1,33 @@
 """CPU checks of the model comparison's boundary (include/sbe_compare.h, sbayes_amd/compare.py): the symbols are exported and
 bound by the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, compare, elpd
-from tests._abi_header import declared, macro
+from sbayes_amd import compare, elpd
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_compare.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = compare.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_compare.h but not exported"
-    assert sorted(compare.PROTOTYPES) == names
-    assert lib.sbe_compare_abi_version() == compare.ABI_VERSION == int(macro(HEADER, "SBE_COMPARE_ABI_VERSION"))
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(compare, HEADER, 12)
 
 
 def test_limits_agree_with_the_header():
-    assert macro(HEADER, "SBE_COMPARE_MAX_MODELS") == str(compare.MAX_MODELS) == "32"
-    assert macro(HEADER, "SBE_COMPARE_MAX_POINTS") == "(1 << 24)" and compare.MAX_POINTS == 1 << 24
-    assert macro(HEADER, "SBE_COMPARE_MAX_REPLICATES") == "(1 << 16)" and compare.MAX_REPLICATES == 1 << 16
-    assert macro(HEADER, "SBE_COMPARE_MAX_IMAGE_BYTES") == "(1ll << 32)" and compare.MAX_IMAGE_BYTES == 1 << 32
-    assert macro(HEADER, "SBE_COMPARE_BLOCK") == str(compare.BLOCK) == "256"
-    assert macro(HEADER, "SBE_COMPARE_CHUNK") == str(compare.CHUNK) == "4096"
-    assert macro(HEADER, "SBE_COMPARE_RUN") == str(compare.RUN) == "1024"
-    assert macro(HEADER, "SBE_COMPARE_BOOT_CHUNK") == str(compare.BOOT_CHUNK) == "1024"
-    assert macro(HEADER, "SBE_COMPARE_CHECK_EVERY") == str(compare.CHECK_EVERY) == "32"
+    assert abi.macro(HEADER, "SBE_COMPARE_MAX_MODELS") == str(compare.MAX_MODELS) == "32"
+    assert abi.macro(HEADER, "SBE_COMPARE_MAX_POINTS") == "(1 << 24)" and compare.MAX_POINTS == 1 << 24
+    assert abi.macro(HEADER, "SBE_COMPARE_MAX_REPLICATES") == "(1 << 16)" and compare.MAX_REPLICATES == 1 << 16
+    assert abi.macro(HEADER, "SBE_COMPARE_MAX_IMAGE_BYTES") == "(1ll << 32)" and compare.MAX_IMAGE_BYTES == 1 << 32
+    assert abi.macro(HEADER, "SBE_COMPARE_BLOCK") == str(compare.BLOCK) == "256"
+    assert abi.macro(HEADER, "SBE_COMPARE_CHUNK") == str(compare.CHUNK) == "4096"
+    assert abi.macro(HEADER, "SBE_COMPARE_RUN") == str(compare.RUN) == "1024"
+    assert abi.macro(HEADER, "SBE_COMPARE_BOOT_CHUNK") == str(compare.BOOT_CHUNK) == "1024"
+    assert abi.macro(HEADER, "SBE_COMPARE_CHECK_EVERY") == str(compare.CHECK_EVERY) == "32"
     # the summation rule: a thread adds CHUNK / BLOCK terms, a bootstrap lane BOOT_CHUNK, a lane of the second kernels at most
     # MAX_POINTS / CHUNK / 64 chunk partials, a thread of the bootstrap's column sums MAX_REPLICATES / BLOCK
     assert compare.CHUNK % compare.BLOCK == 0 and compare.CHUNK // compare.BLOCK <= compare.RUN and compare.BOOT_CHUNK <= compare.RUN
@@ -52,11 +42,7 @@ def test_limits_agree_with_the_header():
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """compare.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(compare))
-    calls = [n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"]
-    bad = [(n.lineno, ast.unparse(n)) for n in calls if len(n.args) != 1 or not isinstance(n.args[0], ast.Name)]
-    assert calls and not bad, bad
+    abi.check_ptr_arguments(compare)
 
 
 @pytest.fixture
@@ -131,27 +117,11 @@ def test_the_kind_the_p_column_and_the_warnings_are_read_from_the_results():
 
 
 def test_c_abi_validates_before_the_device():
-    lib = compare.load()
-    h = ct.c_void_p()
-    assert lib.sbe_compare_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_compare_last_error(None)
-    assert lib.sbe_compare_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_compare_last_error(None)
-    gap, updates, ms = ct.c_double(), ct.c_int64(), ct.c_float()
-    for call in (lambda: lib.sbe_compare_reset(None, 1, 1), lambda: lib.sbe_compare_set_model(None, 0, None),
-                 lambda: lib.sbe_compare_totals(None, None, None), lambda: lib.sbe_compare_differences(None, 0, None, None),
-                 lambda: lib.sbe_compare_stacking(None, 1e-8, 10, None, ct.byref(gap), ct.byref(updates)),
-                 lambda: lib.sbe_compare_bootstrap(None, 0, 10, None, None, None), lambda: lib.sbe_compare_set_bootstrap_batch(None, 64),
-                 lambda: lib.sbe_compare_destroy(None), lambda: lib.sbe_compare_last_kernel_ms(None, ct.byref(ms))):
-        assert call() == 1
-        assert b"null handle" in lib.sbe_compare_last_error(None)
+    assert sorted(abi.check_null_handles(compare)) == sorted(set(compare.PROTOTYPES) - {"sbe_compare_abi_version", "sbe_compare_last_error"})
 
 
 def test_handles_are_not_picklable():
-    h = object.__new__(compare.CompareHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError, match="not picklable"):
-        pickle.dumps(h)
+    abi.check_not_picklable(compare.CompareHandle)
 
 
 def test_a_handle_checks_its_own_arguments_before_the_library():

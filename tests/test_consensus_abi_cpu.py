@@ -1,41 +1,31 @@
 """CPU checks of the consensus boundary (include/sbe_consensus.h, sbayes_amd/consensus.py): the symbols are exported and
 bound by the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, align, consensus
-from tests._abi_header import declared, macro
+from sbayes_amd import align, consensus
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_consensus.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = consensus.load()
-    names = declared(HEADER)
-    assert len(names) == 13
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_consensus.h but not exported"
-    assert sorted(consensus.PROTOTYPES) == names
-    assert lib.sbe_consensus_abi_version() == consensus.ABI_VERSION == int(macro(HEADER, "SBE_CONSENSUS_ABI_VERSION"))
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(consensus, HEADER, 13)
 
 
 def test_limits_agree_with_the_header():
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_CLUSTERS") == str(consensus.MAX_CLUSTERS) == "8"
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_OBJECTS") == str(consensus.MAX_OBJECTS) == "16384"
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_RUNS") == str(consensus.MAX_RUNS) == "64"
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_ROWS") == "(1 << 20)" and consensus.MAX_ROWS == 1 << 20
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_ELEMENTS") == "(1 << 24)" and consensus.MAX_ELEMENTS == 1 << 24
-    assert macro(HEADER, "SBE_CONSENSUS_ROUND") == str(consensus.ROUND) == "256"
-    assert macro(HEADER, "SBE_CONSENSUS_MAX_IMAGE_BYTES") == "(1ll << 34)" and consensus.MAX_IMAGE_BYTES == 1 << 34
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_CLUSTERS") == str(consensus.MAX_CLUSTERS) == "8"
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_OBJECTS") == str(consensus.MAX_OBJECTS) == "16384"
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_RUNS") == str(consensus.MAX_RUNS) == "64"
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_ROWS") == "(1 << 20)" and consensus.MAX_ROWS == 1 << 20
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_ELEMENTS") == "(1 << 24)" and consensus.MAX_ELEMENTS == 1 << 24
+    assert abi.macro(HEADER, "SBE_CONSENSUS_ROUND") == str(consensus.ROUND) == "256"
+    assert abi.macro(HEADER, "SBE_CONSENSUS_MAX_IMAGE_BYTES") == "(1ll << 34)" and consensus.MAX_IMAGE_BYTES == 1 << 34
     assert consensus.MAX_OBJECTS ** 2 * 4 == 1 << 30 and consensus.MAX_OBJECTS <= 1 << 16      # one matrix; a member index in 16 bits
     assert consensus.MAX_OBJECTS * consensus.MAX_ELEMENTS ** 2 < 2 ** 63                        # a row sum of the comparison
     assert consensus.MAX_ELEMENTS * consensus.MAX_OBJECTS ** 2 < 2 ** 63                        # K T m^2 of a score
@@ -52,12 +42,7 @@ def test_limits_agree_with_the_header():
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """consensus.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(consensus))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(consensus)
 
 
 @pytest.fixture
@@ -114,32 +99,11 @@ def test_shapes_beyond_the_limits_are_refused_before_the_device(no_device, monke
 
 
 def test_c_abi_validates_before_the_device():
-    lib = consensus.load()
-    h = ct.c_void_p()
-    assert lib.sbe_consensus_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_consensus_last_error(None)
-    assert lib.sbe_consensus_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_consensus_last_error(None)
-    assert lib.sbe_consensus_reset(None, 1, 1, 1, 1) == 1
-    assert b"null handle" in lib.sbe_consensus_last_error(None)
-    assert lib.sbe_consensus_append_rows(None, 0, None, 0) == 1
-    n = ct.c_int64()
-    assert lib.sbe_consensus_rows(None, 0, ct.byref(n)) == 1
-    assert lib.sbe_consensus_similarity(None, None, 0, None) == 1
-    assert lib.sbe_consensus_scores(None, 0, 0, None) == 1
-    assert lib.sbe_consensus_compare(None, None, None) == 1
-    assert lib.sbe_consensus_set_launch_tiles(None, 1) == 1
-    assert lib.sbe_consensus_destroy(None) == 1
-    ms = ct.c_float()
-    assert lib.sbe_consensus_last_kernel_ms(None, ct.byref(ms)) == 1
-    assert b"null handle" in lib.sbe_consensus_last_error(None)
+    assert sorted(abi.check_null_handles(consensus)) == sorted(set(consensus.PROTOTYPES) - {"sbe_consensus_abi_version", "sbe_consensus_last_error", "sbe_consensus_image_bytes"})
 
 
 def test_handles_are_not_picklable():
-    h = object.__new__(consensus.ConsensusHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError, match="not picklable"):
-        pickle.dumps(h)
+    abi.check_not_picklable(consensus.ConsensusHandle)
 
 
 def test_a_handle_checks_its_own_arguments_before_the_library():

@@ -1,53 +1,38 @@
 """CPU checks of the diagnostics boundary (include/sbe_diag.h, sbayes_amd/diag.py): the symbols are exported and bound by
 the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, diag
-from tests._abi_header import declared, macro
+from sbayes_amd import diag
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_diag.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = diag.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_diag.h but not exported"
-    assert sorted(diag.PROTOTYPES) == names
-    assert lib.sbe_diag_abi_version() == diag.ABI_VERSION
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(diag, HEADER, 12)
 
 
 def test_limits_and_codes_agree_with_the_header():
-    assert macro(HEADER, "SBE_DIAG_MAX_CHAINS") == str(diag.MAX_CHAINS) == "64"
-    assert macro(HEADER, "SBE_DIAG_MIN_DRAWS") == str(diag.MIN_DRAWS) == "4"
-    assert macro(HEADER, "SBE_DIAG_MAX_DRAWS") == "(1 << 20)" and diag.MAX_DRAWS == 1 << 20
+    assert abi.macro(HEADER, "SBE_DIAG_MAX_CHAINS") == str(diag.MAX_CHAINS) == "64"
+    assert abi.macro(HEADER, "SBE_DIAG_MIN_DRAWS") == str(diag.MIN_DRAWS) == "4"
+    assert abi.macro(HEADER, "SBE_DIAG_MAX_DRAWS") == "(1 << 20)" and diag.MAX_DRAWS == 1 << 20
     assert diag.MAX_COLUMNS == 2 ** 31 - 1
-    assert (macro(HEADER, "SBE_DIAG_FLAG_CONSTANT"), macro(HEADER, "SBE_DIAG_FLAG_NONFINITE"), macro(HEADER, "SBE_DIAG_FLAG_TRUNCATED")) == \
+    assert (abi.macro(HEADER, "SBE_DIAG_FLAG_CONSTANT"), abi.macro(HEADER, "SBE_DIAG_FLAG_NONFINITE"), abi.macro(HEADER, "SBE_DIAG_FLAG_TRUNCATED")) == \
         (str(diag.FLAG_CONSTANT), str(diag.FLAG_NONFINITE), str(diag.FLAG_TRUNCATED))
-    assert {int(macro(HEADER, "SBE_DIAG_PATH_LDS")): "lds", int(macro(HEADER, "SBE_DIAG_PATH_GLOBAL")): "global"} == diag.PATHS
+    assert {int(abi.macro(HEADER, "SBE_DIAG_PATH_LDS")): "lds", int(abi.macro(HEADER, "SBE_DIAG_PATH_GLOBAL")): "global"} == diag.PATHS
     # the staged column, the rho_t entries kept in LDS and the kernel's static LDS fit the 160 KiB of a CU
     limit = diag.lds_max_draws()
     assert 8192 <= limit and (limit + 2048) * 8 + 4096 <= 160 * 1024 < (limit + 1 + 2048) * 8 + 4096
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """diag.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(diag))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(diag)
 
 
 @pytest.fixture
@@ -98,32 +83,12 @@ def test_plan_follows_drop_burnin_cut_and_split():
 
 
 def test_c_abi_validates_before_the_device():
-    lib = diag.load()
-    h = ct.c_void_p()
-    assert lib.sbe_diag_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_diag_last_error(None)
-    assert lib.sbe_diag_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_diag_last_error(None)
-    assert lib.sbe_diag_reset(None, 1, 1, 1) == 1
-    assert b"null handle" in lib.sbe_diag_last_error(None)
-    assert lib.sbe_diag_append_rows(None, 0, None, 0) == 1
-    n = ct.c_int64()
-    assert lib.sbe_diag_rows(None, 0, ct.byref(n)) == 1
-    assert lib.sbe_diag_set_launch_columns(None, 4) == 1
-    assert lib.sbe_diag_compute(None, None, 1, 0, None, None, None, None, None, None, None) == 1
-    m, path = ct.c_int(), ct.c_int()
-    assert lib.sbe_diag_last_shape(None, ct.byref(m), ct.byref(n), ct.byref(path), ct.byref(n)) == 1
-    assert lib.sbe_diag_destroy(None) == 1
-    ms = ct.c_float()
-    assert lib.sbe_diag_last_kernel_ms(None, ct.byref(ms)) == 1
-    assert lib.sbe_diag_lds_max_draws() == diag.lds_max_draws()
+    assert sorted(abi.check_null_handles(diag)) == sorted(set(diag.PROTOTYPES) - {"sbe_diag_abi_version", "sbe_diag_last_error", "sbe_diag_lds_max_draws"})
+    assert diag.load().sbe_diag_lds_max_draws() == diag.lds_max_draws()
 
 
 def test_handles_are_not_picklable():
-    h = object.__new__(diag.DiagHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError, match="not picklable"):
-        pickle.dumps(h)
+    abi.check_not_picklable(diag.DiagHandle)
 
 
 def test_a_handle_checks_its_own_arguments_before_the_library():

@@ -1,38 +1,24 @@
 """CPU checks of the ELPD boundary (include/sbe_elpd.h, sbayes_amd/elpd.py): the symbols are exported and bound by the
 module's own prototype table, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, elpd
-from tests._abi_header import declared
+from sbayes_amd import elpd
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_elpd.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = elpd.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_elpd.h but not exported"
-    assert sorted(elpd.PROTOTYPES) == names
-    assert lib.sbe_elpd_abi_version() == elpd.ABI_VERSION
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(elpd, HEADER, 12)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """elpd.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(elpd))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(elpd)
 
 
 def test_lds_threshold_is_within_the_budget():
@@ -84,10 +70,7 @@ def test_c_abi_validates_before_the_device():
     assert b"n_columns=0" in lib.sbe_elpd_last_error(None)
     assert lib.sbe_elpd_create(ct.byref(h), 0, 5, 0) == 1
     assert b"capacity=0" in lib.sbe_elpd_last_error(None)
-    assert lib.sbe_elpd_append_rows(None, None, 1) == 1
-    assert b"null store" in lib.sbe_elpd_last_error(None)
-    out = ct.c_int64()
-    assert lib.sbe_elpd_compute(None, 0, None, 0, None, None, None, None, ct.byref(out)) == 1
+    assert sorted(abi.check_null_handles(elpd, b"null store")) == sorted(set(elpd.PROTOTYPES) - {"sbe_elpd_abi_version", "sbe_elpd_last_error", "sbe_elpd_create", "sbe_elpd_lds_max_samples"})
 
 
 def test_log_capacity_must_be_positive():

@@ -1,33 +1,24 @@
 """CPU checks of the EM initializer's boundary (include/sbe_em.h, sbayes_amd/em.py): the symbols are exported and bound
 by the module's own prototype table, and bad shapes, limits and data are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, em
-from tests._abi_header import declared, macro
+from sbayes_amd import em
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_em.h").read_text()
 
 
 def _header_define(name):
-    return eval(macro(HEADER, name).replace("(int64_t)", ""))
+    return eval(abi.macro(HEADER, name).replace("(int64_t)", ""))
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = em.load()
-    names = declared(HEADER)
-    assert len(names) == 7
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_em.h but not exported"
-    assert sorted(em.PROTOTYPES) == names
-    assert lib.sbe_em_abi_version() == em.ABI_VERSION
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(em, HEADER, 7)
 
 
 def test_python_limits_are_the_header_limits():
@@ -39,12 +30,7 @@ def test_python_limits_are_the_header_limits():
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """em.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(em))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(em)
 
 
 def _data(n=6, f=3, s=4, g=3, k=2):
@@ -108,12 +94,7 @@ def test_c_abi_null_handles_and_pointers():
     h = ct.c_void_p()
     assert lib.sbe_em_create(ct.byref(h), 0, 4, 2, 2, None, None, 1, 1, None) == 1
     assert b"null pointer argument: data" in lib.sbe_em_last_error(None)
-    assert lib.sbe_em_run(None, None, 1, None, None) == 1
-    assert b"null EM handle" in lib.sbe_em_last_error(None)
-    assert lib.sbe_em_set_geo_cost(None, None, 1.0) == 1
-    assert lib.sbe_em_destroy(None) == 1
-    ms = ct.c_float()
-    assert lib.sbe_em_last_kernel_ms(None, ct.byref(ms)) == 1
+    assert sorted(abi.check_null_handles(em, b"null EM handle")) == ["sbe_em_destroy", "sbe_em_last_kernel_ms", "sbe_em_run", "sbe_em_set_geo_cost"]
 
 
 @pytest.fixture

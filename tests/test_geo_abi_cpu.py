@@ -1,52 +1,37 @@
 """CPU checks of the geo-prior boundary (include/sbe_geo.h, sbayes_amd/geo.py): the symbols are exported and bound by the
 module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, geo
-from tests._abi_header import declared, macro
+from sbayes_amd import geo
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_geo.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = geo.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_geo.h but not exported"
-    assert sorted(geo.PROTOTYPES) == names
-    assert lib.sbe_geo_abi_version() == geo.ABI_VERSION
-    assert not set(names) & set(_lib.PROTOTYPES)          # the engine's table is not extended
+    abi.check_symbols(geo, HEADER, 12)
 
 
 def test_limits_and_codes_agree_with_the_header():
-    assert macro(HEADER, "SBE_GEO_MAX_OBJECTS") == str(geo.MAX_OBJECTS)
-    assert macro(HEADER, "SBE_GEO_MAX_MASKS") == "(1 << 20)" and geo.MAX_MASKS == 1 << 20
-    assert macro(HEADER, "SBE_GEO_MAX_LAUNCH_MASKS") == "(1 << 16)" and geo.MAX_LAUNCH_MASKS == 1 << 16
-    assert macro(HEADER, "SBE_GEO_LDS_MEMBERS") == str(geo.LDS_MEMBERS)
+    assert abi.macro(HEADER, "SBE_GEO_MAX_OBJECTS") == str(geo.MAX_OBJECTS)
+    assert abi.macro(HEADER, "SBE_GEO_MAX_MASKS") == "(1 << 20)" and geo.MAX_MASKS == 1 << 20
+    assert abi.macro(HEADER, "SBE_GEO_MAX_LAUNCH_MASKS") == "(1 << 16)" and geo.MAX_LAUNCH_MASKS == 1 << 16
+    assert abi.macro(HEADER, "SBE_GEO_LDS_MEMBERS") == str(geo.LDS_MEMBERS)
     assert geo.MAX_OBJECTS ** 2 * 8 == 8 << 30             # the cost matrix at the limit: 8 GiB, as SBE_EM_MAX_COST_BYTES
     assert (geo.LDS_MEMBERS ** 2 + geo.LDS_MEMBERS) * 8 + 8192 <= 160 * 1024       # the staged sub-matrix fits a workgroup's LDS
     for table, prefix in ((geo.SKELETONS, "SBE_GEO_SKELETON_"), (geo.AGGREGATIONS, "SBE_GEO_AGG_"), (geo.PROBABILITY_FUNCTIONS, "SBE_GEO_PROB_")):
         for name, code in table.items():
-            assert macro(HEADER, prefix + {"complete_graph": "COMPLETE"}.get(name, name.upper())) == str(code)
+            assert abi.macro(HEADER, prefix + {"complete_graph": "COMPLETE"}.get(name, name.upper())) == str(code)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """geo.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(geo))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(geo)
 
 
 class _NoDevice(geo.GeoHandle):
@@ -86,29 +71,11 @@ def test_too_many_masks_are_refused_with_the_limit():
 
 
 def test_c_abi_validates_before_the_device():
-    lib = geo.load()
-    h = ct.c_void_p()
-    assert lib.sbe_geo_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_geo_last_error(None)
-    assert lib.sbe_geo_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_geo_last_error(None)
-    assert lib.sbe_geo_set_cost(None, None, 1) == 1
-    assert b"null handle" in lib.sbe_geo_last_error(None)
-    assert lib.sbe_geo_skeleton(None, None, 0, 0, None, None, None, None) == 1
-    assert lib.sbe_geo_prior(None, None, 0, 0, 0, 0, 1.0, 0.0, None) == 1
-    assert lib.sbe_geo_costs_per_object(None, None, 0, 0, 1.0, 0.0, None, None) == 1
-    assert lib.sbe_geo_log_expit(None, None, 0, None) == 1
-    assert lib.sbe_geo_destroy(None) == 1
-    assert lib.sbe_geo_set_launch_masks(None, 4) == 1
-    ms = ct.c_float()
-    assert lib.sbe_geo_last_kernel_ms(None, ct.byref(ms)) == 1
+    assert sorted(abi.check_null_handles(geo)) == sorted(set(geo.PROTOTYPES) - {"sbe_geo_abi_version", "sbe_geo_last_error"})
 
 
 def test_handles_are_not_picklable_and_enums_pass_as_strings():
-    h = object.__new__(geo.GeoHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError):
-        pickle.dumps(h)
+    abi.check_not_picklable(geo.GeoHandle)
     import enum
 
     class Agg(str, enum.Enum):

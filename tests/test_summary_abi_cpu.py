@@ -1,36 +1,27 @@
 """CPU checks of the summary boundary (include/sbe_summary.h, sbayes_amd/summary.py): the symbols are exported and bound by
 the module's own prototype table, the limits agree, and bad arguments are refused before the device is touched."""
-import ast
 import ctypes as ct
-import inspect
-import pickle
 from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from sbayes_amd import _lib, diag, summary
-from tests._abi_header import declared, macro
+from sbayes_amd import diag, summary
+from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "sbe_summary.h").read_text()
 
 
 def test_every_symbol_of_the_header_is_exported_and_bound():
-    lib = summary.load()
-    names = declared(HEADER)
-    assert len(names) == 12
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in include/sbe_summary.h but not exported"
-    assert sorted(summary.PROTOTYPES) == names
-    assert lib.sbe_summary_abi_version() == summary.ABI_VERSION == int(macro(HEADER, "SBE_SUMMARY_ABI_VERSION"))
-    assert not set(names) & set(_lib.PROTOTYPES) and not set(names) & set(diag.PROTOTYPES)
+    names = abi.check_symbols(summary, HEADER, 12)
+    assert not set(names) & set(diag.PROTOTYPES)
 
 
 def test_limits_and_codes_agree_with_the_header():
-    assert macro(HEADER, "SBE_SUMMARY_MAX_PROBS") == str(summary.MAX_PROBS) == "8"
-    assert {k: int(macro(HEADER, "SBE_SUMMARY_DERIVED_" + k.upper())) for k in summary.DERIVED} == summary.DERIVED
+    assert abi.macro(HEADER, "SBE_SUMMARY_MAX_PROBS") == str(summary.MAX_PROBS) == "8"
+    assert {k: int(abi.macro(HEADER, "SBE_SUMMARY_DERIVED_" + k.upper())) for k in summary.DERIVED} == summary.DERIVED
     # the limits of the diagnostics are the summary's own
     assert (summary.MAX_CHAINS, summary.MIN_DRAWS, summary.MAX_DRAWS, summary.MAX_COLUMNS) == \
         (diag.MAX_CHAINS, diag.MIN_DRAWS, diag.MAX_DRAWS, diag.MAX_COLUMNS)
@@ -41,12 +32,7 @@ def test_limits_and_codes_agree_with_the_header():
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
-    """summary.py passes bare addresses (_ptr): the argument must be a plain local name, never a temporary."""
-    tree = ast.parse(inspect.getsource(summary))
-    bad = [(n.lineno, ast.unparse(n)) for n in ast.walk(tree)
-           if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "_ptr"
-           and (len(n.args) != 1 or not isinstance(n.args[0], ast.Name))]
-    assert not bad, bad
+    abi.check_ptr_arguments(summary)
 
 
 @pytest.fixture
@@ -81,33 +67,11 @@ def test_bad_input_is_refused_before_the_device(no_device, chains, kw, err, matc
 
 
 def test_c_abi_validates_before_the_device():
-    lib = summary.load()
-    h = ct.c_void_p()
-    assert lib.sbe_summary_create(None, 0) == 1
-    assert b"null pointer argument: out" in lib.sbe_summary_last_error(None)
-    assert lib.sbe_summary_create(ct.byref(h), -1) == 1 and not h
-    assert b"device -1 out of range" in lib.sbe_summary_last_error(None)
-    assert lib.sbe_summary_reset(None, 1, 1, 1) == 1
-    assert b"null handle" in lib.sbe_summary_last_error(None)
-    assert lib.sbe_summary_append_rows(None, 0, None, 0) == 1
-    n = ct.c_int64()
-    assert lib.sbe_summary_rows(None, 0, ct.byref(n)) == 1
-    assert lib.sbe_summary_set_launch_columns(None, 4) == 1
-    assert lib.sbe_summary_compute(None, None, 1, 0, 0, None, 0.94, *([None] * 13)) == 1
-    m, path = ct.c_int(), ct.c_int()
-    assert lib.sbe_summary_last_shape(None, ct.byref(m), ct.byref(n), ct.byref(path), ct.byref(n), ct.byref(n)) == 1
-    assert lib.sbe_summary_derived_column(None, 0, 0, None) == 1
-    assert lib.sbe_summary_destroy(None) == 1
-    ms = (ct.c_float * 2)()
-    assert lib.sbe_summary_last_kernel_ms(None, ms) == 1
-    assert b"null handle" in lib.sbe_summary_last_error(None)
+    assert sorted(abi.check_null_handles(summary)) == sorted(set(summary.PROTOTYPES) - {"sbe_summary_abi_version", "sbe_summary_last_error"})
 
 
 def test_handles_are_not_picklable():
-    h = object.__new__(summary.SummaryHandle)
-    h._h = ct.c_void_p()
-    with pytest.raises(TypeError, match="not picklable"):
-        pickle.dumps(h)
+    abi.check_not_picklable(summary.SummaryHandle)
 
 
 def test_a_handle_checks_its_own_arguments_before_the_library():
