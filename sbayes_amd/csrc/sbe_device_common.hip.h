@@ -4,13 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "sbe_mixture_plan.h"     // kBlock, kWave, kMaxComponents, kMaxTuples, kLogTabEntries: shared with the launch decision
 
 namespace sbe {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kMaxComponents = 8;
-constexpr int kMaxTuples = 64;
 constexpr uint16_t kNoGroup = 0xFFFF;
 constexpr uint8_t kNA = 0xFF;
 
@@ -359,7 +356,6 @@ typedef double f64x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) const f64x2_t lds_cf64x2_t;
-constexpr int kLogTabEntries = 128;
 
 // (tab_log_core: the straight-line part, garbage for arguments that are not positive normal doubles --
 //  tab_log_special tells; callers that interleave several logs test the specials once, after the batch)

@@ -124,32 +124,11 @@ int sbe_create(sbe_engine** out, int device, int n_objects, int n_features, int 
 
     sbe_engine* e = new sbe_engine();
     e->device = device;
-    e->N = n_objects; e->F = n_features; e->S = n_states; e->C = n_components; e->n_slots = n_slots;
     e->G.assign(n_groups, n_groups + n_components);
     e->goff.resize(n_components);
     for (int c = 0, o = 0; c < n_components; ++c) { e->goff[c] = o; o += n_groups[c]; }
-    e->Gtot = (int)gtot;
     e->Fp = round_up(n_features, 64);
     e->rs_pitch = round_up(n_features * n_states, 16);
-    e->Pmax = std::min(1 << n_components, 64);
-    e->Np = round_up(n_objects, 4);
-    e->NQ = e->Np / 4;
-    {   // v2 feature-tile width: widest of 64/32/16 whose LDS image leaves two blocks per CU
-        const char* env = getenv("SBE_FT");
-        int ft = 64;
-        auto lds_for = [&](int t) { return ((size_t)(gtot + 1) * t * n_states) * sizeof(float) + (size_t)e->Pmax * n_components * t * sizeof(double) + 8 * 1024; };
-        while (ft > 16 && lds_for(ft) > 78 * 1024) ft >>= 1;
-        if (env && (atoi(env) == 64 || atoi(env) == 32 || atoi(env) == 16)) ft = atoi(env);
-        if (lds_for(ft) > 156 * 1024) {
-            if (env) { delete e; return fail(nullptr, SBE_ERR_ARG, "probability tables too large for LDS staging at the forced tile width (G_total=%lld, S=%d)", (long long)gtot, n_states); }
-            ft = 16;                 // very many groups x states: no LDS staging of tables (L2-served gathers)
-            e->direct = true;
-        }
-        if (getenv("SBE_DIRECT") && atoi(getenv("SBE_DIRECT")) == 1) { ft = 16; e->direct = true; }   // experiments / tests
-        e->ft = ft;
-        e->n_ftiles = div_up(n_features, ft);
-        e->Fq = round_up(n_features, 64);       // row pitch of the quad-interleaved state streams (>= any tiling of F)
-    }
     e->conc_set.assign(n_components, 0);
     e->slots.resize(n_slots);
     e->src_sync.resize(n_slots);
@@ -178,12 +157,21 @@ int sbe_create(sbe_engine** out, int device, int n_objects, int n_features, int 
     CREATE_CHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     CREATE_CHK(hipGetDeviceProperties(&prop, device));
-    e->compute_units = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char* env = getenv("SBE_MFMA_MIN_BATCH")) { if (atoi(env) > 0) e->mfma_min_batch = atoi(env); }      // (A/B runs, tests)
-    if (const char* env = getenv("SBE_MFMA_WIDE_MIN_SHARE")) { if (atoi(env) >= 0) e->mfma_wide_min_share = atoi(env); }
-    if (const char* env = getenv("SBE_MFMA_SMALL_SL4")) e->mfma_small_sl4 = atoi(env) != 0;
-    if (const char* env = getenv("SBE_MFMA_MIN_OBS")) { if (atoll(env) > 0) e->mfma_min_obs = atoll(env); }
-    if (const char* env = getenv("SBE_ROWS_SORTED")) e->opt_rows_sorted = atoi(env);
+    {   // what the launch decision fixes here: tile widths, direct tables, the rows form's tile, ... (sbe_mixture_plan.h)
+        auto env_int = [](const char* name, int* v) -> const int* { const char* s = getenv(name); if (!s) return nullptr; *v = atoi(s); return v; };
+        int ft = 0, rows_ft = 0;
+        const bool direct = getenv("SBE_DIRECT") && atoi(getenv("SBE_DIRECT")) == 1;
+        if (!derive_mix_shape(*e, n_objects, n_features, n_states, n_components, (int)gtot, n_slots,
+                              prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, env_int("SBE_FT", &ft), direct, env_int("SBE_ROWS_FT", &rows_ft))) {
+            sbe_destroy(e);
+            return fail(nullptr, SBE_ERR_ARG, "probability tables too large for LDS staging at the forced tile width (G_total=%lld, S=%d)", (long long)gtot, n_states);
+        }
+    }
+    if (const char* env = getenv("SBE_MFMA_MIN_BATCH")) { if (atoi(env) > 0) e->tune.mfma_min_batch = atoi(env); }      // (A/B runs, tests)
+    if (const char* env = getenv("SBE_MFMA_WIDE_MIN_SHARE")) { if (atoi(env) >= 0) e->tune.mfma_wide_min_share = atoi(env); }
+    if (const char* env = getenv("SBE_MFMA_SMALL_SL4")) e->tune.mfma_small_sl4 = atoi(env) != 0;
+    if (const char* env = getenv("SBE_MFMA_MIN_OBS")) { if (atoll(env) > 0) e->tune.mfma_min_obs = atoll(env); }
+    if (const char* env = getenv("SBE_ROWS_SORTED")) e->tune.opt_rows_sorted = atoi(env);
     snprintf(e->device_name, sizeof e->device_name, "%s%s%s", prop.name, prop.name[0] ? " " : "", prop.gcnArchName);
     CREATE_CHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     CREATE_CHK(hipEventCreate(&e->ev0));
@@ -216,17 +204,9 @@ int sbe_create(sbe_engine** out, int device, int n_objects, int n_features, int 
     CREATE_RC(dmalloc(e, &e->d_tid, NS * e->Np));
     CREATE_RC(dmalloc(e, &e->d_toff, NS * e->Np + 64));       // + padding: the kernel prefetches 16 entries ahead
     CREATE_CHK(hipMemsetAsync(e->d_toff, 0, (NS * e->Np + 64) * sizeof(uint32_t), e->stream));
-    if (C <= 4) {   // k_mixture_rows: widest tile whose LDS image (tables f32 [(Gtot+1)][S+1][ft] + f64 weight planes) fits
-        // (sized for half the possible has_components patterns: a component every object has -- `universal` -- halves
-        //  them; a launch whose slots really have more falls back to k_mixture_v2) + the waves' offset slots
-        const int p_assumed = std::max(1, e->Pmax / 2);
-        auto rows_lds = [&](int t) { return (size_t)(gtot + 1) * (S + 1) * t * 4 + (size_t)p_assumed * ((C + 1) / 2) * t * 16 + (size_t)kRowsWaves * (kWave / t) * (C + 1) * 16; };
-        e->rows_ft = rows_lds(32) <= 160 * 1024 - 512 ? 32 : rows_lds(16) <= 160 * 1024 - 512 ? 16 : 0;
-        if (const char* env = getenv("SBE_ROWS_FT")) { const int v = atoi(env); if (v == 0 || ((v == 16 || v == 32) && rows_lds(v) <= 160 * 1024 - 512)) e->rows_ft = v; }
-        if (e->rows_ft) {
-            CREATE_RC(dmalloc(e, &e->d_rowoff, NS * (C + 1) * e->Np));
-            e->rowoff_epoch.assign(n_slots, ~0ull);
-        }
+    if (e->rows_ft) {   // k_mixture_rows: per-object row offsets (k_rowoff)
+        CREATE_RC(dmalloc(e, &e->d_rowoff, NS * (C + 1) * e->Np));
+        e->rowoff_epoch.assign(n_slots, ~0ull);
     }
     {   // table of tab_log_pos: interval centres c_i = 1 + (i + 1/2)/128 (c_0 = 1), {RN(1/c), RN(-log(RN(1/c)))}
         std::vector<double> tab(2 * kLogTabEntries);
@@ -239,7 +219,7 @@ int sbe_create(sbe_engine** out, int device, int n_objects, int n_features, int 
         CREATE_RC(dmalloc(e, &e->d_logtab, (int64_t)kLogTabEntries));
         CREATE_CHK(hipMemcpy(e->d_logtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (e->ft == 64 && S <= 127 && (int64_t)e->NQ * e->Fq * 8 < ((int64_t)1 << 31)) {
+    if (e->has_state_h) {
         CREATE_RC(dmalloc(e, &e->d_state_h, (int64_t)e->NQ * e->Fq * 4));
         k_init_state_h<<<div_up((int64_t)e->NQ * e->Fq, 256), 256, 0, e->stream>>>(e->d_state_h, (int64_t)e->NQ * e->Fq, e->Fq, e->S);
         CREATE_CHK(hipGetLastError());
@@ -260,12 +240,7 @@ int sbe_create(sbe_engine** out, int device, int n_objects, int n_features, int 
             for (int g = 0; g < e->G[c]; ++g) cog[e->goff[c] + g] = c;
         CREATE_CHK(hipMemcpy(e->d_comp_of_group, cog.data(), (size_t)std::max(e->Gtot, 1) * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    // partials: worst-case block count of the fused kernel (ft = 16, one packed step per thread)
-    {
-        const int64_t min_objs = kBlock / (16 / 4);
-        e->partials_stride = std::max<int64_t>(div_up(F, 16) * std::max<int64_t>(div_up(N, min_objs), 4 * e->compute_units), 1024);
-    }
-    CREATE_RC(dmalloc(e, &e->d_partials, NS * e->partials_stride));
+    CREATE_RC(dmalloc(e, &e->d_partials, NS * e->partials_stride));      // (worst-case block count of the fused kernel)
     CREATE_RC(dmalloc(e, &e->d_arrive, NS + 1));
     CREATE_CHK(hipMemset(e->d_arrive, 0, (size_t)(NS + 1) * sizeof(unsigned)));
     CREATE_RC(dmalloc(e, &e->d_status, (int64_t)ST_WORDS));
@@ -380,7 +355,7 @@ int sbe_get_na(const sbe_engine* ce, uint8_t* out_na) {
 
 int sbe_set_option(sbe_engine* e, int option, int value) {
     CHECK_ENGINE(e);
-    if (option == SBE_OPT_MIXTURE_KERNEL && (value == SBE_MIXTURE_PACKED || value == SBE_MIXTURE_ONEHOT || value == SBE_MIXTURE_PACKED_GENERAL || value == SBE_MIXTURE_PACKED_TUPLE || value == SBE_MIXTURE_PACKED_TUPLE_LDS || value == SBE_MIXTURE_ONEHOT_GENERAL || value == SBE_MIXTURE_PACKED_V2 || value == SBE_MIXTURE_PACKED_TUPLE_MFMA)) { e->opt_kernel = value; return SBE_OK; }
+    if (option == SBE_OPT_MIXTURE_KERNEL && (value == SBE_MIXTURE_PACKED || value == SBE_MIXTURE_ONEHOT || value == SBE_MIXTURE_PACKED_GENERAL || value == SBE_MIXTURE_PACKED_TUPLE || value == SBE_MIXTURE_PACKED_TUPLE_LDS || value == SBE_MIXTURE_ONEHOT_GENERAL || value == SBE_MIXTURE_PACKED_V2 || value == SBE_MIXTURE_PACKED_TUPLE_MFMA)) { e->tune.opt_kernel = value; return SBE_OK; }
     if (option == SBE_OPT_LOG_MODE && (value == SBE_LOG_PER_OBS || value == SBE_LOG_PRODUCT)) { e->opt_log = value; return SBE_OK; }
     if (option == SBE_OPT_STEP_FORM && (value == 0 || value == 1)) { e->opt_step_form = value; return SBE_OK; }
     if (option == SBE_OPT_STEP_DERIVE && (value == 0 || value == 1)) { e->opt_step_derive = value; return SBE_OK; }
@@ -935,7 +910,7 @@ int sbe_mixture_loglik_batch_async(sbe_engine* e, int first_slot, int n) {
     CHECK_ENGINE(e); CHECK_SLOT(e, first_slot);
     if (n < 1 || first_slot + n > e->n_slots) return fail(e, SBE_ERR_ARG, "slot range [%d,%d) out of range", first_slot, first_slot + n);
     HIPCHK(e, hipSetDevice(e->device));
-    return enqueue_mixture(e, first_slot, n, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS);
+    return enqueue_mixture(e, first_slot, n);
 }
 
 int sbe_fetch_results(sbe_engine* e, int first_slot, int n, double* out) {
@@ -951,7 +926,7 @@ int sbe_mixture_loglik_batch(sbe_engine* e, int first_slot, int n, double* out) 
     if (n < 1 || first_slot + n > e->n_slots) return fail(e, SBE_ERR_ARG, "slot range out of range");
     HIPCHK(e, hipSetDevice(e->device));
     DoneSig done;
-    int rc = enqueue_mixture(e, first_slot, n, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, &done);
+    int rc = enqueue_mixture(e, first_slot, n, &done);
     if (rc) return rc;
     rc = wait_done(e, done);                        // results were written straight into mapped host memory
     if (rc) return rc;
@@ -1186,13 +1161,14 @@ int sbe_profile_mixture(sbe_engine* e, int first_slot, int n, int iters, float* 
         HIPCHK(e, hipEventCreate(&ev));
         e->ev_pool.push_back(ev);
     }
-    const int mode = e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS;
-    int rc = enqueue_mixture(e, first_slot, n, mode);     // resolves lazily-built state
+    int rc = enqueue_mixture(e, first_slot, n);     // resolves lazily-built state
     if (rc) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     HIPCHK(e, hipEventRecord(e->ev0, e->stream));
     for (int it = 0; it < iters; ++it) {
-        rc = launch_mixture(e, first_slot, n, mode, e->ev_pool[2 * it], e->ev_pool[2 * it + 1]);
+        MixCall c;
+        c.first_slot = first_slot; c.n = n; c.ev_a = e->ev_pool[2 * it]; c.ev_b = e->ev_pool[2 * it + 1];
+        rc = launch_mixture(e, c);
         if (rc) return rc;
     }
     HIPCHK(e, hipEventRecord(e->ev1, e->stream));

@@ -75,19 +75,15 @@ static int fuse_tables_default() {
     return on;
 }
 
-struct sbe_engine {
+// (what creation fixes for the launch decision -- N, F, S, C, the tile widths, ... -- is the MixShape base: sbe_mixture_plan.h)
+struct sbe_engine : sbe::MixShape {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> ev_pool;
     bool ev_timing = false;  int ev_used = 0;      // sbe_kernel_timing: event pairs recorded around the dominant kernel
-    int N = 0, F = 0, S = 0, C = 0, n_slots = 0;
-    int Fp = 0, rs_pitch = 0, Gtot = 0, Pmax = 0;
-    int Np = 0, NQ = 0;            // objects padded to a multiple of 4; object quads
-    int ft = 64, n_ftiles = 0, Fq = 0;   // v2 fused-kernel feature tile width, tiles, padded features
-    bool direct = false;           // tables of a 16-feature tile exceed LDS: gather from the global tiled tables
+    int Fp = 0, rs_pitch = 0;
     uint64_t rng_seed = 0, rng_draw = 0;   // Philox key / draw counter of sbe_sample_source(z = NULL)
-    int compute_units = 256;
     std::vector<int> G, goff;
     int64_t n_na = 0;
     int64_t hbm_bytes = 0;
@@ -96,7 +92,7 @@ struct sbe_engine {
     char last_kernel[128] = "none";     // kernel form of the most recent fused-kernel launch (sbe_last_mixture_kernel)
 
     // options
-    int opt_kernel = SBE_MIXTURE_PACKED;
+    sbe::MixTuning tune;           // SBE_OPT_MIXTURE_KERNEL and the launch decision's experiment values
     int opt_log = SBE_LOG_PRODUCT;
     int opt_fuse_tables = fuse_tables_default();   // SBE_OPT_FUSE_TABLES
 
@@ -115,30 +111,22 @@ struct sbe_engine {
     float* d_weights = nullptr;    // [slots][F][C]
     float* d_wpat = nullptr;       // [slots][Pmax][F][C]
     uint32_t* d_patbits = nullptr; // [slots][Pmax]
-    uint16_t* d_state_h = nullptr; // [NQ][Fq][4] prepared LDS offsets of k_mixture_tuple64 (ft == 64, S <= 127) or null
+    uint16_t* d_state_h = nullptr; // [NQ][Fq][4] prepared LDS offsets of k_mixture_tuple64 (has_state_h) or null
     double2* d_logtab = nullptr;   // [128] {1/c, log c}: table of tab_log_pos (k_mixture_tuple64's table build)
     uint32_t* d_toff = nullptr;    // [slots][Np] byte offset of the object's tuple block, tid*(S+1)*512 (k_mixture_tuple64)
     uint32_t* d_rowoff = nullptr;  // [slots][C+1][Np] LDS byte offsets of k_mixture_rows (k_rowoff), or null
-    int rows_ft = 0;               // tile width of k_mixture_rows (32 / 16; 0: its LDS image does not fit, or C > 4)
     std::vector<uint64_t> rowoff_epoch;   // per slot: Slot::group_epoch the device array was built from
     // pattern-sorted form of the rows kernel (built at its first launch): the slot's objects by has_components pattern
     uint32_t* d_rowoff_s = nullptr;  int rs_nq_max = 0;   // [slots][rs_nq_max][C+1][4] (k_rowsort)
     int32_t* d_rs_nq = nullptr;           // [slots] quads of the slot's padded order
     uint8_t* d_state_s = nullptr;         // [N + 1][Fp] state index, NA = S; row N all NA (the null object)
     std::vector<uint64_t> rowsort_epoch;
-    int opt_rows_sorted = 1;              // SBE_ROWS_SORTED: 0 never, 1 launches of >= 16 slots at 32-feature tiles (default), 2 whenever it applies (tests)
     std::atomic<uint64_t> epoch_counter{0};
     double2* d_logtab_fine = nullptr;    // the matrix-pipe kernel's 1024-interval log table (built with d_xt)
     unsigned* d_arrive = nullptr;  // [slots + 1] tickets of the north-star kernels' in-kernel final reduction (finish_partial: per slot; matrix-pipe
                                    // form: per group of 16 slots); every launch leaves them at 0
     uint8_t* d_xt = nullptr;       // one-hot block in MFMA fragment order (k_mixture_tuple_mfma), built at the first batched launch
     int xt_NT = 0, xt_KBp = 0;  size_t xt_bytes = 0;
-    int mfma_small_sl4 = 1;        // four slots per block for launches whose blocks fit two rounds on the CUs (SBE_MFMA_SMALL_SL4=0: A/B)
-    int64_t mfma_min_obs = 6400000;  // ... chosen from 32 states per launch on when n x N x F reaches this (SBE_MFMA_MIN_OBS)
-    int mfma_wide_min_share = 16;  // wide matrix-pipe forms (> 8 tuples) by default only from this many objects per padded tuple on (SBE_MFMA_WIDE_MIN_SHARE)
-    int mfma_min_batch = 320;      // smallest launch the matrix-pipe form is chosen for under SBE_MIXTURE_PACKED (SBE_MFMA_MIN_BATCH);
-                                   // round 6, FP4 operands: 24.5 / 24.6 / 24.8 us against 22.2 / 32.1 / 34.9 us of k_mixture_tuple64 at
-                                   // 256 / 384 / 512 headline states (tools/diag/mfma_threshold.py, profiles/r6/mfma_threshold.log)
     uint8_t* d_tid = nullptr;      // [slots][Np] group-tuple index per object (k_mixture_combo)
     uint16_t* d_tuple_g = nullptr; // [slots][kMaxTuples][kMaxComponents]
     uint8_t* d_tuple_p = nullptr;  // [slots][kMaxTuples]
@@ -149,7 +137,7 @@ struct sbe_engine {
     int32_t* d_comp_of_group = nullptr;                     // [Gtot] mixture component of every global group index
     std::vector<uint8_t> conc_set;
     // scratch
-    double* d_partials = nullptr;  int64_t partials_stride = 0;   // [slots][max_blocks]
+    double* d_partials = nullptr;  // [slots][partials_stride]
     double* d_results = nullptr;   // [slots] device view of h_results (host-mapped)
     double* h_results = nullptr;   // pinned + mapped [slots]: k_reduce_partials writes straight to the host
     int* d_status = nullptr;       // [ST_WORDS]
@@ -217,8 +205,6 @@ struct sbe_engine {
     // (sbe_step_batch_delta patches those entries instead of re-deriving / copying whole arrays)
     std::vector<SrcSync> ids_sync;
 
-    int64_t table_elems() const { return (int64_t)Gtot * F * S; }
-    int64_t tile_tab_elems() const { return (int64_t)(Gtot + 1) * S * ft; }
     int64_t probs_t_elems() const { return (int64_t)n_ftiles * tile_tab_elems(); }
     int64_t wpat_tile_elems() const { return (int64_t)Pmax * C * ft; }
     int64_t wpat_t_elems() const { return (int64_t)n_ftiles * wpat_tile_elems(); }
@@ -875,42 +861,6 @@ int retile_probs(sbe_engine* e, int slot, int component) {
     return SBE_OK;
 }
 
-// ---- geometry + launch of the fused kernel ---------------------------------------------------
-struct MixGeom {
-    int ft, ft_shift, n_ftiles, objs_per_chunk, n_chunks, n_blocks;
-    size_t lds_bytes;
-};
-
-// v2 geometry: chunks of object quads; one wave step = 64/ft quads.  The chunk's ids are staged
-// in LDS (8*C + 4 bytes per quad), which caps the chunk length.
-MixGeom mix_geometry_v2(const sbe_engine* e, int P, int n_batch, int blocks_per_cu = 4) {
-    MixGeom g{};
-    g.ft = e->ft;
-    g.n_ftiles = e->n_ftiles;
-    // no more workgroups than the CUs hold at once when the tile image is large: every workgroup stages the whole
-    // image, so extra generations only multiply the staging traffic (stress shape, single eval: 15.9 -> 13 us)
-    if (!e->direct) {
-        const size_t image = (size_t)e->tile_tab_elems() * sizeof(float) + (size_t)P * e->C * e->ft * sizeof(double);
-        blocks_per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)blocks_per_cu, (160 * 1024) / (image + 4096)));
-    }
-    const int64_t target_blocks = (int64_t)blocks_per_cu * e->compute_units;
-    int64_t chunks = std::max<int64_t>(1, target_blocks / ((int64_t)g.n_ftiles * std::max(1, n_batch)));
-    const int min_quads = 4 * (kWave / e->ft);            // one step for each of the 4 waves
-    const int max_quads = std::max(min_quads, (8 * 1024) / (8 * e->C + 4));
-    g.objs_per_chunk = std::min<int>(max_quads, std::max<int>(min_quads, div_up(e->NQ, chunks)));   // in quads
-    g.n_chunks = div_up(e->NQ, g.objs_per_chunk);
-    g.n_blocks = g.n_chunks * g.n_ftiles;
-    g.lds_bytes = (size_t)g.objs_per_chunk * (8 * e->C + 4);
-    if (!e->direct) g.lds_bytes += (size_t)e->tile_tab_elems() * sizeof(float) + (size_t)P * e->C * e->ft * sizeof(double);
-    return g;
-}
-
-int max_patterns(sbe_engine* e, int first_slot, int n) {
-    int P = 1;
-    for (int s = first_slot; s < first_slot + n; ++s) P = std::max<int>(P, (int)e->slots[s].patterns.size());
-    return P;
-}
-
 int check_slot_ready(sbe_engine* e, int slot, bool need_weights) {
     Slot& s = e->slots[slot];
     if (!s.groups_set) return fail(e, SBE_ERR_STATE, "slot %d: groups not set for every component", slot);
@@ -934,12 +884,12 @@ int ensure_xt(sbe_engine* e) {
     auto build = [&]() -> int {
         HIPCHK(e, hipMalloc((void**)&xt, bytes));
         HIPCHK(e, hipMemsetAsync(xt, 0, bytes, e->stream));
-        std::vector<double> tab(2 * 1024);               // the kernel's own log table (tab_log4_n)
+        std::vector<double> tab(2 * kFineLogEntries);               // the kernel's own log table (tab_log4_n)
         fine_log_table(tab.data());
         // (the per-column object counts of the exponent bias sit behind the table in the same allocation)
         HIPCHK(e, hipMalloc((void**)&logtab, tab.size() * sizeof(double) + column_tables_bytes(NT)));
         HIPCHK(e, hipMemcpy(logtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-        launch_column_tables(e->d_state, reinterpret_cast<int32_t*>(logtab + 1024), e->N, e->F, e->S, e->Fp, NT, e->stream);
+        launch_column_tables(e->d_state, reinterpret_cast<int32_t*>(logtab + kFineLogEntries), e->N, e->F, e->S, e->Fp, NT, e->stream);
         HIPCHK(e, hipGetLastError());
         launch_xt_frags(e->d_state, xt, e->N, e->F, e->S, e->Fp, NT, KBp, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -958,89 +908,6 @@ int ensure_xt(sbe_engine* e) {
     return SBE_OK;
 }
 
-// geometry of a matrix-pipe launch over n slots with at most KT tuples each; n_split = 0: the form does not apply
-struct MfmaGeom { int n_split, nt_per_split, MT, SL; size_t lds; bool shared; };      // SL: slots per block (16 / 4 / 2)
-MfmaGeom mfma_geometry(const sbe_engine* e, int n, int KT) {
-    MfmaGeom g{};
-    g.SL = tuple_mfma_slots_per_block(KT);           // 16 slots x <= 8 tuples, 4 x <= 32, 2 x <= 64 per block: the most KT allows
-    if (g.SL == 0 || e->C > 4) return g;
-    const int NT = div_up((int64_t)e->F * e->S, 32), KBp = round_up(div_up(e->N, kTupleMfmaKBlockObjects), 4);
-    // Few states per launch: with 16 slots per block a launch of n states is ceil(n / 16) x (at most 4 column splits) blocks -- at
-    // 512 states half the CUs idle and every block still walks a whole pass of MT M tiles (24.6 us at 256..1024 headline states).
-    // Four slots per block (ONE M tile of <= 8 tuples x 4 slots) make four times the blocks of a third of the work per pass.  The
-    // two geometries are compared by rounds of blocks x passes per block x M tiles (a pass costs ~4.3 us per M tile at the headline
-    // shape): 14.6 / 16.1 / 17.9 / 21.4 us at 32 / 256 / 320 / 512 states (1 / 1 / 2 / 2 units against 3) where k_mixture_tuple64
-    // takes 16.0 / 21.1 / 26.5 / 35.1 us; at 576 states the four-slot form needs 4 units (30.6 us) and the 16-slot form stays
-    // (24.6 us): profiles/r6/mfma_threshold.log
-    if (g.SL == 16 && e->mfma_small_sl4) {
-        auto units = [&](int SL, int MT) -> int64_t {
-            const int groups = div_up(n, SL);
-            const int split = std::max(1, std::min(div_up(NT, 16), e->compute_units / std::max(1, groups)));
-            const int passes = div_up(round_up(div_up(NT, split), 2), 16);
-            return (int64_t)div_up(groups * split, e->compute_units) * passes * MT;
-        };
-        if (units(4, 1) < units(16, div_up(KT, 2))) g.SL = 4;
-    }
-    // ... and fewer slots per block while the A image -- MT x KBp KB, MT = tuples x slots / 32 -- does not fit a
-    // CU's LDS: many objects with few tuples (5000 objects x 6 tuples: 16 slots need 3 x 80 KB, 4 slots 1 x 80 KB)
-    for (;;) {
-        g.MT = div_up(KT, 32 / g.SL);
-        g.lds = tuple_mfma_lds_bytes(g.MT, e->C, KBp);
-        if (g.lds <= 160 * 1024 || g.SL == 2) break;
-        g.SL = g.SL == 16 ? 4 : 2;
-    }
-    if (g.lds > 160 * 1024) return g;
-    // the tables are addressed through 32-bit buffer offsets
-    const int64_t probs_bytes = ((int64_t)e->n_slots * e->table_elems() + (int64_t)e->F * e->S) * 4;
-    const int64_t wpat_bytes = ((int64_t)e->n_slots * e->Pmax * e->F * e->C + (int64_t)e->F * e->C) * 4;
-    if (probs_bytes >= ((int64_t)1 << 32) || wpat_bytes >= ((int64_t)1 << 32) || ((int64_t)(NT + 1) * KBp + 4) * 1024 >= ((int64_t)1 << 31)) return g;
-    // one block = SL slots x a range of column tiles; its 8 waves take the tiles in pairs, so a split of fewer than
-    // 16 tiles leaves waves idle: as many splits as fill the CUs, no finer
-    const int groups = div_up(n, g.SL);
-    int n_split = std::max(1, std::min(div_up(NT, 16), e->compute_units / std::max(1, groups)));
-    if (const char* env = getenv("SBE_MFMA_SPLIT")) { if (atoi(env) > 0) n_split = std::min(atoi(env), NT); }   // experiments
-    g.nt_per_split = round_up(div_up(NT, n_split), 2);
-    // (the kernel sums count * binary exponent in 32-bit integers, one accumulator per lane and slot: in a pass of 16 tiles a
-    //  lane adds the entries of its kTupleMfmaColsPerPass columns -- over every M tile and both tuples of a tile -- into the
-    //  same accumulator, and a slot's counts of ONE column add up to at most N over its tuples; the exponents are summed
-    //  BIASED (0 .. 2046; the bias leaves as 1023 x the columns' object count at the end), 2100 covers every double)
-    if ((int64_t)div_up(g.nt_per_split, 16) * kTupleMfmaColsPerPass * e->N * 2100 >= ((int64_t)1 << 31)) return g;
-    g.n_split = div_up(NT, g.nt_per_split);
-    return g;
-}
-
-int launch_mfma_form(sbe_engine* e, int first_slot, int n, int KT, const MfmaGeom& mg, const int32_t* d_slots,
-                     bool reduce_in_kernel = false, const DoneSig& done = DoneSig{}) {
-    int rc = ensure_xt(e);
-    if (rc) return rc;
-    MfmaMixParams p{};
-    p.F = e->F; p.S = e->S; p.FS = e->F * e->S; p.Gtot = e->Gtot; p.Np = e->Np;
-    p.NT = e->xt_NT; p.KBp = e->xt_KBp; p.KT = KT; p.SL = mg.SL; p.shared = mg.shared ? 1 : 0;
-    p.n_batch = n; p.n_split = mg.n_split; p.nt_per_split = mg.nt_per_split;
-    p.first_slot = first_slot; p.slot_list = d_slots;
-    p.xt = e->d_xt; p.xt_bytes = (uint32_t)e->xt_bytes;
-    p.tid = e->d_tid; p.tid_stride = e->Np;
-    p.tuple_g = e->d_tuple_g; p.tuple_g_stride = (int64_t)kMaxTuples * kMaxComponents;
-    p.tuple_p = e->d_tuple_p; p.tuple_p_stride = kMaxTuples;
-    p.probs = e->d_probs; p.probs_stride = e->table_elems();
-    p.probs_ones_off = (uint32_t)((int64_t)e->n_slots * e->table_elems() * 4);
-    p.probs_bytes = p.probs_ones_off + (uint32_t)(e->F * e->S * 4);
-    p.wpat = e->d_wpat; p.wpat_stride = (int64_t)e->Pmax * e->F * e->C;
-    p.wpat_ones_off = (uint32_t)((int64_t)e->n_slots * e->Pmax * e->F * e->C * 4);
-    p.wpat_bytes = p.wpat_ones_off + (uint32_t)(e->F * e->C * 4);
-    p.logtab = e->d_logtab_fine;
-    p.colcount = reinterpret_cast<const int32_t*>(e->d_logtab_fine + 1024);
-    p.colfeat = p.colcount + (size_t)(e->xt_NT + 1) * 32;
-    p.tile_prefix = p.colcount + (size_t)(e->xt_NT + 1) * 64;
-    p.partials = e->d_partials; p.partials_stride = e->partials_stride;
-    if (reduce_in_kernel) { p.results = e->d_results; p.arrive = e->d_arrive; p.done = done; }
-    const dim3 grid((unsigned)(div_up(n, mg.SL) * mg.n_split));
-    if (!launch_tuple_mfma(e->C, p, grid, mg.lds, e->stream))
-        return fail(e, SBE_ERR_STATE, "k_mixture_tuple_mfma was built with static LDS: its log table must sit at LDS address 0 "
-                                      "(toolchain change; rebuild without static __shared__ in sbe_mixture_mfma.hip)");
-    return SBE_OK;
-}
-
 // sbe_kernel_timing: the next event pair of the pool while recording is on (one pair per fused-kernel launch, on the engine's
 // own stream), else two nulls
 int next_timing_events(sbe_engine* e, hipEvent_t* ev_a, hipEvent_t* ev_b) {
@@ -1056,264 +923,196 @@ int next_timing_events(sbe_engine* e, hipEvent_t* ev_a, hipEvent_t* ev_b) {
     return SBE_OK;
 }
 
-// Enqueue the dominant kernel (optionally bracketed by an event pair) and the fixed-order
-// partial reduction.  mode: LOG_PER_OBS / LOG_PRODUCT.
-// Slots: first_slot .. first_slot+n-1, or (batched steps) the n slots listed in `slots` (host) / `d_slots` (the same
-// list, device-visible); then `d_fins` holds one step epilogue per listed slot.
-int launch_mixture(sbe_engine* e, int first_slot, int n, int mode, hipEvent_t ev_a, hipEvent_t ev_b,
-                   const StepFinish* fin = nullptr, const int32_t* slots = nullptr, const int32_t* d_slots = nullptr,
-                   const StepFinish* d_fins = nullptr, DoneSig* done_out = nullptr) {
-    auto slot_at = [&](int i) { return slots ? (int)slots[i] : first_slot + i; };
-    int P = 1;
-    for (int i = 0; i < n; ++i) P = std::max<int>(P, (int)e->slots[slot_at(i)].patterns.size());
-    const bool onehot = e->opt_kernel == SBE_MIXTURE_ONEHOT || e->opt_kernel == SBE_MIXTURE_ONEHOT_GENERAL;
-    MixGeom g = mix_geometry_v2(e, P, n);
-    if (!g.ft) return fail(e, SBE_ERR_ARG, "probability tables too large for LDS staging (G_total=%d, S=%d)", e->Gtot, e->S);
-    // group-tuple form: eligible when every slot of the launch has few distinct tuples, the log table fits
-    // LDS and a block sees enough observations to amortise building it.  It prefers long chunks (one block
-    // per CU is enough: the table build is per block), so it gets its own geometry.
-    int KT = 0;
-    const bool force_mfma = e->opt_kernel == SBE_MIXTURE_PACKED_TUPLE_MFMA;
-    const bool force_combo = e->opt_kernel == SBE_MIXTURE_PACKED_TUPLE || e->opt_kernel == SBE_MIXTURE_PACKED_TUPLE_LDS;
-    bool combo = e->opt_kernel == SBE_MIXTURE_PACKED || e->opt_kernel == SBE_MIXTURE_ONEHOT || force_combo || force_mfma;
-    for (int i = 0; i < n && combo; ++i) {
-        const int sl = slot_at(i);
-        if (e->slots[sl].n_tuples == 0) combo = false;
-        KT = std::max(KT, e->slots[sl].n_tuples);
+// ---- launch of the fused kernel (which form runs, and its geometry: plan_mixture, sbe_mixture_plan.h) -----------------------
+// One launch of the dominant kernel and the fixed-order reduction of its partial sums.  Slots: first_slot .. first_slot+n-1,
+// or (batched steps) the n slots listed in `slots` (host) / `d_slots` (the same list, device-visible); then `d_fins` holds one
+// step epilogue per listed slot.
+struct MixCall {
+    int first_slot = 0, n = 1;
+    const int32_t* slots = nullptr;  const int32_t* d_slots = nullptr;
+    const StepFinish* fin = nullptr;             // a single step's epilogue, run by the reduction
+    const StepFinish* d_fins = nullptr;
+    DoneSig* done_out = nullptr;                 // set: the caller waits for this descriptor (wait_done)
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;   // recorded around the fused kernel
+    int slot_at(int i) const { return slots ? (int)slots[i] : first_slot + i; }
+};
+
+MixFacts mixture_facts(const sbe_engine* e, const MixCall& c) {
+    MixFacts f;
+    f.n = c.n;
+    f.share_ok = true;
+    bool tuples = true;
+    for (int i = 0; i < c.n; ++i) {
+        const Slot& s = e->slots[c.slot_at(i)];
+        f.P = std::max<int>(f.P, (int)s.patterns.size());
+        f.KT = std::max(f.KT, s.n_tuples);
+        tuples &= s.n_tuples != 0;
+        f.share_ok &= s.share_ok;
     }
-    // large batches: the per-observation gather as an integer contraction on the matrix pipe (k_mixture_tuple_mfma)
-    MfmaGeom mg{};
-    // (default: from mfma_min_batch states per launch on whatever the shape, and -- four slots per block -- from 32 states on
-    //  when the launch holds enough observations for the kernel's fixed costs: 32 headline states = 6.4 M)
-    const bool mfma_default = e->opt_kernel == SBE_MIXTURE_PACKED &&
-                              (n >= e->mfma_min_batch || (e->mfma_small_sl4 && n >= 32 && (int64_t)n * e->N * e->F >= e->mfma_min_obs));
-    if (combo && (force_mfma || mfma_default)) {
-        mg = mfma_geometry(e, n, KT);
-        // The wide forms (more than 8 tuples: 4 / 2 slots per block) pay one log per (padded tuple, feature, state) where the
-        // vector-pipe form pays one gather per observation: by default only where a table entry is shared by enough objects
-        // (SBE_MFMA_WIDE_MIN_SHARE, objects per padded tuple; measured crossover: profiles/r6/wide_forms.log)
-        if (!force_mfma && mg.n_split > 0 && KT > 8 && e->N < e->mfma_wide_min_share * mg.MT * (32 / mg.SL)) mg = MfmaGeom{};
-    }
-    const bool mfma = mg.n_split > 0;
-    // the shared-operand epilogue: C = 2, 16 slots per block, at most 3 M tiles (6 tuples; 4 tiles spill), every slot of the
-    // launch fitting it (per-slot flag)
-    if (mfma && e->C == 2 && mg.SL == 16 && mg.MT <= 3 && tuple_mfma_shared()) {
-        mg.shared = true;
-        for (int i = 0; i < n && mg.shared; ++i) mg.shared = e->slots[slot_at(i)].share_ok;
-    }
-    if (force_mfma && !mfma)
-        return fail(e, SBE_ERR_ARG, "matrix-pipe group-tuple kernel forced but not applicable (tuples=%d, C=%d, LDS %zu bytes)", KT, e->C, mg.lds);
-    if (mfma) combo = false;
-    size_t combo_lds = 0;
-    int combo_w_off = 0, combo_tab_off = 0;
-    bool tuple64 = false;
-    if (combo) {
-        const MixGeom gc = mix_geometry_v2(e, P, n, 2);
-        // 64-feature tiles, packed stream: the scalar-unit form (tuple metadata in VGPRs, no id staging)
-        tuple64 = !onehot && gc.ft == 64 && e->d_state_h && e->opt_kernel != SBE_MIXTURE_PACKED_TUPLE_LDS;
-        // LDS image: T[KT][S+1][ft] f64 | tq[quads] u32 | tuple rows u16 | tuple patterns u32 | weights f64 [| byte table]
-        //   (tuple64: T | weights)
-        const int cu = e->C <= 4 ? e->C : kMaxComponents;
-        combo_lds = (size_t)KT * (e->S + 1) * gc.ft * sizeof(double);
-        if (!tuple64) {
-            combo_lds += (size_t)gc.objs_per_chunk * 4;
-            combo_lds += ((size_t)KT * cu + ((KT * cu) & 1)) * sizeof(uint16_t) + (size_t)KT * sizeof(uint32_t);
-        }
-        combo_lds = (combo_lds + 15) / 16 * 16;
-        combo_w_off = (int)combo_lds;
-        combo_lds += (size_t)P * e->C * gc.ft * sizeof(double);
-        if (tuple64) combo_lds += tuple64_waves() * sizeof(double) + kLogTabEntries * sizeof(double2);   // reduction scratch (the kernel has no static LDS) + log table
-        if (onehot) {      // byte-position lookup table [seg16][32] u16; a tile row segment must fit one step
-            const int seg16 = gc.ft * e->S / 16;
-            if (seg16 > kBlock) combo = false;
-            combo_tab_off = (int)combo_lds;
-            combo_lds += (size_t)seg16 * 32 * sizeof(uint16_t);
-        }
-        const int64_t obs_per_block = (int64_t)gc.objs_per_chunk * 4 * gc.ft;
-        if (combo && !force_combo && (combo_lds > 40 * 1024 || obs_per_block < (int64_t)3 * KT * e->S * gc.ft)) combo = false;
-        if (force_combo && (!combo || combo_lds > 150 * 1024))
-            return fail(e, SBE_ERR_ARG, "group-tuple kernel forced but not applicable (tuples=%d, LDS %zu bytes)", KT, combo_lds);
-        if (combo) g = gc;
-    } else if (force_combo) {
-        return fail(e, SBE_ERR_ARG, "group-tuple kernel forced but not applicable (tuples=%d, LDS %zu bytes)", KT, combo_lds);
-    }
-    // rows form (k_mixture_rows): the general packed kernel whenever its LDS image fits -- 1024-thread blocks over
-    // 32-feature (or 16-feature) tiles; SBE_MIXTURE_PACKED_V2 keeps the older k_mixture_v2 (A/B, tests)
-    bool rows = !mfma && !combo && !onehot && e->rows_ft != 0 && e->opt_kernel != SBE_MIXTURE_PACKED_V2;
-    const size_t rows_image = rows ? (size_t)(e->Gtot + 1) * (e->S + 1) * e->rows_ft * 4 + (size_t)P * ((e->C + 1) / 2) * e->rows_ft * 16
-                                         + (size_t)kRowsWaves * (kWave / e->rows_ft) * (e->C + 1) * 16 : 0;      // tables | weights | offset slots
-    if (rows && rows_image > 160 * 1024 - 512) rows = false;      // more patterns than the tile width was sized for
-    // pattern-sorted objects (weights in registers): 32-feature tiles, a second offsets slot per wave in LDS, state-row
-    // offsets of 24 bits
-    const size_t sorted_image = rows_image + (size_t)kRowsWaves * (kWave / std::max(1, e->rows_ft)) * (e->C + 1) * 16;
-    const bool sorted = rows && (e->opt_rows_sorted == 2 || (e->opt_rows_sorted == 1 && n >= 16)) && e->rows_ft == 32 && sorted_image <= 160 * 1024 - 512 &&
-                        (int64_t)(e->N + 1) * e->Fq < ((int64_t)1 << 24) && e->Pmax <= 64;
-    // a single eval with a large image (stress shape: 153 KB per block) is staging-bound in the rows form (measured
-    // 13.8 us against 12.5 us for k_mixture_v2's many small blocks); from two evals per launch on the rows form wins
-    if (rows && n == 1 && rows_image > 72 * 1024 && e->opt_kernel != SBE_MIXTURE_PACKED_GENERAL) rows = false;
-    // The rows form needs long object ranges (a 1024-thread block covers 32 quads per step) and enough observations
-    // per launch to fill one block per CU; below that k_mixture_v2's 256-thread blocks win.  Thresholds from
-    // tools/rows_crossover.py on an MI355X (kernel time of both forms over N = 500..5000, B = 8..256, C = 2 / 4,
-    // and the stress shape itself): they depend on the tile width k_mixture_v2 would run at (64: efficient, 16: not).
-    if (rows && e->opt_kernel != SBE_MIXTURE_PACKED_GENERAL) {
-        const int64_t obs = (int64_t)n * e->N * e->F;
-        const int64_t min_obs = g.ft >= 64 ? 64000000 : g.ft >= 32 ? 24000000 : 10000000;
-        const int min_quads = g.ft >= 64 ? 500 : g.ft >= 32 ? 375 : 250;
-        if (obs < min_obs || e->NQ < min_quads) rows = false;
-    }
-    if (rows) {
-        const int rft = e->rows_ft, gran = kRowsWaves * (kWave / rft);         // quads per block step
-        const int n_t = div_up(e->F, rft);
-        const size_t image = sorted ? sorted_image : rows_image;
-        if (sorted && !e->d_rowoff_s) {                                        // one-time: the sorted form's arrays
-            const int step_objs = 4 * (kWave / rft);
-            e->rs_nq_max = round_up(e->N + e->Pmax * (step_objs - 1), step_objs) / 4;
-            int rc = dmalloc(e, &e->d_rowoff_s, (int64_t)e->n_slots * e->rs_nq_max * (e->C + 1) * 4); if (rc) return rc;
-            rc = dmalloc(e, &e->d_rs_nq, e->n_slots); if (rc) return rc;
-            rc = dmalloc(e, &e->d_state_s, (int64_t)(e->N + 1) * e->Fq); if (rc) return rc;
-            launch_state_s(e->d_state, e->d_state_s, e->N, e->F, e->Fp, e->Fq, e->S, e->stream);
-            HIPCHK(e, hipGetLastError());
-            e->rowsort_epoch.assign(e->n_slots, ~0ull);
-        }
-        const int NQ_geo = sorted ? e->rs_nq_max : e->NQ;                      // (sorted: the longest padded order a slot can have)
-        // every block stages the whole image: with a large image one block per CU and as few object chunks as fill
-        // the chip; small images take two generations of blocks
-        // (a block that stages a large image wants at least ~8 block steps of work behind it)
-        const int64_t target = (int64_t)e->compute_units * (image > 72 * 1024 ? 1 : 2);
-        const int min_steps = image > 72 * 1024 ? 8 : image > 24 * 1024 ? 4 : 1;
-        int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(div_up(NQ_geo, (int64_t)gran * min_steps), div_up(target, (int64_t)n_t * n)));
-        const int qpc = round_up(div_up(NQ_geo, chunks), gran);
-        g.ft = rft; g.n_ftiles = n_t; g.objs_per_chunk = qpc; g.n_chunks = div_up(NQ_geo, qpc);
-        g.n_blocks = g.n_chunks * n_t; g.lds_bytes = image;
-        // per-object row offsets of the slots whose group ids changed since their offsets were built
-        bool stale = false;
-        if (sorted) {
-            for (int i = 0; i < n; ++i) stale |= e->rowsort_epoch[slot_at(i)] != e->slots[slot_at(i)].group_epoch;
-            if (stale) {
-                launch_rowsort(e->d_gid, e->d_pid, e->d_rowoff_s, e->d_rs_nq, (int64_t)e->C * e->Np, e->Np,
-                               (int64_t)e->rs_nq_max * (e->C + 1) * 4, first_slot, d_slots, n, e->N, e->Np, e->C, e->Gtot, e->Pmax,
-                               (uint32_t)((e->S + 1) * rft * 4), (uint32_t)e->Fq, 4 * (kWave / rft), e->stream);
-                HIPCHK(e, hipGetLastError());
-                for (int i = 0; i < n; ++i) e->rowsort_epoch[slot_at(i)] = e->slots[slot_at(i)].group_epoch;
-            }
-            stale = false;
-        } else
-        for (int i = 0; i < n; ++i) stale |= e->rowoff_epoch[slot_at(i)] != e->slots[slot_at(i)].group_epoch;
-        if (stale) {
-            const int cells = (e->C + 1) * e->Np;
-            k_rowoff<<<dim3(div_up(cells, 256), n), 256, 0, e->stream>>>(
-                e->d_gid, e->d_pid, e->d_rowoff, (int64_t)e->C * e->Np, e->Np, (int64_t)cells, first_slot, d_slots, e->N, e->Np,
-                e->C, e->Gtot, (uint32_t)((e->S + 1) * rft * 4), (uint32_t)(((e->C + 1) / 2) * rft * 16));
-            HIPCHK(e, hipGetLastError());
-            for (int i = 0; i < n; ++i) e->rowoff_epoch[slot_at(i)] = e->slots[slot_at(i)].group_epoch;
-        }
-    }
-    if (mfma) g.n_blocks = mg.n_split;                // partial sums per slot: one per column split
-    if (g.n_blocks > e->partials_stride) return fail(e, SBE_ERR_STATE, "internal: partials buffer too small (%d > %lld)", g.n_blocks, (long long)e->partials_stride);
-    if (!mfma && !combo && !rows && g.lds_bytes > 159 * 1024)
-        return fail(e, SBE_ERR_ARG, "probability / weight tables too large for LDS staging at tile width %d (%zu bytes; G_total=%d, S=%d, P=%d)",
-                    g.ft, g.lds_bytes, e->Gtot, e->S, P);
-    dim3 grid(g.n_blocks, n);
-    if (mfma) { int rc = ensure_xt(e); if (rc) return rc; }      // (one-time build: outside the event pair)
-    if (ev_a) HIPCHK(e, hipEventRecord(ev_a, e->stream));
-    // Without a step epilogue the kernel finishes the reduction itself (the last block of a slot -- of a group of 16 slots in
-    // the matrix-pipe form -- adds the partial sums): one launch per eval (batch) instead of two.  SBE_REDUCE_IN_KERNEL=0
-    // keeps k_reduce_partials (A/B runs).
+    if (!tuples) f.KT = 0;
+    f.epilogue = c.fin || c.d_fins;
+    f.waits = c.done_out != nullptr;
+    return f;
+}
+
+// the engine's tuning values plus the ones that are not fixed at creation
+MixTuning launch_tuning(const sbe_engine* e, const MixFacts& f) {
+    MixTuning t = e->tune;
+    if (considers_tuple_mfma(*e, t, f))                                            // experiments: read at every such launch
+        if (const char* env = getenv("SBE_MFMA_SPLIT")) t.mfma_split = atoi(env);
+    t.shared_allowed = tuple_mfma_shared();
     static const bool in_kernel_opt = !(getenv("SBE_REDUCE_IN_KERNEL") && atoi(getenv("SBE_REDUCE_IN_KERNEL")) == 0);
-    // Where it pays (measured, tools/probe/single_eval_latency.py and bench.py): always in the matrix-pipe form (two to four
-    // blocks per 16 slots) and when a slot is ONE block (no tickets at all); for a few blocks per slot in the asynchronous
-    // calls (throughput: one launch less per eval, cfg1 138 -> 164 k evals/s).  A host-synchronous call waits for the last
-    // block's store -> ticket -> loads, three dependent trips to the coherence point, which is 1.2-2 us MORE than the second
-    // launch; and with hundreds of blocks per slot the tickets at one address serialise (headline, one eval: 8.1 -> 11.2 us).
-    const bool in_kernel = !fin && !d_fins && in_kernel_opt && (mfma || g.n_blocks == 1 || (!done_out && g.n_blocks <= 16));
-    const bool mfma_reduce = mfma && in_kernel;
-    DoneSig done_k{};
-    if (in_kernel) {
-        done_k = done_out ? next_done(e, (unsigned)(mfma ? div_up(n, mg.SL) : n)) : DoneSig{};
-        if (done_out) *done_out = done_k;
+    t.in_kernel_allowed = in_kernel_opt;
+    return t;
+}
+
+// Everything a planned launch needs on the device besides the launch itself: the matrix-pipe form's operand image, the sorted
+// rows form's arrays (one-time, at first use) and the per-object row offsets of the slots whose group ids changed since
+// their offsets were built.
+int prepare_mixture(sbe_engine* e, const MixPlan& pl, const MixCall& c) {
+    if (pl.form == MixForm::TupleMfma) return ensure_xt(e);
+    if (pl.form != MixForm::Rows && pl.form != MixForm::RowsSorted) return SBE_OK;
+    const bool sorted = pl.form == MixForm::RowsSorted;
+    const int rft = pl.ft;
+    if (sorted && !e->d_rowoff_s) {
+        e->rs_nq_max = pl.rs_nq_max;
+        int rc = dmalloc(e, &e->d_rowoff_s, (int64_t)e->n_slots * e->rs_nq_max * (e->C + 1) * 4); if (rc) return rc;
+        rc = dmalloc(e, &e->d_rs_nq, e->n_slots); if (rc) return rc;
+        rc = dmalloc(e, &e->d_state_s, (int64_t)(e->N + 1) * e->Fq); if (rc) return rc;
+        launch_state_s(e->d_state, e->d_state_s, e->N, e->F, e->Fp, e->Fq, e->S, e->stream);
+        HIPCHK(e, hipGetLastError());
+        e->rowsort_epoch.assign(e->n_slots, ~0ull);
     }
-    if (mfma) {
-        snprintf(e->last_kernel, sizeof e->last_kernel, "k_mixture_tuple_mfma<packed stream, group-tuple form, matrix pipe fp4, %d slots x M tiles %d, C=%d%s>", mg.SL, mg.MT, e->C, mg.shared ? ", shared operands" : "");
-        int rc = launch_mfma_form(e, first_slot, n, KT, mg, d_slots, mfma_reduce, done_k);
-        if (rc) return rc;
+    std::vector<uint64_t>& built = sorted ? e->rowsort_epoch : e->rowoff_epoch;
+    bool stale = false;
+    for (int i = 0; i < c.n; ++i) stale |= built[c.slot_at(i)] != e->slots[c.slot_at(i)].group_epoch;
+    if (!stale) return SBE_OK;
+    if (sorted) {
+        launch_rowsort(e->d_gid, e->d_pid, e->d_rowoff_s, e->d_rs_nq, (int64_t)e->C * e->Np, e->Np,
+                       (int64_t)e->rs_nq_max * (e->C + 1) * 4, c.first_slot, c.d_slots, c.n, e->N, e->Np, e->C, e->Gtot, e->Pmax,
+                       (uint32_t)((e->S + 1) * rft * 4), (uint32_t)e->Fq, 4 * (kWave / rft), e->stream);
     } else {
-        // XCD-aware 1-D grid (see k_mixture_v2): units = work items x slot groups, unit u on XCD u % 8
-        int gcd8 = 8;
-        while (g.n_blocks % gcd8) gcd8 >>= 1;
-        const int slot_groups = std::max(1, std::min(8 / gcd8, n));
-        const int slots_per_group = div_up(n, slot_groups);
-        const int n_units = g.n_blocks * slot_groups;
-        grid = dim3(8 * div_up(n_units, 8) * slots_per_group, 1);
-        Mix2Params p{};
-        p.N = e->N; p.NQ = e->NQ; p.Np = e->Np; p.F = e->F; p.Fq = e->Fq; p.S = e->S; p.C = e->C;
-        p.Gtot = e->Gtot; p.P = P; p.n_ftiles = g.n_ftiles; p.quads_per_chunk = g.objs_per_chunk;
-        p.state_q = reinterpret_cast<const uint32_t*>(e->d_state_q);
-        p.onehot = e->d_onehot; p.rs_pitch = e->rs_pitch;
-        p.gid = e->d_gid; p.gid_stride = (int64_t)e->C * e->Np;
-        p.pid = e->d_pid; p.pid_stride = e->Np;
-        p.probs_t = e->d_probs_t; p.probs_t_stride = e->probs_t_elems();
-        p.wpat_t = e->d_wpat_t; p.wpat_t_stride = e->wpat_t_elems(); p.wpat_tile_stride = (int)e->wpat_tile_elems();
-        p.partials = e->d_partials; p.partials_stride = e->partials_stride; p.first_slot = first_slot;
-        if (in_kernel) { p.results = e->d_results; p.arrive = e->d_arrive; p.done = done_k; }
-        p.slot_list = d_slots;
-        p.n_work = g.n_blocks; p.n_batch = n;
-        p.slot_groups = slot_groups; p.slots_per_group = slots_per_group;
-        p.tid = e->d_tid; p.tid_stride = e->Np;
-        p.state_h = reinterpret_cast<const uint2*>(e->d_state_h);
-        p.toff = e->d_toff; p.toff_stride = e->Np;
-        p.logtab = e->d_logtab;
-        p.ragged_w = (tuple64 && e->F % 64 != 0 && e->F % 64 <= 32) ? e->F % 64 : 0;
-        if (combo && tuple64) {   // own block order (slots dealt to XCDs, generations, heavy work items first; see the kernel)
-            p.gen_slots = std::max(1, (4 * e->compute_units / 8) / g.n_blocks);
-            const int gens = div_up(div_up(n, 8), p.gen_slots);
-            grid = n >= 8 ? dim3(8 * gens * p.gen_slots * g.n_blocks, 1) : dim3(n * g.n_blocks, 1);
-        }
-        p.tuple_g = e->d_tuple_g; p.tuple_g_stride = (int64_t)kMaxTuples * kMaxComponents;
-        p.tuple_p = e->d_tuple_p; p.tuple_p_stride = kMaxTuples;
-        p.combo_w_off = combo_w_off; p.combo_tab_off = combo_tab_off;
-        p.KT = KT;
-        p.eft = e->ft;
-        p.wpat = e->d_wpat; p.wpat_stride = (int64_t)e->Pmax * e->F * e->C;
-        p.rowoff = e->d_rowoff; p.rowoff_stride = (int64_t)(e->C + 1) * e->Np;
-        p.rowoff_s = e->d_rowoff_s; p.rowoff_s_stride = (int64_t)e->rs_nq_max * (e->C + 1) * 4;
-        p.rs_nq = e->d_rs_nq; p.state_s = e->d_state_s; p.state_s_pitch = e->Fq;
-        {   // shares of a rows block's steps by wave age class (see k_mixture_rows), per mille
-            constexpr int split[4] = {450, 270, 170, 110};
-            p.rows_cum[0] = 0;
-            for (int i = 0; i < 4; ++i) p.rows_cum[i + 1] = p.rows_cum[i] + split[i];
-        }
-        snprintf(e->last_kernel, sizeof e->last_kernel, "%s<%s%s, tile %d, C=%d>",
-                 combo ? (tuple64 ? "k_mixture_tuple64" : "k_mixture_combo") : rows ? "k_mixture_rows" : (onehot ? "k_mixture_onehot_v2" : "k_mixture_v2"),
-                 onehot ? "one-hot stream" : "packed stream", combo ? ", group-tuple form" : (rows && sorted ? ", pattern-sorted objects" : (e->direct ? ", direct tables" : "")), g.ft, e->C);
-        // (the kernels live in their own translation unit: sbe_mixture.hip)
-        if (combo && tuple64) launch_tuple64(e->C, p, grid, combo_lds, e->stream);
-        else if (combo) launch_combo(onehot, g.ft, e->C, p, grid, combo_lds, e->stream);
-        else if (rows) launch_rows(mode, g.ft, e->C, p, grid, g.lds_bytes, e->stream, sorted);
-        else if (onehot) launch_oh2(mode, g.ft, e->C, p, grid, g.lds_bytes, e->stream, e->direct);
-        else launch_v2(mode, g.ft, e->C, p, grid, g.lds_bytes, e->stream, e->direct);
+        const int cells = (e->C + 1) * e->Np;
+        k_rowoff<<<dim3(div_up(cells, 256), c.n), 256, 0, e->stream>>>(
+            e->d_gid, e->d_pid, e->d_rowoff, (int64_t)e->C * e->Np, e->Np, (int64_t)cells, c.first_slot, c.d_slots, e->N, e->Np,
+            e->C, e->Gtot, (uint32_t)((e->S + 1) * rft * 4), (uint32_t)(((e->C + 1) / 2) * rft * 16));
     }
-    if (ev_b) HIPCHK(e, hipEventRecord(ev_b, e->stream));
     HIPCHK(e, hipGetLastError());
-    if (in_kernel) return SBE_OK;
-    const unsigned n_red = (unsigned)(n + (d_fins ? n : (fin ? 1 : 0)));
-    const DoneSig done = done_out ? next_done(e, n_red) : DoneSig{};      // (the caller waits with wait_done)
-    if (done_out) *done_out = done;
-    k_reduce_partials<<<n_red, kBlock, 0, e->stream>>>(e->d_partials, e->partials_stride, g.n_blocks,
-                                                       e->d_results, first_slot, n, fin ? *fin : StepFinish{},
-                                                       d_slots, d_fins, done);
+    for (int i = 0; i < c.n; ++i) built[c.slot_at(i)] = e->slots[c.slot_at(i)].group_epoch;
+    return SBE_OK;
+}
+
+// the matrix-pipe form (sbe_mixture_mfma.hip); `done`: signalled by the kernel when it finishes the reduction itself
+int launch_mfma_form(sbe_engine* e, const MixCall& c, const MixPlan& pl, const DoneSig& done) {
+    MfmaMixParams p{};
+    p.F = e->F; p.S = e->S; p.FS = e->F * e->S; p.Gtot = e->Gtot; p.Np = e->Np;
+    p.NT = e->xt_NT; p.KBp = e->xt_KBp; p.KT = pl.KT; p.SL = pl.SL; p.shared = pl.shared ? 1 : 0;
+    p.n_batch = c.n; p.n_split = pl.n_split; p.nt_per_split = pl.nt_per_split;
+    p.first_slot = c.first_slot; p.slot_list = c.d_slots;
+    p.xt = e->d_xt; p.xt_bytes = (uint32_t)e->xt_bytes;
+    p.tid = e->d_tid; p.tid_stride = e->Np;
+    p.tuple_g = e->d_tuple_g; p.tuple_g_stride = (int64_t)kMaxTuples * kMaxComponents;
+    p.tuple_p = e->d_tuple_p; p.tuple_p_stride = kMaxTuples;
+    p.probs = e->d_probs; p.probs_stride = e->table_elems();
+    p.probs_ones_off = (uint32_t)((int64_t)e->n_slots * e->table_elems() * 4);
+    p.probs_bytes = p.probs_ones_off + (uint32_t)(e->F * e->S * 4);
+    p.wpat = e->d_wpat; p.wpat_stride = (int64_t)e->Pmax * e->F * e->C;
+    p.wpat_ones_off = (uint32_t)((int64_t)e->n_slots * e->Pmax * e->F * e->C * 4);
+    p.wpat_bytes = p.wpat_ones_off + (uint32_t)(e->F * e->C * 4);
+    p.logtab = e->d_logtab_fine;
+    p.colcount = reinterpret_cast<const int32_t*>(e->d_logtab_fine + kFineLogEntries);
+    p.colfeat = p.colcount + (size_t)(e->xt_NT + 1) * 32;
+    p.tile_prefix = p.colcount + (size_t)(e->xt_NT + 1) * 64;
+    p.partials = e->d_partials; p.partials_stride = e->partials_stride;
+    if (pl.in_kernel) { p.results = e->d_results; p.arrive = e->d_arrive; p.done = done; }
+    if (!launch_tuple_mfma(e->C, p, dim3(pl.grid_x), pl.lds_bytes, e->stream))
+        return fail(e, SBE_ERR_STATE, "k_mixture_tuple_mfma was built with static LDS: its log table must sit at LDS address 0 "
+                                      "(toolchain change; rebuild without static __shared__ in sbe_mixture_mfma.hip)");
+    return SBE_OK;
+}
+
+// every other form: feature tiles x chunks of object quads (the kernels live in their own translation units: sbe_mixture*.hip)
+void launch_tile_form(sbe_engine* e, const MixCall& c, const MixPlan& pl, const DoneSig& done) {
+    Mix2Params p{};
+    p.N = e->N; p.NQ = e->NQ; p.Np = e->Np; p.F = e->F; p.Fq = e->Fq; p.S = e->S; p.C = e->C;
+    p.Gtot = e->Gtot; p.P = pl.P; p.n_ftiles = pl.n_ftiles; p.quads_per_chunk = pl.quads_per_chunk;
+    p.state_q = reinterpret_cast<const uint32_t*>(e->d_state_q);
+    p.onehot = e->d_onehot; p.rs_pitch = e->rs_pitch;
+    p.gid = e->d_gid; p.gid_stride = (int64_t)e->C * e->Np;
+    p.pid = e->d_pid; p.pid_stride = e->Np;
+    p.probs_t = e->d_probs_t; p.probs_t_stride = e->probs_t_elems();
+    p.wpat_t = e->d_wpat_t; p.wpat_t_stride = e->wpat_t_elems(); p.wpat_tile_stride = (int)e->wpat_tile_elems();
+    p.partials = e->d_partials; p.partials_stride = e->partials_stride; p.first_slot = c.first_slot;
+    if (pl.in_kernel) { p.results = e->d_results; p.arrive = e->d_arrive; p.done = done; }
+    p.slot_list = c.d_slots;
+    p.n_work = pl.n_partials; p.n_batch = c.n;
+    p.slot_groups = pl.slot_groups; p.slots_per_group = pl.slots_per_group;
+    p.tid = e->d_tid; p.tid_stride = e->Np;
+    p.state_h = reinterpret_cast<const uint2*>(e->d_state_h);
+    p.toff = e->d_toff; p.toff_stride = e->Np;
+    p.logtab = e->d_logtab;
+    p.ragged_w = pl.ragged_w; p.gen_slots = pl.gen_slots;
+    p.tuple_g = e->d_tuple_g; p.tuple_g_stride = (int64_t)kMaxTuples * kMaxComponents;
+    p.tuple_p = e->d_tuple_p; p.tuple_p_stride = kMaxTuples;
+    p.combo_w_off = pl.combo_w_off; p.combo_tab_off = pl.combo_tab_off;
+    p.KT = pl.KT;
+    p.eft = e->ft;
+    p.wpat = e->d_wpat; p.wpat_stride = (int64_t)e->Pmax * e->F * e->C;
+    p.rowoff = e->d_rowoff; p.rowoff_stride = (int64_t)(e->C + 1) * e->Np;
+    p.rowoff_s = e->d_rowoff_s; p.rowoff_s_stride = (int64_t)e->rs_nq_max * (e->C + 1) * 4;
+    p.rs_nq = e->d_rs_nq; p.state_s = e->d_state_s; p.state_s_pitch = e->Fq;
+    {   // shares of a rows block's steps by wave age class (see k_mixture_rows), per mille
+        constexpr int split[4] = {450, 270, 170, 110};
+        p.rows_cum[0] = 0;
+        for (int i = 0; i < 4; ++i) p.rows_cum[i + 1] = p.rows_cum[i] + split[i];
+    }
+    const int mode = e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS;
+    const dim3 grid(pl.grid_x, 1);
+    switch (pl.form) {
+        case MixForm::Tuple64: launch_tuple64(e->C, p, grid, pl.lds_bytes, e->stream); break;
+        case MixForm::Combo: launch_combo(pl.onehot, pl.ft, e->C, p, grid, pl.lds_bytes, e->stream); break;
+        case MixForm::Rows: case MixForm::RowsSorted:
+            launch_rows(mode, pl.ft, e->C, p, grid, pl.lds_bytes, e->stream, pl.form == MixForm::RowsSorted); break;
+        case MixForm::OnehotV2: launch_oh2(mode, pl.ft, e->C, p, grid, pl.lds_bytes, e->stream, e->direct); break;
+        default: launch_v2(mode, pl.ft, e->C, p, grid, pl.lds_bytes, e->stream, e->direct); break;
+    }
+}
+
+int launch_mixture(sbe_engine* e, const MixCall& c) {
+    const MixFacts facts = mixture_facts(e, c);
+    const MixPlan pl = plan_mixture(*e, launch_tuning(e, facts), facts);
+    if (pl.err) return fail(e, pl.err, "%s", pl.msg);
+    int rc = prepare_mixture(e, pl, c);          // (one-time builds and refreshes: outside the event pair)
+    if (rc) return rc;
+    if (c.ev_a) HIPCHK(e, hipEventRecord(c.ev_a, e->stream));
+    DoneSig done_k{};
+    if (pl.in_kernel && c.done_out) *c.done_out = done_k = next_done(e, pl.done_blocks);
+    plan_name(pl, *e, e->last_kernel, sizeof e->last_kernel);
+    if (pl.form == MixForm::TupleMfma) { rc = launch_mfma_form(e, c, pl, done_k); if (rc) return rc; }
+    else launch_tile_form(e, c, pl, done_k);
+    if (c.ev_b) HIPCHK(e, hipEventRecord(c.ev_b, e->stream));
+    HIPCHK(e, hipGetLastError());
+    if (pl.in_kernel) return SBE_OK;
+    const unsigned n_red = (unsigned)(c.n + (c.d_fins ? c.n : (c.fin ? 1 : 0)));
+    const DoneSig done = c.done_out ? next_done(e, n_red) : DoneSig{};      // (the caller waits with wait_done)
+    if (c.done_out) *c.done_out = done;
+    k_reduce_partials<<<n_red, kBlock, 0, e->stream>>>(e->d_partials, e->partials_stride, pl.n_partials,
+                                                       e->d_results, c.first_slot, c.n, c.fin ? *c.fin : StepFinish{},
+                                                       c.d_slots, c.d_fins, done);
     HIPCHK(e, hipGetLastError());
     return SBE_OK;
 }
 
-int enqueue_mixture(sbe_engine* e, int first_slot, int n, int mode, DoneSig* done_out = nullptr) {
+int enqueue_mixture(sbe_engine* e, int first_slot, int n, DoneSig* done_out = nullptr) {
     for (int s = first_slot; s < first_slot + n; ++s) {
         int rc = check_slot_ready(e, s, true);
         if (rc) return rc;
         if (e->slots[s].patterns_dirty) { rc = upload_patterns_and_weights(e, s); if (rc) return rc; }
     }
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    { int rc = next_timing_events(e, &ev_a, &ev_b); if (rc) return rc; }
-    return launch_mixture(e, first_slot, n, mode, ev_a, ev_b, nullptr, nullptr, nullptr, nullptr, done_out);
+    MixCall c;
+    c.first_slot = first_slot; c.n = n; c.done_out = done_out;
+    { int rc = next_timing_events(e, &c.ev_a, &c.ev_b); if (rc) return rc; }
+    return launch_mixture(e, c);
 }
 
 int counts_launch(sbe_engine* e, int slot_a, int sign_a, int slot_b, int sign_b, const int32_t* d_objects,

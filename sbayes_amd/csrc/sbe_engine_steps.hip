@@ -382,8 +382,9 @@ static int step_lean(sbe_engine* e, int cur_slot, int cand_slot, const uint8_t* 
     // ---- kernels 2 + 3: fused mixture eval, reduction + step epilogue (mapped-memory results) -------------------
     StepFinish fin = make_step_finish(e);
     DoneSig done;
-    rc = launch_mixture(e, cand_slot, 1, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, nullptr, nullptr, &fin, nullptr, nullptr,
-                        nullptr, &done);
+    MixCall mix;
+    mix.first_slot = cand_slot; mix.fin = &fin; mix.done_out = &done;
+    rc = launch_mixture(e, mix);
     if (rc) return rc;
     const auto t2 = std::chrono::steady_clock::now();
     rc = wait_done(e, done);
@@ -583,9 +584,10 @@ int sbe_step_batch(sbe_engine* e, int n_chains, const int32_t* cur_slots, const 
             std::swap(e->slots[cand_slots[i]], cds[i]);                               // (swap: both keep their storage)
         }
         if (part == 0) mark();
-        rc = launch_mixture(e, 0, np, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, nullptr, nullptr, nullptr,
-                            cand_slots + i0, reinterpret_cast<const int32_t*>(dm + part_cores + part_fins),
-                            reinterpret_cast<const StepFinish*>(dm + part_cores), part == n_parts - 1 ? &batch_done : nullptr);
+        MixCall mix;
+        mix.n = np; mix.slots = cand_slots + i0; mix.d_slots = reinterpret_cast<const int32_t*>(dm + part_cores + part_fins);
+        mix.d_fins = reinterpret_cast<const StepFinish*>(dm + part_cores); mix.done_out = part == n_parts - 1 ? &batch_done : nullptr;
+        rc = launch_mixture(e, mix);
         if (rc) return rc;
     }
     mark();
@@ -939,12 +941,12 @@ int sbe_step_batch_delta(sbe_engine* e, int n_chains, const int32_t* cur_slots, 
         k_step_core_batch<<<dim3(max_blocks, ng), kBlock, lds, e->stream>>>(reinterpret_cast<const StepCore*>(dm));
         HIPCHK(e, hipGetLastError());
         markd();                                 // 3: step cores built, uploaded, launched
-        hipEvent_t tev_a = nullptr, tev_b = nullptr;       // (sbe_kernel_timing brackets the fused kernel of a batched step too)
-        rc = next_timing_events(e, &tev_a, &tev_b);
+        MixCall mix;
+        mix.n = ng; mix.slots = cand_go.data(); mix.d_slots = reinterpret_cast<const int32_t*>(dm + part_cores + part_fins);
+        mix.d_fins = reinterpret_cast<const StepFinish*>(dm + part_cores); mix.done_out = &fast_done;
+        rc = next_timing_events(e, &mix.ev_a, &mix.ev_b);       // (sbe_kernel_timing brackets the fused kernel of a batched step too)
         if (rc) return rc;
-        rc = launch_mixture(e, 0, ng, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, tev_a, tev_b, nullptr,
-                            cand_go.data(), reinterpret_cast<const int32_t*>(dm + part_cores + part_fins),
-                            reinterpret_cast<const StepFinish*>(dm + part_cores), &fast_done);
+        rc = launch_mixture(e, mix);
         for (int j = 0; j < ng; ++j) {           // (bookkeeping under the device work: everything is enqueued)
             const int i = go[j];
             commit_src_sync(e, cur_slots[i], cand_slots[i], changed_objects ? changed_objects + rows_ptr[i] : nullptr, rows_ptr[i + 1] - rows_ptr[i]);
@@ -1046,8 +1048,9 @@ int sbe_step_delta(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* mo
     commit_ids_sync(e, cur_slot, cand_slot, e->step_moved);
     StepFinish fin = make_step_finish(e);
     DoneSig done;
-    rc = launch_mixture(e, cand_slot, 1, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, nullptr, nullptr, &fin, nullptr, nullptr,
-                        nullptr, &done);
+    MixCall mix;
+    mix.first_slot = cand_slot; mix.fin = &fin; mix.done_out = &done;
+    rc = launch_mixture(e, mix);
     if (rc) return rc;
     rc = wait_done(e, done);
     if (rc) return rc;
@@ -1153,8 +1156,9 @@ int sbe_gibbs_step(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* ob
     fin.lq_partials[0] = d_part_f; fin.lq_partials[1] = d_part_b; fin.lq_n[0] = fin.lq_n[1] = nblk;
     fin.lq_out = reinterpret_cast<double*>(e->d_step_host + step_host_lq_offset(e));
     DoneSig done;
-    rc = launch_mixture(e, cand_slot, 1, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS, nullptr, nullptr, &fin, nullptr, nullptr,
-                        nullptr, &done);
+    MixCall mix;
+    mix.first_slot = cand_slot; mix.fin = &fin; mix.done_out = &done;
+    rc = launch_mixture(e, mix);
     if (rc) return rc;
     rc = wait_done(e, done);
     if (rc) return rc;
@@ -1217,7 +1221,7 @@ static int step_general(sbe_engine* e, int cur_slot, int cand_slot, const uint8_
         e->d_counts + (int64_t)cand_slot * e->table_elems(), e->d_conc, e->d_step_pf, 0, e->Gtot, e->F, e->S, 1);
     k_group_sum_f32<<<div_up((int64_t)e->Gtot * 8, 64), 64, 0, e->stream>>>(e->d_step_pf, e->d_step_pg, e->Gtot, e->F);
     HIPCHK(e, hipGetLastError());
-    rc = enqueue_mixture(e, cand_slot, 1, e->opt_log == SBE_LOG_PRODUCT ? LOG_PRODUCT : LOG_PER_OBS);
+    rc = enqueue_mixture(e, cand_slot, 1);
     if (rc) return done(rc);
     // one read-back, one synchronisation
     const size_t pg_bytes = (size_t)e->Gtot * sizeof(double);

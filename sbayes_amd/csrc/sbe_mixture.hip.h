@@ -14,9 +14,6 @@ namespace sbe {
 //                 binary exponent is stripped with integer ops; one fp64 log per thread (see ProdAcc)
 enum MixMode : int { LOG_PER_OBS = 0, LOG_PRODUCT = 1, WRITE_OBS = 2 };
 
-constexpr int kRowsBlock = 1024;
-constexpr int kRowsWaves = kRowsBlock / kWave;
-
 struct Mix2Params {
     int N, NQ, Np, F, Fq, S, C, Gtot, P;
     int n_ftiles, quads_per_chunk;
@@ -89,11 +86,6 @@ struct MfmaMixParams {
     DoneSig done;
 };
 
-// waves per block of k_mixture_tuple64.  (8-wave blocks -- twice the waves per SIMD at the same LDS footprint -- were
-// measured twice: 72.7 us at 80 VGPRs / 3 blocks per CU, 107 us at 64 VGPRs / 4 blocks per CU, against 61-63 us: the
-// kernel does not fit those register budgets without spilling in its table build.)
-constexpr int tuple64_waves() { return 4; }
-
 // Launchers (sbe_mixture.hip): pick the template instance for (mode, tile width, component count) and enqueue it.
 // mode: LOG_PER_OBS / LOG_PRODUCT; ft: 64 / 32 / 16; C: components (1..4 compile-time instances, else the runtime form).
 void launch_v2(int mode, int ft, int C, const Mix2Params& p, dim3 grid, size_t lds, hipStream_t st, bool direct);
@@ -106,17 +98,13 @@ void launch_rowsort(const uint16_t* gid, const uint8_t* pid, uint32_t* out, int3
                     int64_t out_stride, int first_slot, const int32_t* slot_list, int n_slots, int N, int Np, int C, int Gtot, int Pmax,
                     uint32_t row_bytes, uint32_t state_pitch, int step_objects, hipStream_t st);
 void launch_state_s(const uint8_t* state, uint8_t* state_s, int N, int F, int Fp, int pitch, int S, hipStream_t st);
-// sbe_mixture_mfma.hip
-constexpr int kTupleMfmaKBlockObjects = 64;       // objects per k-block of the FP4 count contraction
-int tuple_mfma_slots_per_block(int KT);           // 16 (KT <= 8) / 4 (<= 32) / 2 (<= 64): the MOST slots per block KT tuples allow; 0: the form does not apply
+// sbe_mixture_mfma.hip (its block shape and LDS size: sbe_mixture_plan.h)
 void launch_xt_frags(const uint8_t* state, uint8_t* xt, int N, int F, int S, int Fp, int NT, int KBp, hipStream_t st);
 size_t column_tables_bytes(int NT);               // colcount | colfeat | tile_prefix (MfmaMixParams), one allocation
 void launch_column_tables(const uint8_t* state, int32_t* out, int N, int F, int S, int Fp, int NT, hipStream_t st);
-size_t tuple_mfma_lds_bytes(int MT, int C, int KBp);
 void fine_log_table(double* tab);                 // [2 * 1024] {1/c, log c} of k_mixture_tuple_mfma's log (sbe_mixture_mfma.hip)
 // false (nothing launched): an instance of the kernel carries static LDS, so its dynamic block does not start at address 0
 bool launch_tuple_mfma(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st);
 bool tuple_mfma_shared();                        // the shared-operand epilogue where it applies (SBE_MFMA_SHARED=0: never); fixed for the process
-constexpr int kTupleMfmaColsPerPass = 2;          // column tiles a wave of k_mixture_tuple_mfma owns per pass (= columns per lane)
 
 }  // namespace sbe

@@ -591,11 +591,6 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
     signal_done(p.done);
 }
 
-size_t tuple_mfma_lds_bytes(int MT, int C, int KBp) {     // log table | A fragments | meta (32 MT entries whatever the form) | reduction
-    const size_t meta = (size_t)32 * MT * (C <= 1 ? 8 : (C <= 3 ? 16 : 32));
-    return (size_t)MT * KBp * 1024 + kFineLogEntries * 16 + meta + (size_t)kMfmaWaves * 2 * 16 * sizeof(double);
-}
-
 // entries per epilogue step: a whole register quad where the registers allow it, half a quad for the widest instances
 template <int MT, int CT> constexpr int mfma_gt() { return (MT >= 4 || (MT == 3 && CT >= 3)) ? 2 : 4; }
 
@@ -620,7 +615,7 @@ static void launch_mfma_mt(int C, const MfmaMixParams& p, dim3 grid, size_t lds,
 template <int MT, int CT, int SLB, bool SHARE = false>
 static bool allow_lds() {
     const void* fn = reinterpret_cast<const void*>(&k_mixture_tuple_mfma<MT, CT, mfma_gt<MT, CT>(), SLB, SHARE>);
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     hipFuncAttributes attr{};
     if (hipFuncGetAttributes(&attr, fn) != hipSuccess) { (void)hipGetLastError(); return true; }   // (not answerable: the kernel's own guard stays)
     return attr.sharedSizeBytes == 0;
@@ -646,12 +641,6 @@ bool tuple_mfma_shared() {
     return on;
 }
 
-// slots per block for KT tuples (0: the form does not apply): 16 up to 8 tuples, 4 up to 32, 2 up to 64
-int tuple_mfma_slots_per_block(int KT) {
-    if (KT < 1 || KT > 64) return 0;
-    return KT <= 8 ? 16 : KT <= 32 ? 4 : 2;
-}
-
 template <int SLB>
 static void launch_mfma_slb(int MT, int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
     switch (MT) {
@@ -665,7 +654,7 @@ static void launch_mfma_slb(int MT, int C, const MfmaMixParams& p, dim3 grid, si
 bool launch_tuple_mfma(int C, const MfmaMixParams& p, dim3 grid, size_t lds, hipStream_t st) {
     static const bool no_static_lds = [] { bool ok = allow_lds_all<4>(); ok &= allow_lds_all<2>(); ok &= allow_lds_all<1>(); return ok; }();
     if (!no_static_lds) return false;
-    const int SL = p.SL;                                 // (chosen by the host: mfma_geometry)
+    const int SL = p.SL;                                 // (chosen by the host: plan_mixture)
     const int MT = (p.KT + 32 / SL - 1) / (32 / SL);
     if (SL == 16) launch_mfma_slb<4>(MT, C, p, grid, lds, st);
     else if (SL == 4) launch_mfma_slb<2>(MT, C, p, grid, lds, st);

@@ -13,7 +13,6 @@ typedef float v16f_t __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const v4i_t lds_cv4i_t;
 
 constexpr int kMfmaSlots = 16;          // slots per block in the narrow form (<= 8 tuples); wide forms: 4 (<= 32 tuples), 2 (<= 64)
-constexpr int kMfmaWaves = 8;
 constexpr int kMfmaThreads = kMfmaWaves * kWave;
 
 // Table-driven log for this kernel's epilogue, G chains interleaved: log v = k ln2 + log c_i + log1p(r), r = m / c_i - 1, with
@@ -30,7 +29,6 @@ constexpr int kMfmaThreads = kMfmaWaves * kWave;
 // probability ~1 has a log-likelihood of ~0, which the reference gets to its own rounding: tools/fuzz_gpu.py checks to
 // 1e-10 relative + 1e-16 per observation, and caught a first form that summed k ln2 and log m apart without the split:
 // 2e-12 off at a log-likelihood of 1e-5).
-constexpr int kFineLogEntries = 1024;
 constexpr int kFineLogSplit = 424;                                        // 1 + 424/1024 = 1.4140625 ~ sqrt(2)
 constexpr uint32_t kFineLogCarry = 0x00100000u - ((uint32_t)kFineLogSplit << 10);
 // (round 6: the exponent comes back BIASED -- (hi + carry) >> 20, no "- 1023" per entry: the caller takes 1023 x the column's
