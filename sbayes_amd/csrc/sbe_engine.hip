@@ -944,8 +944,8 @@ static int collapsed_groups(sbe_engine* e, int slot, int g_lo, int G, float* d_p
     int rc = ensure_io(e, (size_t)G * sizeof(double));
     if (rc) return rc;
     const int32_t* counts = e->d_counts + (int64_t)slot * e->table_elems();
-    const size_t lds = (size_t)e->F * e->S * sizeof(double) + (size_t)e->F * sizeof(float);
-    if (lds <= ((size_t)96 << 10)) {
+    const size_t lds = collapsed_lds_bytes(e);
+    if (lds <= kCollapsedLdsMax) {
         const DoneSig done = next_done(e, (unsigned)G);
         k_collapsed_groups<int32_t><<<G, 1024, lds, e->stream>>>(counts, e->d_conc, e->d_lg_conc, e->d_sum_a, e->d_lg_sum_a, d_pf,
                                                                   (double*)e->d_io, g_lo, e->F, e->S, done);
@@ -953,32 +953,24 @@ static int collapsed_groups(sbe_engine* e, int slot, int g_lo, int G, float* d_p
         rc = wait_done(e, done);
         if (rc) return rc;
         return synced(e);
-    } else {
-        float* pf = d_pf;
-        if (!pf) {
-            rc = ensure_scratch(e, (size_t)G * e->F * sizeof(float));
-            if (rc) return rc;
-            pf = (float*)e->d_scratch;
-        }
-        k_dcl<int32_t><<<div_up((int64_t)G * e->F, 256), 256, 0, e->stream>>>(counts, e->d_conc, pf, g_lo, g_lo + G, e->F, e->S, 1);
-        HIPCHK(e, hipGetLastError());
-        k_group_sum_f32<<<div_up((int64_t)G * 8, 64), 64, 0, e->stream>>>(pf, (double*)e->d_io, G, e->F);
-        HIPCHK(e, hipGetLastError());
     }
+    if (!d_pf) {
+        rc = ensure_scratch(e, (size_t)G * e->F * sizeof(float));
+        if (rc) return rc;
+        d_pf = (float*)e->d_scratch;
+    }
+    rc = enqueue_dcl(e, counts, e->d_conc, 1, g_lo, G, d_pf, (double*)e->d_io);
+    if (rc) return rc;
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return synced(e);
 }
 
 int sbe_collapsed_loglik_all(sbe_engine* e, int slot, double* per_group_out) {
     CHECK_ENGINE(e); CHECK_SLOT(e, slot); CHECK_PTR(e, per_group_out);
-    Slot& s = e->slots[slot];
-    for (int c = 0; c < e->C; ++c) {
-        if (e->G[c] == 0) continue;
-        if (!s.counts_set[c]) return fail(e, SBE_ERR_STATE, "slot %d: counts of component %d not set", slot, c);
-        if (!e->conc_set[c]) return fail(e, SBE_ERR_STATE, "concentration of component %d not set", c);
-    }
+    int rc = check_collapsed_ready(e, slot, 0, e->C);
+    if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    int rc = collapsed_groups(e, slot, 0, e->Gtot, nullptr);
+    rc = collapsed_groups(e, slot, 0, e->Gtot, nullptr);
     if (rc) return rc;
     memcpy(per_group_out, e->h_io, (size_t)e->Gtot * sizeof(double));
     return SBE_OK;
@@ -988,13 +980,11 @@ int sbe_collapsed_loglik(sbe_engine* e, int slot, int component, double* per_gro
     CHECK_ENGINE(e); CHECK_SLOT(e, slot); CHECK_COMP(e, component);
     if (e->G[component] == 0) return SBE_OK;       // no group: Likelihood.compute_lh_clusters sums an empty cache
     CHECK_PTR(e, per_group_out);
-    Slot& s = e->slots[slot];
-    if (!s.counts_set[component]) return fail(e, SBE_ERR_STATE, "slot %d: counts of component %d not set", slot, component);
-    if (!e->conc_set[component]) return fail(e, SBE_ERR_STATE, "concentration of component %d not set", component);
+    int rc = check_collapsed_ready(e, slot, component, component + 1);
+    if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     const int G = e->G[component], g_lo = e->goff[component];
     float* d_pf = nullptr;
-    int rc = SBE_OK;
     if (per_feature_out) {
         rc = ensure_scratch(e, (size_t)G * e->F * sizeof(float));
         if (rc) return rc;

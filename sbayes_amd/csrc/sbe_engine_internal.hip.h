@@ -870,6 +870,33 @@ int check_slot_ready(sbe_engine* e, int slot, bool need_weights) {
     return SBE_OK;
 }
 
+// ---- collapsed likelihood (sbe_dirichlet.hip.h) ---------------------------------------------------------------------
+// what a7 / a8 of the components [c_lo, c_hi) of a slot read: their counts and concentrations (a component without groups: nothing)
+int check_collapsed_ready(sbe_engine* e, int slot, int c_lo, int c_hi) {
+    Slot& s = e->slots[slot];
+    for (int c = c_lo; c < c_hi; ++c) {
+        if (e->G[c] == 0) continue;
+        if (!s.counts_set[c]) return fail(e, SBE_ERR_STATE, "slot %d: counts of component %d not set", slot, c);
+        if (!e->conc_set[c]) return fail(e, SBE_ERR_STATE, "concentration of component %d not set", c);
+    }
+    return SBE_OK;
+}
+
+// the one-launch form (k_collapsed_groups, k_collapsed_source_prior): a group's F*S terms and F rows in LDS, within this budget
+constexpr size_t kCollapsedLdsMax = (size_t)96 << 10;
+inline size_t collapsed_lds_bytes(const sbe_engine* e) { return (size_t)e->F * e->S * sizeof(double) + (size_t)e->F * sizeof(float); }
+
+// the two-launch form: k_dcl's float32 rows of the groups [g_lo, g_lo + G) into d_pf, then (d_pg given) their per-group sums
+template <class TC>
+int enqueue_dcl(sbe_engine* e, const TC* counts, const double* conc, int conc_per_group, int g_lo, int G, float* d_pf, double* d_pg) {
+    k_dcl<TC><<<div_up((int64_t)G * e->F, 256), 256, 0, e->stream>>>(counts, conc, d_pf, g_lo, g_lo + G, e->F, e->S, conc_per_group);
+    HIPCHK(e, hipGetLastError());
+    if (!d_pg) return SBE_OK;
+    k_group_sum_f32<<<div_up((int64_t)G * 8, 64), 64, 0, e->stream>>>(d_pf, d_pg, G, e->F);
+    HIPCHK(e, hipGetLastError());
+    return SBE_OK;
+}
+
 // ---- matrix-pipe form of the group-tuple kernel (sbe_mixture_mfma.hip) ---------------------------------------------
 // The one-hot block in MFMA fragment order, built once, at the first launch that wants it: [NT + 1][KBp] fragments of
 // 1 KB (tile NT and the PF fragments behind it are zero: what the kernel reads instead of branching on bounds).

@@ -723,21 +723,17 @@ int sbe_source_prior(sbe_engine* e, int slot, double* per_object_out) {
 int sbe_collapsed_and_source_prior(sbe_engine* e, int slot, double* per_group_out, double* per_object_out) {
     CHECK_ENGINE(e); CHECK_SLOT(e, slot); CHECK_PTR(e, per_group_out); CHECK_PTR(e, per_object_out);
     Slot& s = e->slots[slot];
-    for (int c = 0; c < e->C; ++c) {
-        if (e->G[c] == 0) continue;
-        if (!s.counts_set[c]) return fail(e, SBE_ERR_STATE, "slot %d: counts of component %d not set", slot, c);
-        if (!e->conc_set[c]) return fail(e, SBE_ERR_STATE, "concentration of component %d not set", c);
-    }
+    int rc = check_collapsed_ready(e, slot, 0, e->C);
+    if (rc) return rc;
     if (!s.groups_set || !s.source_set || !s.weights_set) return fail(e, SBE_ERR_STATE, "slot %d: groups / source / weights not set", slot);
-    const size_t lds = (size_t)e->F * e->S * sizeof(double) + (size_t)e->F * sizeof(float);
+    const size_t lds = collapsed_lds_bytes(e);
     const size_t gb = al256((size_t)e->Gtot * sizeof(double)), out_bytes = gb + (size_t)e->N * sizeof(double);
-    if (e->Gtot == 0 || lds > ((size_t)96 << 10) || out_bytes > kMappedOutMax || !poll_done_enabled()) {
-        int rc = sbe_collapsed_loglik_all(e, slot, per_group_out);
+    if (e->Gtot == 0 || lds > kCollapsedLdsMax || out_bytes > kMappedOutMax || !poll_done_enabled()) {
+        rc = sbe_collapsed_loglik_all(e, slot, per_group_out);
         if (rc) return rc;
         return sbe_source_prior(e, slot, per_object_out);
     }
     HIPCHK(e, hipSetDevice(e->device));
-    int rc = SBE_OK;
     if (s.patterns_dirty) { rc = upload_patterns_and_weights(e, slot); if (rc) return rc; }
     rc = ensure_io(e, out_bytes);
     if (rc) return rc;

@@ -68,11 +68,9 @@ int sbe_dirichlet_logpdf(sbe_engine* e, const float* counts, int n_groups, const
     double* d_pg = (double*)(e->d_scratch + cb + ab + pf);
     { int _urc = upload(e, d_cnt, counts, (size_t)n * sizeof(float)); if (_urc) return _urc; }
     { int _urc = upload(e, d_a, conc, (size_t)(conc_per_group ? n : fs) * sizeof(double)); if (_urc) return _urc; }
-    k_dcl<float><<<div_up((int64_t)n_groups * e->F, 256), 256, 0, e->stream>>>(d_cnt, d_a, d_pf, 0, n_groups, e->F, e->S, conc_per_group ? 1 : 0);
-    HIPCHK(e, hipGetLastError());
+    rc = enqueue_dcl(e, d_cnt, d_a, conc_per_group ? 1 : 0, 0, n_groups, d_pf, per_group_out ? d_pg : nullptr);
+    if (rc) return rc;
     if (per_group_out) {
-        k_group_sum_f32<<<div_up((int64_t)n_groups * 8, 64), 64, 0, e->stream>>>(d_pf, d_pg, n_groups, e->F);
-        HIPCHK(e, hipGetLastError());
         rc = d2h(e, per_group_out, d_pg, (size_t)n_groups * sizeof(double));
         if (rc) return rc;
     }

@@ -1217,10 +1217,8 @@ static int step_general(sbe_engine* e, int cur_slot, int cand_slot, const uint8_
     rc = check_after(e, ST_BAD_NORMALIZE);
     if (rc) return done(rc);
     // collapsed likelihood of every group (a7/a8) into a device buffer
-    k_dcl<int32_t><<<div_up((int64_t)e->Gtot * e->F, 256), 256, 0, e->stream>>>(
-        e->d_counts + (int64_t)cand_slot * e->table_elems(), e->d_conc, e->d_step_pf, 0, e->Gtot, e->F, e->S, 1);
-    k_group_sum_f32<<<div_up((int64_t)e->Gtot * 8, 64), 64, 0, e->stream>>>(e->d_step_pf, e->d_step_pg, e->Gtot, e->F);
-    HIPCHK(e, hipGetLastError());
+    rc = enqueue_dcl(e, e->d_counts + (int64_t)cand_slot * e->table_elems(), e->d_conc, 1, 0, e->Gtot, e->d_step_pf, e->d_step_pg);
+    if (rc) return done(rc);
     rc = enqueue_mixture(e, cand_slot, 1);
     if (rc) return done(rc);
     // one read-back, one synchronisation

@@ -415,6 +415,16 @@ __global__ void k_probs(const TC* __restrict__ counts, const double* __restrict_
 // a5: per-pattern normalised weights (likelihood.py:171-190).  One thread per (pattern, f).
 //   w = pattern * weights (bool x float32 -> float32);  w /= sum_c w   (float32, NumPy order)
 // ------------------------------------------------------------------------------------------
+// One row of it, the weights read through `w` (memory, or an array the caller loaded): v_c = m_c / np_sum(m) with
+// m_c = bit c of `bits` ? w_c : 0 * w_c -- NumPy's bool * float32, so a NaN or inf under a cleared bit still reaches the sum.
+// The register forms (weight_tables_z_row_reg, the Gibbs kernels) restate it on statically indexed values for speed.
+template <class Emit>
+__device__ __forceinline__ void normalized_weights_row(const float* w, uint32_t bits, int C, Emit emit) {
+    auto masked = [&](int c) -> float { return ((bits >> c) & 1u) ? w[c] : 0.0f * w[c]; };
+    const float total = np_pairwise_sum<float>(masked, C);
+    for (int c = 0; c < C; ++c) emit(c, masked(c) / total);
+}
+
 // Optional extras of the slot form (one launch per sbe_set_weights): `weights_keep` = the slot's resident [F][C] copy
 // of `weights` (which may then be host-mapped staging memory), `wpat_t` = the tile-transposed float64 copy
 // [n_ftiles][Pmax][C][ft], exact widening (what the fused kernels read; padding features stay zero from creation).
@@ -433,15 +443,12 @@ __device__ __forceinline__ void weight_patterns_item(int i, const WeightPatternA
     float w[kMaxComponents];
     for (int c = 0; c < C; ++c) w[c] = a.weights[(int64_t)f * C + c];
     if (a.weights_keep && p == 0) for (int c = 0; c < C; ++c) a.weights_keep[(int64_t)f * C + c] = w[c];
-    auto masked = [&](int c) -> float { return ((bits >> c) & 1u) ? w[c] : 0.0f * w[c]; };
-    const float total = np_pairwise_sum<float>(masked, C);
     float* out = a.wpat + ((int64_t)p * F + f) * C;
     double* out_t = a.wpat_t ? a.wpat_t + (((int64_t)(f / a.ft) * a.Pmax + p) * C) * a.ft + f % a.ft : nullptr;
-    for (int c = 0; c < C; ++c) {
-        const float v = masked(c) / total;
+    normalized_weights_row(w, bits, C, [&](int c, float v) {
         out[c] = v;
         if (out_t) out_t[(int64_t)c * a.ft] = (double)v;
-    }
+    });
 }
 static __global__ void k_weight_patterns(const float* __restrict__ weights /* [F][C] */,
                                   const uint32_t* __restrict__ pattern_bits /* [P] */,
@@ -510,10 +517,8 @@ static __global__ void k_normalize_weight_rows(const float* __restrict__ weights
         if (n >= N) break;
         const uint32_t b = bits[r];
         const float* w = (stage_weights ? nw_lds : weights) + f * C;
-        auto masked = [&](int c) -> float { return ((b >> c) & 1u) ? w[c] : 0.0f * w[c]; };
-        const float total = np_pairwise_sum<float>(masked, C);
         float* o = out + ((int64_t)n * F + f) * C;
-        for (int c = 0; c < C; ++c) o[c] = masked(c) / total;
+        normalized_weights_row(w, b, C, [&](int c, float v) { o[c] = v; });
     }
     signal_done(done);
 }
@@ -664,91 +669,6 @@ static __global__ void k_lh_exact(const uint8_t* __restrict__ state, const uint8
 }
 
 // ------------------------------------------------------------------------------------------
-// a7 + a8: collapsed Dirichlet-categorical log-pdf (util.py:1373-1394, likelihood.py:65-101).
-// k_dcl: one thread per (group, feature):
-//   float32( lgamma(sum a) - lgamma(n + sum a) + sum_{s: a>0} (lgamma(c + a) - lgamma(a)) )
-// k_group_sum_f32: one thread per group: float32 NumPy-order sum over features -> float64 cache.
-// ------------------------------------------------------------------------------------------
-template <class TC>
-__global__ void k_dcl(const TC* __restrict__ counts, const double* __restrict__ conc_in,
-                      float* __restrict__ per_feature, int g_lo, int g_hi, int F, int S, int conc_per_group) {
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= (int64_t)(g_hi - g_lo) * F) return;
-    const int64_t base = ((int64_t)g_lo * F + row) * S;
-    // concentration either per group [G][F][S] or one [F][S] table broadcast over groups
-    const double* conc = conc_per_group ? conc_in : conc_in - base + (row % F) * (int64_t)S;
-    auto cnt = [&](int s) -> float { return (float)counts[base + s]; };
-    auto a = [&](int s) -> double { return conc[base + s]; };
-    const float n = np_pairwise_sum<float>(cnt, S);
-    const double sum_a = np_pairwise_sum<double>(a, S);
-    const double cst = sbe_lgamma_pos(sum_a) - sbe_lgamma_pos((double)n + sum_a);
-    auto series = [&](int s) -> double {
-        const double as = conc[base + s];
-        return as > 0.0 ? sbe_lgamma_pos((double)(float)counts[base + s] + as) - sbe_lgamma_pos(as) : 0.0;
-    };
-    per_feature[row] = (float)(cst + np_pairwise_sum<double>(series, S));
-}
-
-static __global__ void k_group_sum_f32(const float* __restrict__ per_feature, double* __restrict__ per_group,
-                                int n_groups, int F) {
-    // one group per octet of lanes (np_pairwise_sum_f32_x8: NumPy's order, an eighth of the dependent chain)
-    const int g = (blockIdx.x * blockDim.x + threadIdx.x) >> 3;
-    if (g >= n_groups) return;
-    const float* p = per_feature + (int64_t)g * F;
-    auto get = [&](int i) -> float { return p[i]; };
-    const float total = np_pairwise_sum_f32_x8(get, F, (int)(threadIdx.x & 7));
-    if ((threadIdx.x & 7) == 0) per_group[g] = (double)total;
-}
-
-// a7 + a8 in ONE launch (round 3: the drop-in Likelihood.__call__ asks for this once or twice per MCMC step, and a
-// launch costs more than the arithmetic): block = one group.  Phase 1, one thread per table element: the lgamma term
-// of the element, with k_conc_lgamma's count-independent tables (ONE lgamma per element -- same function, same
-// arguments as k_dcl's two, so the same value); phase 2, one thread per feature: the ordered sums over the S states,
-// the row constant, the float32 cast (k_dcl's expression); phase 3, eight lanes: the float32 NumPy-order sum over the
-// features (k_group_sum_f32's).  Dynamic LDS: F*S doubles + F floats.  `per_feature` (may be null) gets the rows.
-template <class TC>
-__device__ __forceinline__ void collapsed_group_block(
-    const TC* __restrict__ counts, const double* __restrict__ conc, const double* __restrict__ lg_conc,
-    const double* __restrict__ sum_a, const double* __restrict__ lg_sum_a, float* __restrict__ per_feature,
-    double* __restrict__ per_group, int g_lo, int F, int S, int block /* = group - g_lo */, unsigned char* cg_lds) {
-    double* ser = reinterpret_cast<double*>(cg_lds);                       // [F][S]
-    float* pf = reinterpret_cast<float*>(cg_lds + (size_t)F * S * sizeof(double));   // [F]
-    const int g = g_lo + block;
-    const int64_t gbase = (int64_t)g * F * S;
-    for (int e = threadIdx.x; e < F * S; e += blockDim.x) {
-        const double as = conc[gbase + e];
-        ser[e] = as > 0.0 ? sbe_lgamma_pos((double)(float)counts[gbase + e] + as) - lg_conc[gbase + e] : 0.0;
-    }
-    __syncthreads();
-    for (int f = threadIdx.x; f < F; f += blockDim.x) {
-        const int64_t base = gbase + (int64_t)f * S;
-        auto cnt = [&](int k) -> float { return (float)counts[base + k]; };
-        auto ser_at = [&](int k) -> double { return ser[f * S + k]; };
-        const float n = np_pairwise_sum<float>(cnt, S);
-        const double sa = sum_a[(int64_t)g * F + f];
-        const double cst = lg_sum_a[(int64_t)g * F + f] - sbe_lgamma_pos((double)n + sa);
-        const float v = (float)(cst + np_pairwise_sum<double>(ser_at, S));
-        pf[f] = v;
-        if (per_feature) per_feature[(int64_t)block * F + f] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        auto get = [&](int i) -> float { return pf[i]; };
-        const float total = np_pairwise_sum_f32_x8(get, F, (int)threadIdx.x);
-        if (threadIdx.x == 0) per_group[block] = (double)total;
-    }
-}
-template <class TC>
-__global__ __launch_bounds__(1024) void k_collapsed_groups(
-    const TC* __restrict__ counts, const double* __restrict__ conc, const double* __restrict__ lg_conc,
-    const double* __restrict__ sum_a, const double* __restrict__ lg_sum_a, float* __restrict__ per_feature,
-    double* __restrict__ per_group, int g_lo, int F, int S, DoneSig done = DoneSig{}) {
-    extern __shared__ __align__(16) unsigned char cg_lds[];
-    collapsed_group_block<TC>(counts, conc, lg_conc, sum_a, lg_sum_a, per_feature, per_group, g_lo, F, S, (int)blockIdx.x, cg_lds);
-    signal_done(done);
-}
-
-// ------------------------------------------------------------------------------------------
 // a6, per-observation form: obs[n][f] = sum_c w[pat(n)][f][c] * lh_c(n, f)   (loggers.py:355-357,
 // operators.py:568-574, 1060-1061) with lh = 1 for NA observations (the reference multiplies the
 // weights by likelihood_per_component's NA value 1) and lh = 0 for "no group".  Dense output
@@ -878,5 +798,6 @@ static __global__ void k_rowoff(const uint16_t* __restrict__ gid, const uint8_t*
 
 }  // namespace sbe
 
+#include "sbe_dirichlet.hip.h"
 #include "sbe_kernels_operators.hip.h"
 #include "sbe_kernels_sampling.hip.h"

@@ -21,21 +21,7 @@ namespace sbe {
 //   wcur  = normalize( normalize_weights(weights, pattern) ** (1/T_prior) )
 //   wflip = normalize_weights( weights ** (1/T_prior), pattern with the cluster bit flipped )
 // float32 throughout, NumPy reduction order; x ** 1.0 is exact, other exponents go through powf.
-// One (pattern, feature) row of those tables: wc[c] = wcur, wf[c] = wflip.
-__device__ __forceinline__ void weight_tables_z_row(const float* __restrict__ w, uint32_t bits, int C, float inv_tp,
-                                                    int use_pow, float* wc, float* wf) {
-    const uint32_t fbits = bits ^ 1u;
-    auto masked = [&](int c) -> float { return ((bits >> c) & 1u) ? w[c] : 0.0f * w[c]; };
-    const float tot = np_pairwise_sum<float>(masked, C);
-    auto powd = [&](int c) -> float { const float a = masked(c) / tot; return use_pow ? powf(a, inv_tp) : a; };
-    const float tot2 = np_pairwise_sum<float>(powd, C);
-    auto fl = [&](int c) -> float {
-        const float pw = use_pow ? powf(w[c], inv_tp) : w[c];
-        return ((fbits >> c) & 1u) ? pw : 0.0f * pw;
-    };
-    const float tot3 = np_pairwise_sum<float>(fl, C);
-    for (int c = 0; c < C; ++c) { wc[c] = powd(c) / tot2; wf[c] = fl(c) / tot3; }
-}
+// One (pattern, feature) row of those tables, wc[c] = wcur, wf[c] = wflip: weight_tables_z_row_reg below.
 
 // Tables a resident operator call builds for itself (sbe_cluster_posterior_marginals, sbe_jump_lh_resident; one launch per
 // call): k_cluster_marginals_ws / k_jump_lh_ws below.  A block is 16 waves with two jobs.  Waves
@@ -78,10 +64,10 @@ __device__ __forceinline__ void ws_build_rows(const InlineTables& tin, float* __
     }
 }
 
-// The same row computed in REGISTERS (C <= CM < 8: NumPy's sum of fewer than eight terms is the plain left-to-right chain):
-// the C weights are loaded once, together, and every intermediate is a statically indexed register.  The general form
-// above reads w[c] from memory inside loops with a run-time trip count -- a dozen loads, each waited for before the
-// next -- which was 11 of the 19 us of the fused marginals kernel (profiles/r4/ws_kernel_clock.log).  Same arithmetic.
+// The row of the weight tables above, computed in REGISTERS (C <= CM <= 8: one NumPy leaf, np_sum_regs): the C weights are
+// loaded once, together, and every intermediate is a statically indexed register.  A form that read w[c] from memory
+// inside loops with a run-time trip count -- a dozen loads, each waited for before the next -- was 11 of the 19 us of
+// the fused marginals kernel (profiles/r4/ws_kernel_clock.log) and is gone; the masked sum is normalized_weights_row's.
 template <int CM>
 __device__ __forceinline__ void weight_tables_z_row_reg(const float* __restrict__ w, uint32_t bits, int C, float inv_tp, int use_pow,
                                                         float (&wc)[CM], float (&wf)[CM]) {
@@ -281,7 +267,7 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
 //     stay(n,f)    = p_conf + wh(n)[f][0] * p_source[f][x]                          float32 (mul, then add)
 //     jump(n,f)    = p_conf + wh(n)[f][0] * p_target[f][x]
 //     out[0][i]    = sum_{f not NA} log stay,   out[1][i] = sum_{f not NA} log jump  (fp64 logs and sums)
-// wh = normalize(update_weights(sample) ** (1/T_prior)) (the `wcur` of weight_tables_z_row), x = the observed state.
+// wh = normalize(update_weights(sample) ** (1/T_prior)) (the `wcur` of weight_tables_z_row_reg), x = the observed state.
 // The float32 arithmetic is the reference's, operation for operation; only the product over features -- np.prod in
 // float32 there, which underflows to 0 beyond F ~ 75 -- is replaced by a sum of logs.  `pconf` are the
 // caller's tempered tables of every confounder group (global group index minus the cluster count), `p_source` /

@@ -593,25 +593,6 @@ static __global__ void k_multi_copy(CopySegs cs) {
 //   weight blocks: normalised weights per pattern (from the payload's / the current slot's weights and patterns)
 //   copy blocks  : the other per-slot arrays, current slot or payload -> candidate (k_step_apply without counts)
 // ------------------------------------------------------------------------------------------
-// lgamma terms of the concentration tables that do not depend on the counts (one-call steps, round 3): per element
-// lgamma(conc) (0 where conc <= 0: that state is not applicable), per (group, feature) row sum_a = the NumPy-order sum
-// of the row and lgamma(sum_a).  Built once per sbe_set_concentration; k_step_core then evaluates ONE lgamma per
-// element and per row instead of two (same function, same arguments: the values are the ones it computed itself).
-static __global__ void k_conc_lgamma(const double* __restrict__ conc, double* __restrict__ lg_conc, double* __restrict__ sum_a,
-                              double* __restrict__ lg_sum_a, int g_lo, int g_hi, int F, int S) {
-    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= (int64_t)(g_hi - g_lo) * F) return;
-    const int64_t r = (int64_t)g_lo * F + row, base = r * S;
-    for (int s = 0; s < S; ++s) {
-        const double a = conc[base + s];
-        lg_conc[base + s] = a > 0.0 ? sbe_lgamma_pos(a) : 0.0;
-    }
-    auto conc_at = [&](int k) -> double { return conc[base + k]; };
-    const double sa = np_pairwise_sum<double>(conc_at, S);
-    sum_a[r] = sa;
-    lg_sum_a[r] = sbe_lgamma_pos(sa);
-}
-
 struct StepCore {
     // copy blocks
     CopySegs cs; int src_seg;
@@ -697,7 +678,7 @@ __device__ __forceinline__ void step_core_body(const StepCore& a, unsigned char*
             const float cf = (float)cn;
             const double conc = a.conc[gi];
             sh_post[e] = (double)cf + conc;
-            sh_ser[e] = conc > 0.0 ? sbe_lgamma_pos((double)cf + conc) - a.lg_conc[gi] : 0.0;
+            sh_ser[e] = dcat_state_term(cf, conc, a.lg_conc[gi]);
         }
         __syncthreads();
         for (int r = threadIdx.x; r < R; r += kBlock) {                              // ordered sums of a row
@@ -711,9 +692,8 @@ __device__ __forceinline__ void step_core_body(const StepCore& a, unsigned char*
             if (!(total > 0.0)) raise_status(a.status, ST_BAD_NORMALIZE, 1);
             sh_total[r] = total;
             const float n = np_pairwise_sum<float>(cnt_at, S);
-            const double sum_a = a.sum_a[(int64_t)g * F + f];
-            const double cst = a.lg_sum_a[(int64_t)g * F + f] - sbe_lgamma_pos((double)n + sum_a);
-            a.per_feature[(int64_t)g * F + f] = (float)(cst + np_pairwise_sum<double>(ser_at, S));
+            a.per_feature[(int64_t)g * F + f] = dcat_row(a.lg_sum_a[(int64_t)g * F + f], n, a.sum_a[(int64_t)g * F + f],
+                                                         np_pairwise_sum<double>(ser_at, S));
         }
         __syncthreads();
         for (int e = threadIdx.x; e < E; e += kBlock) {
@@ -731,19 +711,7 @@ __device__ __forceinline__ void step_core_body(const StepCore& a, unsigned char*
     if (wb < a.n_weight_blocks) {
         const int64_t j = (int64_t)wb * kBlock + threadIdx.x;
         if (j >= (int64_t)a.P * F) return;
-        const int p = (int)(j / F), f = (int)(j % F);
-        const uint32_t bits = a.pattern_bits[p];
-        const float* w = a.weights + (int64_t)f * C;
-        auto masked = [&](int c) -> float { return ((bits >> c) & 1u) ? w[c] : 0.0f * w[c]; };
-        const float total = np_pairwise_sum<float>(masked, C);
-        float* out = a.wpat + ((int64_t)p * F + f) * C;
-        const int tile = f / a.ft, tl = f % a.ft;
-        double* ot = a.wpat_t + (((int64_t)tile * a.Pmax + p) * C) * a.ft + tl;
-        for (int c = 0; c < C; ++c) {
-            const float v = masked(c) / total;
-            out[c] = v;
-            ot[(int64_t)c * a.ft] = (double)v;
-        }
+        weight_patterns_item((int)j, WeightPatternArgs{a.weights, a.pattern_bits, a.wpat, nullptr, a.wpat_t, a.P, F, C, a.Pmax, a.ft});
         return;
     }
     // copy blocks

@@ -1,8 +1,9 @@
 """The collapsed likelihood's per-feature term on the device, entry by entry against a 40-digit evaluation and form against
 form (the cases, the reference and the derived bound: tests/_collapsed_range_cases.py; tests/test_collapsed_range_cpu.py
-asserts without a device that the checker is right and sharp).  The term is written three times -- k_dcl (<float> behind
-sbe_dirichlet_logpdf, <int32_t> behind the resident calls of a wide table), collapsed_group_block (k_collapsed_groups,
-k_collapsed_source_prior) and the tile blocks of step_core_body -- and claims "same function, same arguments, same value":
+asserts without a device that the checker is right and sharp).  The term's routines (sbe_dirichlet.hip.h) have three callers
+-- k_dcl (<float> behind sbe_dirichlet_logpdf, <int32_t> behind the resident calls of a wide table), collapsed_group_block
+(k_collapsed_groups, k_collapsed_source_prior) and the tile blocks of step_core_body -- each with its own thread mapping, its
+own sums and (k_dcl: in place, the others: k_conc_lgamma's tables) its own source of lgamma(a); they must agree to the bit:
 
     1  Engine.dirichlet_logpdf, concentration shared and per group: every entry within the bound, +0.0 where E is exactly
        0, float32(E) on every sharp entry away from a midpoint;

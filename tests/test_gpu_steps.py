@@ -204,6 +204,55 @@ def test_one_call_steps_at_baseline_workloads(name):
         assert abs(lq - want_q) <= 3e-6 * abs(want_q) and abs(lqb - want_qb) <= 3e-6 * abs(want_qb)
 
 
+def test_step_weight_blocks_write_the_normalized_weights():
+    """The weight blocks of the one-call step, read back directly (the other tests see them through the mixture value):
+    F = 65 is a full 64-feature tile and a ragged one, four has_components patterns make P * F = 260 > 256, so two
+    weight blocks; objects 18..23 are in no cluster and the pattern (0, 1, 0) has a single component."""
+    N, F, S, n_groups = 24, 65, 3, [3, 1, 2]
+    C = len(n_groups)
+    rng = np.random.default_rng(65)
+    feats, groups, weights, source, conc = random_case(rng, N, F, S, n_groups, 0.03)
+    na = ~feats.any(-1)
+    clusters = np.zeros((3, N), dtype=bool)
+    for k in range(3):
+        clusters[k, 6 * k:6 * k + 6] = True
+    new_groups = [clusters] + groups[1:]
+    new_weights = rng.dirichlet(np.ones(C), size=F).astype(np.float32)
+    hc = orc.has_components(new_groups)
+    want = orc.normalize_weights(new_weights, hc)
+    patterns = {tuple(int(b) for b in row) for row in hc}
+    assert np.isfinite(want).all() and want.dtype == np.float32
+    assert patterns == {(0, 1, 0), (0, 1, 1), (1, 1, 0), (1, 1, 1)} and len(patterns) * F > 256
+    objs = np.arange(N, dtype=np.int32)                       # every object gets source rows over the components it now has
+    rows = np.eye(C, dtype=bool)[np.argmax(rng.random((N, F, C)) * hc[:, None, :], axis=-1)]
+    rows[na] = False
+
+    def load(eng, slot):
+        eng.load_state(slot, groups, weights, source=source)
+        for c in range(C):
+            eng.update_probs(slot, c)
+
+    with Engine(feats, n_groups, n_slots=3) as eng:
+        for c in range(C):
+            eng.set_concentration(c, conc[c])
+        load(eng, 0)
+        for form, cand in ((0, 1), (1, 2)):
+            eng.set_option(step_form=form)
+            eng.step(0, cand, clusters=clusters, changed_objects=objs, source_rows=rows, weights=new_weights)
+            assert np.array_equal(eng.weights_normalized(cand), want), ("step", form)
+        eng.set_option(step_form=0)
+    with Engine(feats, n_groups, n_slots=4) as eng:
+        for c in range(C):
+            eng.set_concentration(c, conc[c])
+        load(eng, 0)
+        load(eng, 2)
+        eng.step_batch(np.array([0, 2], dtype=np.int32), np.array([1, 3], dtype=np.int32), np.stack([clusters] * 2),
+                       np.ones(2, dtype=bool), np.array([0, N, 2 * N], dtype=np.int32), np.tile(objs, 2),
+                       np.concatenate([rows] * 2), np.stack([new_weights] * 2), np.ones(2, dtype=bool))
+        for cand in (1, 3):
+            assert np.array_equal(eng.weights_normalized(cand), want), ("step_batch", cand)
+
+
 # ---- batched multi-chain step (sbe_step_batch) -----------------------------------------------------------------
 def _batch_equals_single_steps(workload, B, n_sweeps, seed=8, distinct_states=None, expect_kernel=None):
     """B chains stepped by ONE sbe_step_batch call against B sbe_step calls and, at the end, the oracle."""
