@@ -427,6 +427,23 @@ class FakeEngine:
             return ids, sel, back, touched, rows
         return ids, sel, back
 
+    def given_unchanged_probs(self, slot, i_cluster, objects, hc_new, hc_old, temperature=1.0, prior_temperature=1.0,
+                              from_prior=False):
+        """(p, p_back) float32 [n, F, C] of given_unchanged_gibbs above: the two rows it draws from and looks the old source
+        up in, by the same expressions -- for tests that place uniforms on the steps of cumsum(p).  Not a call of the engine:
+        nothing is logged."""
+        objects = np.asarray(objects)
+        n_calls = len(self.calls)
+        lh = FakeEngine.given_unchanged_lh(self, slot, i_cluster, objects, temperature, prior_temperature)     # float32 [n, F, C]
+        del self.calls[n_calls:]
+        weights = self._slot(slot)["weights"]
+        inv_tp = 1 / float(prior_temperature)
+        probs = []
+        for hc in (hc_new, hc_old):
+            w = orc.normalize_weights(weights, np.asarray(hc, dtype=bool)) ** inv_tp
+            probs.append(w if from_prior else orc.normalize(w * lh, axis=-1))
+        return probs[0], probs[1]
+
     def gibbs_propose_supported(self):
         return True
 
