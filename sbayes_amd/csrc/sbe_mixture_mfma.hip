@@ -19,7 +19,7 @@
 // (row = (t & 1) * 16 + slot): the 32x32 accumulator layout (col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5))
 // then gives every lane ONE column and, per register quad, ONE tuple of four consecutive slots.  A wave owns pairs of
 // column tiles: 2 x MT accumulator tiles, A fragments from LDS (shared by all waves), X fragments straight from L2 in
-// 1 KB fully coalesced pieces (fragment order in memory), four k-blocks ahead.  Both operands take their k index from the
+// 1 KB fully coalesced pieces (fragment order in memory), three k-blocks ahead.  Both operands take their k index from the
 // same (lane half, byte) position, so the product does not depend on the instruction's internal k order.
 //
 // Operand format: FP4.  0 and 1.0 are exact in e2m1 (0x0, 0x2) and a count <= N < 2^24 is exact in an f32 accumulator, so
@@ -35,6 +35,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "sbe_mixture_mfma.hip.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
     // ---- column tiles of this wave; the first X fragments are asked for before anything else --------------------------
     // X fragments come through a buffer descriptor: lane-constant vector offset, scalar fragment offset, no address
     // arithmetic and no bounds branches -- a tile beyond the split's range reads the zero tile behind the array
-    // (index NT), and the PF fragments read ahead past a tile's last k-block are the next tile's first (discarded).
+    // (index NT), and the PF - 1 fragments read ahead past a tile's last k-block are the next tile's first (discarded).
     const int nt_lo = split * p.nt_per_split, nt_hi = min(p.NT, nt_lo + p.nt_per_split);
     constexpr int PF = 4;                         // k-blocks in flight (KBp is a multiple of PF)
     const __amdgpu_buffer_rsrc_t xt_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.xt), 0, (int)p.xt_bytes, 0x00020000);
@@ -188,12 +189,16 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         return;
     }
     // ---- phase 0: tuple metadata, log table, A fragments (sbe_mixture_mfma.hip.h) -----------------------------------------
-    mfma_phase0<MT, CT, decltype(slot_of), SL, !SHARE>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp);
-    // shared-operand form: the slot and step descriptors take the place of the per-tuple metadata (256 + 256 MT <= 512 MT bytes)
+    // shared-operand form: the slot and step descriptors take the place of the per-tuple metadata (256 + 256 MT <= 512 MT bytes);
+    // what they are built from is asked for here, ahead of phase 0's own loads
     static_assert(!SHARE || (SL == 16 && CT == 2 && MT <= 3), "the shared-operand epilogue: 16 slots, C = 2, <= 6 tuples");
     const uint4* sdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off);
     const uint4* tdesc = reinterpret_cast<const uint4*>(lds_raw + meta_off + SL * 16);
-    if constexpr (SHARE) mfma_shared_desc<MT, SL>(p, slot_of, const_cast<uint4*>(sdesc), const_cast<uint4*>(tdesc));
+    const int slot_mine = slot_of((int)threadIdx.x & (SL - 1));
+    SharedDescIn<SHARE ? TPB : 1> sd_in;
+    if constexpr (SHARE) mfma_shared_desc_load<MT, SL>(p, slot_mine, sd_in);
+    mfma_phase0<MT, CT, decltype(slot_of), SL, !SHARE>(lds_raw, p, slot_of, tab_off, a_off, meta, KBp, slot_mine);
+    if constexpr (SHARE) mfma_shared_desc<MT, SL>(p, sd_in, const_cast<uint4*>(sdesc), const_cast<uint4*>(tdesc));
     __syncthreads();
     // a slot of the block that does not fit the shared form: the block's results are NaN (block-uniform)
     bool bad = false;
@@ -221,46 +226,56 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
     // counts of one pass (RN column tiles from the scalar fragment offsets toff[]) into acc; the first PF X fragments of the
     // pass are in bq already
     auto counts_pass = [&](acc_t (&acc)[MT][kMfmaRN], const int (&toff)[kMfmaRN]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int r = 0; r < kMfmaRN; ++r)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[m][r][i] = 0;
         // A fragments one k-block ahead in their own registers (the read after the last k-block lands in the next M tile
-        // or in the log table: valid LDS, unused), X fragments PF k-blocks ahead; per k-block 3 LDS reads, 2 loads, 2 MT MFMAs
+        // or in the log table: valid LDS, unused), read at immediate offsets off one address per M tile that moves once per PF
+        // k-blocks; X fragments in a ring of PF slots: k-block kb reads slot kb % PF where it lies, and the slot that k-block
+        // kb - 1 read -- its MFMAs have issued -- takes fragment kb - 1 + PF (so nothing is copied; PF - 1 k-blocks ahead).
+        // Per k-block 3 LDS reads, 2 loads, 2 MT MFMAs.  The pass's first k-block takes a literal zero C operand: the
+        // accumulators are never zeroed in registers.
+        uint32_t a_at[MT];
         v4i_t a_cur[MT];
 #pragma unroll
-        for (int m = 0; m < MT; ++m) a_cur[m] = *(lds_cv4i_t*)(uintptr_t)(a_lane + ((uint32_t)m * (uint32_t)KBp) * 1024u);
-        for (int kb0 = 0; kb0 < KBp; kb0 += PF) {
+        for (int m = 0; m < MT; ++m) {
+            a_at[m] = a_lane + ((uint32_t)m * (uint32_t)KBp) * 1024u;
+            asm volatile("" : "+v"(a_at[m]));          // (formed here, per pass: hoisted, the addresses of the first k-blocks
+                                                       //  would hold eight registers through the epilogue)
+            a_cur[m] = *(lds_cv4i_t*)(uintptr_t)a_at[m];
+        }
+        auto k_group = [&](int kb0, auto first_c) __attribute__((always_inline)) {
+            constexpr bool first = decltype(first_c)::value;
 #pragma unroll
             for (int i = 0; i < PF; ++i) {
-                const int kb = kb0 + i;
                 v4i_t a_nxt[MT];
 #pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    a_nxt[m] = *(lds_cv4i_t*)(uintptr_t)(a_lane + ((uint32_t)m * (uint32_t)KBp + (uint32_t)(kb + 1)) * 1024u);
-                v4i_t b[kMfmaRN];
+                for (int m = 0; m < MT; ++m) a_nxt[m] = *(lds_cv4i_t*)(uintptr_t)(a_at[m] + (uint32_t)(i + 1) * 1024u);
+                const bool refill = !(first && i == 0);              // (the pass's first k-block: every slot is still unread)
+                if (refill) {
 #pragma unroll
-                for (int r = 0; r < kMfmaRN; ++r) b[r] = bq[i][r];
-#pragma unroll
-                for (int r = 0; r < kMfmaRN; ++r) bq[i][r] = load_b(toff[r], kb + PF);
+                    for (int r = 0; r < kMfmaRN; ++r) bq[(i + PF - 1) % PF][r] = load_b(toff[r], kb0 + i + PF - 1);
+                }
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
 #pragma unroll
                     for (int r = 0; r < kMfmaRN; ++r) {
                         // (an FP4 operand is the first four registers of the eight-register operand)
+                        const v4i_t bx = bq[i][r];
                         const v8i_t a8 = {a_cur[m].x, a_cur[m].y, a_cur[m].z, a_cur[m].w, 0, 0, 0, 0};
-                        const v8i_t b8 = {b[r].x, b[r].y, b[r].z, b[r].w, 0, 0, 0, 0};
-                        acc[m][r] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[m][r], 4, 4, 0, 0, 0, 0);
+                        const v8i_t b8 = {bx.x, bx.y, bx.z, bx.w, 0, 0, 0, 0};
+                        const acc_t zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                        if (first && i == 0) acc[m][r] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, zero, 4, 4, 0, 0, 0, 0);
+                        else acc[m][r] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[m][r], 4, 4, 0, 0, 0, 0);
                     }
 #pragma unroll
                 for (int m = 0; m < MT; ++m) a_cur[m] = a_nxt[m];
                 __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);                 // the next k-block's A fragments
-                __builtin_amdgcn_sched_group_barrier(0x020, kMfmaRN, 0);            // X fragments PF k-blocks ahead
+                if (refill) __builtin_amdgcn_sched_group_barrier(0x020, kMfmaRN, 0);    // X fragments for a later k-block
                 __builtin_amdgcn_sched_group_barrier(0x008, MT * kMfmaRN, 0);       // this k-block's MFMAs
             }
-        }
+#pragma unroll
+            for (int m = 0; m < MT; ++m) a_at[m] += (uint32_t)PF * 1024u;
+        };
+        k_group(0, std::true_type{});
+        for (int kb0 = PF; kb0 < KBp; kb0 += PF) k_group(kb0, std::false_type{});
     };
 
     // epilogue: LL += cnt * log(sum_c w * p) over the wave's RN * MT count tiles.  A "quad" = the four entries
@@ -454,6 +469,9 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         }
     };
 
+    const __amdgpu_buffer_rsrc_t cc_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(p.colcount), 0, (p.NT + 1) * 128, 0x00020000);
+    auto load_cc = [&](int nt) -> int { return (int)__builtin_amdgcn_raw_buffer_load_b32(cc_rsrc, cl * 4, (nt < nt_hi ? nt : p.NT) * 128, 0); };
+    int ccnt[kMfmaRN];
     for (int nt0 = nt_lo + w * kMfmaRN; nt0 < nt_hi; nt0 += kMfmaWaves * kMfmaRN) {
         int toff[kMfmaRN];
 #pragma unroll
@@ -467,13 +485,19 @@ __global__ __launch_bounds__(kMfmaThreads, 1) void k_mixture_tuple_mfma(MfmaMixP
         }
         // the column's object count over all tuples (data only: every object is in exactly one tuple of every slot), for the
         // exponent bias; tiles beyond the split read the zero row behind the array
-        int ccnt[kMfmaRN];
+        // (through a buffer descriptor like every other operand: lane-constant vector offset, scalar tile offset; the next
+        //  pass's two values are asked for once this pass's have been added, and arrive under the epilogue)
+        if (first_pass) {
 #pragma unroll
-        for (int r = 0; r < kMfmaRN; ++r) ccnt[r] = p.colcount[(nt0 + r < nt_hi ? nt0 + r : p.NT) * 32 + cl];
+            for (int r = 0; r < kMfmaRN; ++r) ccnt[r] = load_cc(nt0 + r);
+        }
         acc_t acc[MT][kMfmaRN];
         counts_pass(acc, toff);
 #pragma unroll
-        for (int r = 0; r < kMfmaRN; ++r) csum += ccnt[r];
+        for (int r = 0; r < kMfmaRN; ++r) {
+            csum += ccnt[r];
+            ccnt[r] = load_cc(nt0 + kMfmaWaves * kMfmaRN + r);
+        }
         if constexpr (SHARE) {
 #pragma unroll
             for (int r = 0; r < kMfmaRN; ++r) {

@@ -75,17 +75,19 @@ struct __attribute__((aligned(CT <= 1 ? 8 : (CT <= 3 ? 16 : 32)))) TupleMeta {
 };
 
 // Phase 0 of a block (all kMfmaThreads threads call it; the caller's barrier follows): tuple metadata, log table, A fragments.
-// `slot_of(sl)`: absolute slot of the block's sl-th slot, or -1.  LDS: log table at tab_off (= 0), A fragments from a_off,
-// metadata at `meta`.
+// `slot_of(sl)`: absolute slot of the block's sl-th slot, or -1; `slot_mine` = slot_of(threadIdx.x % SL), the slot of every
+// id unit of this thread (the thread count is a multiple of SL), looked up once by the caller.  LDS: log table at tab_off
+// (= 0), A fragments from a_off, metadata at `meta`.
 // SL = slots per block (16 / 4 / 2): an M tile's 32 rows are 32 / SL tuples x SL slots, row = (tuple in tile) * SL + slot; the
 // block holds TPB = MT * 32 / SL tuples.
 // META = false: no per-tuple metadata (the shared-operand epilogue reads its own descriptors: mfma_shared_desc).
 template <int MT, int CT, typename SlotOf, int SL = kMfmaSlots, bool META = true>
 __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMixParams& p, const SlotOf& slot_of, uint32_t tab_off,
-                                            uint32_t a_off, TupleMeta<CT>* meta, int KBp) {
+                                            uint32_t a_off, TupleMeta<CT>* meta, int KBp, int slot_mine) {
     typedef TupleMeta<CT> Meta;
     constexpr int TPT = 32 / SL, TPB = MT * TPT;                  // tuples per M tile / per block
     static_assert(SL == 16 || SL == 4 || SL == 2, "slots per block");
+    static_assert(kMfmaThreads % SL == 0, "a thread's id units all belong to one slot");
     // ---- phase 0: tuple metadata, log table, A fragments ------------------------------------------------------------
     // Offsets of a tuple that is not there (another slot's tuple, the padding tuple of an odd KT, a slot beyond the batch)
     // and of a component the tuple has no group in point at the rows of ONES behind the two arrays: no observation is
@@ -108,6 +110,14 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
     };
     // one unit = the 32 tuple ids of (slot sl, lane half h of k-block kb: 32 objects) -> the 2 MT indicator pieces (16 bytes =
     // 32 nibbles each).  UB units' ids are asked for together.
+    // Up to 8 tuples per block (PERM): an id byte is 0..7 -- the host numbers a slot's tuples densely and the launch's KT is the
+    // largest count among its slots (derive_tuples / update_patterns_and_tuples, plan_mixture), so KT <= TPB <= 8 bounds every
+    // id of the launch -- and v_perm_b32 with the id word as selector looks four objects up at once in an 8-byte table whose
+    // byte t is 0x02 (1.0 in e2m1) and whose other bytes are 0: selector 0..3 takes a byte of the low table word, 4..7 of
+    // the high one, 12 the constant 0x00 (13 and above would give 0xFF, 8..11 a replicated sign bit: never ids here).  The
+    // filler for objects beyond Np and slots that are not there is therefore 12 in every byte.  Wider blocks compare bytes.
+    constexpr bool PERM = TPB <= 8;
+    constexpr uint32_t kNoTuple = PERM ? 0x0C0C0C0Cu : 0xFFFFFFFFu;
     const int n_units = SL * KBp * 2;
     constexpr int UB = 2;
     uint32_t d[UB][8];
@@ -115,11 +125,11 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
 #pragma unroll
         for (int k = 0; k < UB; ++k) {
             const int u = u0 + k * kMfmaThreads;
-            const int sl = u % SL, n0 = (u / SL) * 32;     // (u / SL) = kb * 2 + h
-            const int slot = u < n_units ? slot_of(sl) : -1;
+            const int n0 = (u / SL) * 32;                  // (u / SL) = kb * 2 + h; u % SL = threadIdx.x % SL
+            const int slot = u < n_units ? slot_mine : -1;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                d[k][i] = 0xFFFFFFFFu;                                        // matches no tuple
+                d[k][i] = kNoTuple;                                           // matches no tuple
                 if (slot >= 0 && n0 + 4 * i + 4 <= p.Np)
                     d[k][i] = *reinterpret_cast<const uint32_t*>(p.tid + (int64_t)slot * p.tid_stride + n0 + 4 * i);
             }
@@ -138,6 +148,13 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
                 uint32_t* ov = reinterpret_cast<uint32_t*>(&o);
 #pragma unroll
                 for (int wv = 0; wv < 4; ++wv) {
+                    if constexpr (PERM) {
+                        const uint64_t lut = 0x02ull << (8 * (t & 7));
+                        const uint32_t lo = __builtin_amdgcn_perm((uint32_t)(lut >> 32), (uint32_t)lut, d[k][2 * wv]);
+                        const uint32_t hi = __builtin_amdgcn_perm((uint32_t)(lut >> 32), (uint32_t)lut, d[k][2 * wv + 1]);
+                        ov[wv] = lo | (hi << 4);                // the same bytes as below
+                        continue;
+                    }
                     uint32_t eq[2];
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
@@ -194,22 +211,41 @@ __device__ __forceinline__ void mfma_phase0(unsigned char* lds_raw, const MfmaMi
 // sel = 1: the tuple has pattern b.  A tuple that is not there (pattern 0xFF, t >= KT, a slot beyond the batch) has no counts;
 // it keeps its component-0 row on the ones row, as in the per-tuple metadata, and selector 0.  bad != 0: the slot does not
 // fit the form (the host's per-slot flag was wrong) -- the block then reports NaN for its slots instead of a wrong number.
-template <int MT, int SL, typename SlotOf>
-__device__ __forceinline__ void mfma_shared_desc(const MfmaMixParams& p, const SlotOf& slot_of, uint4* sdesc, uint4* tdesc) {
+// The two halves are called apart: the loads (thread sl's slot and its tuples' pattern and groups) leave with phase 0's first
+// loads, the descriptors are built after the A image is written -- one round trip to L2 / HBM for the block, not two.
+template <int TPB>
+struct SharedDescIn {
+    int slot;
+    uint32_t pat[TPB], g0[TPB], g1[TPB];
+};
+
+// `slot`: thread sl's slot of the block, or -1.  The rows exist for every slot and every tuple index below kMaxTuples, so the
+// loads carry no condition (a branch per tuple makes each wait for the one before); what is not there is masked afterwards.
+template <int MT, int SL>
+__device__ __forceinline__ void mfma_shared_desc_load(const MfmaMixParams& p, int slot, SharedDescIn<MT * 32 / SL>& in) {
     constexpr int TPB = MT * 32 / SL;
     static_assert(SL == 16 && TPB <= kMaxTuples, "the shared-operand form has 16 slots of <= 8 tuples");
     if ((int)threadIdx.x >= SL) return;
-    const int sl = (int)threadIdx.x, slot = slot_of(sl);
-    uint32_t pat[TPB], g0[TPB], g1[TPB];
+    in.slot = slot;
+    const uint8_t* const tp = p.tuple_p + (int64_t)max(slot, 0) * p.tuple_p_stride;
+    const uint16_t* const tg = p.tuple_g + (int64_t)max(slot, 0) * p.tuple_g_stride;
 #pragma unroll
     for (int t = 0; t < TPB; ++t) {                       // (asked for together: one round trip)
-        pat[t] = 0xFFu; g0[t] = g1[t] = 0xFFFFFFFFu;
-        if (slot >= 0 && t < p.KT) {
-            pat[t] = p.tuple_p[(int64_t)slot * p.tuple_p_stride + t];
-            g0[t] = p.tuple_g[(int64_t)slot * p.tuple_g_stride + t * kMaxComponents + 0];
-            g1[t] = p.tuple_g[(int64_t)slot * p.tuple_g_stride + t * kMaxComponents + 1];
-        }
+        in.pat[t] = tp[t];
+        in.g0[t] = tg[t * kMaxComponents + 0];
+        in.g1[t] = tg[t * kMaxComponents + 1];
     }
+}
+
+template <int MT, int SL>
+__device__ __forceinline__ void mfma_shared_desc(const MfmaMixParams& p, const SharedDescIn<MT * 32 / SL>& in, uint4* sdesc, uint4* tdesc) {
+    constexpr int TPB = MT * 32 / SL;
+    if ((int)threadIdx.x >= SL) return;
+    const int sl = (int)threadIdx.x, slot = in.slot;
+    const uint32_t (&g0)[TPB] = in.g0, (&g1)[TPB] = in.g1;
+    uint32_t pat[TPB];
+#pragma unroll
+    for (int t = 0; t < TPB; ++t) pat[t] = (slot >= 0 && t < p.KT) ? in.pat[t] : 0xFFu;      // (not there: its groups are not looked at)
     auto goff = [&](uint32_t g) -> uint32_t {
         return (int)g < p.Gtot ? (uint32_t)(((int64_t)slot * p.probs_stride + (int64_t)g * p.FS) * 4) : p.probs_ones_off;
     };
