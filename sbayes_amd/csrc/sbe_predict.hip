@@ -1,0 +1,505 @@
+// sbe_predict.hip -- the posterior predictive of the logged samples on the device (include/sbe_predict.h): per cell the
+// mixture row of every sample, summed over the samples, each component's responsibility for the observed cells and the
+// pointwise likelihood rows.  The contract is tests/_predict_oracle.py; DESIGN.md section 21 has the layout, the structure
+// of the kernels and the limits.
+//
+// An accumulate call holds its n samples on the device and runs three kernels:
+//   k_predict_ids       a thread per (sample, object): the 0 / 1 cluster rows become one cluster id per object, an object in
+//                       two clusters is reported;
+//   k_predict_validate  a thread per weight row and per table row: entries, positive entry, sum;
+//   k_predict_accumulate<SP, CP>  (only after the host has read that the two above found nothing)
+//                       a workgroup owns a tile of Ft features x Nt = 256 / Ft objects, a thread one cell of it with the
+//                       cell's S + C float64 accumulators in registers (SP, CP: S and C padded to a power of two, so the
+//                       loops over them unroll) for all n samples: pred_sum / resp_sum are read once and written once per
+//                       call.  Per sample the workgroup stages the tile's slice of the tables, [R][Ft][S], and of the
+//                       weights, [Ft][C], into one of two LDS buffers: the slice of sample t + 1 is written while sample t
+//                       is computed from the other buffer, one barrier per sample.  The weight normalisation is computed
+//                       per cell from the object's h flags (no table over the 2^C patterns).  Threads along the tile's
+//                       features are adjacent, so a sample's lik row is written in runs of Ft floats.
+// The first offender travels as one uint64 key (sample, kind, position) through an integer atomicMin.  No floating-point
+// atomics: a cell belongs to one thread, which adds the samples in order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "sbe_unit.hip.h"
+#include "../../include/sbe_predict.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxS = SBE_PREDICT_MAX_STATES;
+constexpr int kMaxC = SBE_PREDICT_MAX_COMPONENTS;
+constexpr int kMaxR = SBE_PREDICT_MAX_ROWS;
+constexpr int kMaxTile = SBE_PREDICT_MAX_TILE;
+constexpr uint16_t kNoCluster = 0xFFFF;
+constexpr uint8_t kNA = SBE_PREDICT_NA;
+constexpr unsigned long long kNoError = ~0ull;
+constexpr int kDefaultTile = 16;                     // features per tile, where the slice allows it
+constexpr size_t kSmallSlices = (size_t)40 << 10;    // the default plan keeps the two slices under this: four workgroups per CU
+static_assert(kMaxTile <= kBlock, "a tile of Ft features gives every thread of a row of Ft a feature");
+
+// kinds of offender, in the order the header lists them
+enum : int { kOverlap = 0, kWeightEntry = 1, kWeightSum = 2, kTableEntry = 3, kTableRowEmpty = 4, kTableSum = 5 };
+
+__host__ __device__ inline unsigned long long error_key(int64_t sample, int kind, int64_t at) {
+    return ((unsigned long long)sample << 40) | ((unsigned long long)kind << 36) | (unsigned long long)at;
+}
+
+// ---- preparation: cluster rows -> cluster id per object --------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_predict_ids(const uint8_t* clusters, int64_t n, int64_t N, int K, uint16_t* kid,
+                                                        unsigned long long* err) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n * N) return;
+    const int64_t t = q / N, obj = q - t * N;
+    const uint8_t* rows = clusters + t * K * N + obj;
+    int found = 0;
+    uint16_t id = kNoCluster;
+    for (int k = 0; k < K; ++k)
+        if (rows[(int64_t)k * N]) {
+            if (!found) id = (uint16_t)k;
+            ++found;
+        }
+    kid[q] = id;
+    if (found > 1) atomicMin(err, error_key(t, kOverlap, obj));
+}
+
+// ---- validation: one thread per row (a sample's F weight rows, then its R F table rows) -----------------------------------
+__global__ __launch_bounds__(kBlock) void k_predict_validate(const double* weights, const double* tables, int64_t n, int F, int S, int C, int R,
+                                                             unsigned long long* err) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t per_sample = (int64_t)F * (1 + R);
+    if (q >= n * per_sample) return;
+    const int64_t t = q / per_sample, j = q - t * per_sample;
+    const bool is_weight = j < F;
+    const int64_t row = is_weight ? j : j - F;               // f, or r F + f
+    const int len = is_weight ? C : S;
+    const double* v = is_weight ? weights + (t * F + row) * C : tables + (t * (int64_t)R * F + row) * S;
+    double sum = 0.0;
+    bool positive = false;
+    for (int i = 0; i < len; ++i) {
+        const double x = v[i];
+        if (!(x >= 0.0) || isinf(x)) {                       // negative, NaN or infinite
+            atomicMin(err, error_key(t, is_weight ? kWeightEntry : kTableEntry, row * len + i));
+            return;
+        }
+        positive |= x > 0.0;
+        sum += x;
+    }
+    if (!is_weight && !positive) {
+        atomicMin(err, error_key(t, kTableRowEmpty, row));
+        return;
+    }
+    if (fabs(sum - 1.0) > SBE_PREDICT_SUM_TOL) atomicMin(err, error_key(t, is_weight ? kWeightSum : kTableSum, row));
+}
+
+// ---- the accumulation -------------------------------------------------------------------------------------------------------
+struct AccArgs {
+    const uint8_t* codes;          // [N][F]
+    const uint8_t* groups;         // [C-1][N]
+    const uint16_t* kid;           // [n][N]
+    const double* weights;         // [n][F][C]
+    const double* tables;          // [n][R][F][S]
+    double* pred;                  // [N][F][S]
+    double* resp;                  // [N][F][C]
+    float* lik;                    // [n][N F] or null
+    unsigned long long* n_zero;
+    int64_t N;
+    int F, S, C, R;
+    int n;
+    int Ft, Nt, f_tiles;
+    int64_t block0;                // of this launch
+    int row_off[kMaxC];            // first table row of a component's groups (row_off[0] = 0: the clusters)
+};
+
+// the tile's slice of sample t into `buf`: [R][Ft][S] of the tables, then [Ft][C] of the weights; the features of the last
+// tile behind F are zero
+__device__ inline void stage_slice(double* buf, const AccArgs& g, int t, int f0, int fw) {
+    const int row_len = g.Ft * g.S, have = fw * g.S, total = g.R * row_len;
+    const double* tab = g.tables + ((int64_t)t * g.R * g.F + f0) * g.S;
+    for (int j = threadIdx.x; j < total; j += kBlock) {
+        const int r = j / row_len, q = j - r * row_len;
+        buf[j] = q < have ? tab[(int64_t)r * g.F * g.S + q] : 0.0;
+    }
+    const double* w = g.weights + ((int64_t)t * g.F + f0) * g.C;
+    for (int j = threadIdx.x; j < g.Ft * g.C; j += kBlock) buf[total + j] = j < fw * g.C ? w[j] : 0.0;
+}
+
+template <int SP, int CP>
+__global__ __launch_bounds__(kBlock) void k_predict_accumulate(const AccArgs g) {
+    extern __shared__ double lds[];                            // two slices
+    const int64_t b = g.block0 + blockIdx.x;
+    const int ft = (int)(b % g.f_tiles);
+    const int64_t nt = b / g.f_tiles;
+    const int f0 = ft * g.Ft, fw = min(g.Ft, g.F - f0);
+    const int fl = threadIdx.x % g.Ft, nl = threadIdx.x / g.Ft;
+    const int64_t obj = nt * g.Nt + nl;
+    const int f = f0 + fl;
+    const bool live = nl < g.Nt && obj < g.N && f < g.F;
+    const int slice = g.R * g.Ft * g.S + g.Ft * g.C;
+    const int w_at = g.R * g.Ft * g.S + fl * g.C;
+
+    double pred[SP], resp[CP];
+    int row[CP];                                               // the object's table row per component (0: not applicable)
+    bool has[CP];
+    int x = kNA;
+    const int64_t cell = live ? obj * g.F + f : 0;
+#pragma unroll
+    for (int s = 0; s < SP; ++s) pred[s] = live && s < g.S ? g.pred[cell * g.S + s] : 0.0;
+#pragma unroll
+    for (int c = 0; c < CP; ++c) {
+        resp[c] = live && c < g.C ? g.resp[cell * g.C + c] : 0.0;
+        has[c] = false;
+        row[c] = 0;
+        if (live && c >= 1 && c < g.C) {
+            const int grp = g.groups[(int64_t)(c - 1) * g.N + obj];
+            has[c] = grp != kNA;
+            row[c] = has[c] ? g.row_off[c] + grp : 0;
+        }
+    }
+    if (live) x = g.codes[cell];
+    unsigned long long zeros = 0;
+
+    stage_slice(lds, g, 0, f0, fw);
+    __syncthreads();
+    for (int t = 0; t < g.n; ++t) {
+        const double* cur = lds + (t & 1) * slice;
+        if (t + 1 < g.n) stage_slice(lds + ((t + 1) & 1) * slice, g, t + 1, f0, fw);
+        if (live) {
+            const uint16_t id = g.kid[(int64_t)t * g.N + obj];
+            has[0] = id != kNoCluster;
+            row[0] = has[0] ? id : 0;
+            double wn[CP], wsum = 0.0;
+            const double* base[CP];
+#pragma unroll
+            for (int c = 0; c < CP; ++c) {
+                wn[c] = c < g.C && has[c] ? cur[w_at + c] : 0.0;
+                if (c < g.C) wsum += wn[c];
+                base[c] = cur + (row[c] * g.Ft + fl) * g.S;
+            }
+#pragma unroll
+            for (int c = 0; c < CP; ++c) wn[c] = wsum > 0.0 ? wn[c] / wsum : 0.0;
+#pragma unroll
+            for (int s = 0; s < SP; ++s)
+                if (s < g.S) {
+                    double m = 0.0;
+#pragma unroll
+                    for (int c = 0; c < CP; ++c)
+                        if (c < g.C) m += wn[c] * base[c][s];
+                    pred[s] += m;
+                }
+            float lik = 1.0f;
+            if (x != kNA) {
+                double part[CP], mx = 0.0;
+#pragma unroll
+                for (int c = 0; c < CP; ++c) {
+                    part[c] = c < g.C ? wn[c] * base[c][x] : 0.0;
+                    if (c < g.C) mx += part[c];
+                }
+                if (mx > 0.0) {
+#pragma unroll
+                    for (int c = 0; c < CP; ++c) resp[c] += part[c] / mx;
+                } else {
+                    ++zeros;
+                }
+                lik = (float)mx;
+            }
+            if (g.lik) g.lik[(int64_t)t * g.N * g.F + cell] = lik;
+        }
+        __syncthreads();                                       // sample t is read, the slice of t + 1 is written
+    }
+    if (!live) return;
+#pragma unroll
+    for (int s = 0; s < SP; ++s)
+        if (s < g.S) g.pred[cell * g.S + s] = pred[s];
+#pragma unroll
+    for (int c = 0; c < CP; ++c)
+        if (c < g.C) g.resp[cell * g.C + c] = resp[c];
+    if (zeros) atomicAdd(g.n_zero, zeros);
+}
+
+using AccKernel = void (*)(const AccArgs);
+
+template <int SP>
+AccKernel acc_kernel_c(int C) {
+    if (C <= 1) return k_predict_accumulate<SP, 1>;
+    if (C <= 2) return k_predict_accumulate<SP, 2>;
+    if (C <= 4) return k_predict_accumulate<SP, 4>;
+    return k_predict_accumulate<SP, 8>;
+}
+
+AccKernel acc_kernel(int S, int C) {
+    if (S <= 2) return acc_kernel_c<2>(C);
+    if (S <= 4) return acc_kernel_c<4>(C);
+    if (S <= 8) return acc_kernel_c<8>(C);
+    if (S <= 16) return acc_kernel_c<16>(C);
+    return acc_kernel_c<32>(C);
+}
+
+}  // namespace
+
+struct sbe_predict : sbe_unit_handle {
+    bool has_data = false;
+    int64_t N = 0;
+    int F = 0, S = 0, C = 0, K = 0, R = 0;
+    int row_off[kMaxC] = {};
+    int forced_tile = 0;                // 0: the default
+    int64_t n_samples = 0;
+    uint8_t* d_codes = nullptr;         // [N][F]
+    size_t codes_bytes = 0;
+    uint8_t* d_groups = nullptr;        // [C-1][N]
+    size_t groups_bytes = 0;
+    double* d_acc = nullptr;            // pred_sum [N][F][S], then resp_sum [N][F][C]
+    size_t acc_bytes = 0;
+    unsigned long long* d_words = nullptr;   // [0]: n_zero, [1]: the first offender's key
+    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
+    size_t clusters_bytes = 0;
+    double* d_weights = nullptr;        // [n][F][C]
+    size_t weights_bytes = 0;
+    double* d_tables = nullptr;         // [n][R][F][S]
+    size_t tables_bytes = 0;
+    uint16_t* d_kid = nullptr;          // [n][N]
+    size_t kid_bytes = 0;
+    float* d_lik = nullptr;             // [n][N F]
+    size_t lik_bytes = 0;
+    std::vector<void*> buffers() const { return {d_codes, d_groups, d_acc, d_words, d_clusters, d_weights, d_tables, d_kid, d_lik}; }
+    double* pred() const { return d_acc; }
+    double* resp() const { return d_acc + (size_t)N * F * S; }
+    size_t acc_doubles() const { return (size_t)N * F * (S + C); }
+};
+
+namespace {
+
+constexpr char kNullHandle[] = "null handle";
+
+bool shape_ok(int64_t N, int64_t F, int S, int C, int K, int R) {
+    return N >= 1 && N <= SBE_PREDICT_MAX_OBJECTS && F >= 1 && F <= SBE_PREDICT_MAX_FEATURES && S >= 1 && S <= kMaxS && C >= 1 && C <= kMaxC &&
+           K >= 1 && R >= K && R <= kMaxR && N * F * (S + C) * 8 <= SBE_PREDICT_MAX_ACC_BYTES;
+}
+
+int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R, bool lik) {
+    return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + (lik ? 4 * N * F : 0);
+}
+
+size_t slices_bytes(const sbe_predict* h, int Ft) { return 2 * (size_t)Ft * ((size_t)h->R * h->S + h->C) * sizeof(double); }
+
+// host bytes <-> device in pieces of at most kStageBytes, on the handle's stream
+int copy_pieces(sbe_predict* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    for (size_t at = 0; at < bytes; at += (size_t)kStageBytes)
+        HIPCHK(h, hipMemcpyAsync((char*)dst + at, (const char*)src + at, std::min((size_t)kStageBytes, bytes - at), kind, h->stream));
+    return SBE_OK;
+}
+
+int zero_accumulators(sbe_predict* h) {
+    HIPCHK(h, hipMemsetAsync(h->d_acc, 0, h->acc_doubles() * sizeof(double), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_words, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->n_samples = 0;
+    return SBE_OK;
+}
+
+// the message of a validation failure
+int data_error(sbe_predict* h, unsigned long long key) {
+    const long long t = (long long)(key >> 40), at = (long long)(key & ((1ull << 36) - 1));
+    const int F = h->F, S = h->S, C = h->C;
+    switch ((int)((key >> 36) & 15)) {
+    case kOverlap: return fail(h, SBE_ERR_DATA, "sample %lld: object %lld is in more than one cluster", t, at);
+    case kWeightEntry: return fail(h, SBE_ERR_DATA, "sample %lld: weights[%lld][%lld] is negative or not finite", t, at / C, at % C);
+    case kWeightSum: return fail(h, SBE_ERR_DATA, "sample %lld: the weights of feature %lld sum further than %g from 1", t, at, SBE_PREDICT_SUM_TOL);
+    case kTableEntry:
+        return fail(h, SBE_ERR_DATA, "sample %lld: tables[%lld][%lld][%lld] (row, feature, state) is negative or not finite", t, at / S / F,
+                    at / S % F, at % S);
+    case kTableRowEmpty: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld has no positive entry", t, at / F, at % F);
+    default: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld sums further than %g from 1", t, at / F, at % F, SBE_PREDICT_SUM_TOL);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbe_predict_abi_version(void) { return SBE_PREDICT_ABI_VERSION; }
+
+const char* sbe_predict_last_error(const sbe_predict* h) { return unit_last_error(h); }
+
+int sbe_predict_create(sbe_predict** out, int device) { return unit_create_on_device(out, device, "sbe_predict_create"); }
+
+int sbe_predict_destroy(sbe_predict* h) { return unit_destroy(h, kNullHandle); }
+
+int sbe_predict_last_kernel_ms(const sbe_predict* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
+
+int64_t sbe_predict_sample_bytes(int64_t n_objects, int64_t n_features, int n_states, int n_components, int n_clusters, int n_rows, int with_lik) {
+    return shape_ok(n_objects, n_features, n_states, n_components, n_clusters, n_rows)
+               ? sample_bytes(n_objects, n_features, n_states, n_components, n_clusters, n_rows, with_lik != 0)
+               : 0;
+}
+
+int sbe_predict_set_feature_tile(sbe_predict* h, int features) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
+    h->forced_tile = features;
+    return SBE_OK;
+}
+
+int sbe_predict_set_data(sbe_predict* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (N < 1 || N > SBE_PREDICT_MAX_OBJECTS) return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d]", (long long)N, SBE_PREDICT_MAX_OBJECTS);
+    if (F < 1 || F > SBE_PREDICT_MAX_FEATURES) return fail(h, SBE_ERR_ARG, "n_features=%lld out of range [1, %d]", (long long)F, SBE_PREDICT_MAX_FEATURES);
+    if (S < 1 || S > kMaxS) return fail(h, SBE_ERR_ARG, "n_states=%d out of range [1, %d]", S, kMaxS);
+    if (C < 1 || C > kMaxC) return fail(h, SBE_ERR_ARG, "n_components=%d out of range [1, %d]", C, kMaxC);
+    if (K < 1 || K > kMaxR) return fail(h, SBE_ERR_ARG, "n_clusters=%d out of range [1, %d]", K, kMaxR);
+    if (!codes) return fail(h, SBE_ERR_ARG, "null pointer argument: codes");
+    if (C > 1 && (!groups || !n_groups)) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !groups ? "groups" : "n_groups");
+    int row_off[kMaxC] = {};
+    int R = K;
+    for (int c = 1; c < C; ++c) {
+        if (n_groups[c - 1] < 1 || n_groups[c - 1] > kMaxR)
+            return fail(h, SBE_ERR_ARG, "n_groups[%d]=%d out of range [1, %d]", c - 1, n_groups[c - 1], kMaxR);
+        row_off[c] = R;
+        R += n_groups[c - 1];
+    }
+    if (R > kMaxR) return fail(h, SBE_ERR_ARG, "%d clusters and the confounders' groups make %d table rows, the limit is %d", K, R, kMaxR);
+    if (N * F * (S + C) * 8 > SBE_PREDICT_MAX_ACC_BYTES)
+        return fail(h, SBE_ERR_ARG, "the accumulators of %lld objects x %lld features x (%d states + %d components) take %lld bytes on the device, the limit is %lld",
+                    (long long)N, (long long)F, S, C, (long long)(N * F * (S + C) * 8), (long long)SBE_PREDICT_MAX_ACC_BYTES);
+    for (int64_t q = 0; q < N * F; ++q)
+        if (codes[q] >= S && codes[q] != kNA)
+            return fail(h, SBE_ERR_DATA, "codes[%lld][%lld]=%d is neither a state below %d nor 255", (long long)(q / F), (long long)(q % F), (int)codes[q], S);
+    for (int c = 1; c < C; ++c)
+        for (int64_t i = 0; i < N; ++i) {
+            const uint8_t g = groups[(int64_t)(c - 1) * N + i];
+            if (g >= n_groups[c - 1] && g != kNA)
+                return fail(h, SBE_ERR_DATA, "groups[%d][%lld]=%d is neither a group below %d nor 255", c - 1, (long long)i, (int)g, n_groups[c - 1]);
+        }
+    h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
+    if (!rc) rc = unit_ensure(h, h->d_groups, h->groups_bytes, std::max<size_t>(1, (size_t)(C - 1) * (size_t)N));
+    if (!rc) rc = unit_ensure(h, h->d_acc, h->acc_bytes, (size_t)(N * F * (S + C)) * sizeof(double));
+    if (!rc) rc = unit_ensure(h, h->d_words, 2 * sizeof(unsigned long long));
+    if (!rc) rc = copy_pieces(h, h->d_codes, codes, (size_t)(N * F), hipMemcpyHostToDevice);
+    if (!rc && C > 1) rc = copy_pieces(h, h->d_groups, groups, (size_t)(C - 1) * (size_t)N, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    h->N = N;
+    h->F = (int)F;
+    h->S = S;
+    h->C = C;
+    h->K = K;
+    h->R = R;
+    std::copy(row_off, row_off + kMaxC, h->row_off);
+    if ((rc = zero_accumulators(h))) return rc;          // (waits for the copies too)
+    h->has_data = true;
+    return SBE_OK;
+}
+
+int sbe_predict_reset(sbe_predict* h) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return zero_accumulators(h);
+}
+
+int sbe_predict_accumulate(sbe_predict* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables, float* lik_out) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
+    if (n == 0) return SBE_OK;
+    if (!clusters || !weights || !tables)
+        return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
+    const int64_t N = h->N, F = h->F;
+    const int S = h->S, C = h->C, K = h->K, R = h->R;
+    const int64_t per_sample = sample_bytes(N, F, S, C, K, R, lik_out != nullptr);
+    if (n > SBE_PREDICT_MAX_STAGE_BYTES / per_sample)
+        return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
+                    (long long)n, (long long)per_sample, (long long)SBE_PREDICT_MAX_STAGE_BYTES, (long long)(SBE_PREDICT_MAX_STAGE_BYTES / per_sample));
+    // the tile along the features
+    int Ft = h->forced_tile;
+    if (Ft == 0) {
+        Ft = std::min(kDefaultTile, pow2_at_least((int)F));
+        while (Ft > 1 && slices_bytes(h, Ft) > kSmallSlices) Ft /= 2;
+    }
+    const size_t lds = slices_bytes(h, Ft);
+    if (lds > kLdsBudget)
+        return fail(h, SBE_ERR_ARG, "a tile of %d features takes two slices of %d rows x %d states: %lld bytes of LDS, the limit is %lld", Ft, R, S,
+                    (long long)lds, (long long)kLdsBudget);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
+    int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
+    if (!rc) rc = unit_ensure(h, h->d_weights, h->weights_bytes, w_bytes);
+    if (!rc) rc = unit_ensure(h, h->d_tables, h->tables_bytes, t_bytes);
+    if (!rc) rc = unit_ensure(h, h->d_kid, h->kid_bytes, (size_t)n * N * sizeof(uint16_t));
+    if (!rc && lik_out) rc = unit_ensure(h, h->d_lik, h->lik_bytes, (size_t)n * N * F * sizeof(float));
+    if (!rc) rc = copy_pieces(h, h->d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
+    if (!rc) rc = copy_pieces(h, h->d_weights, weights, w_bytes, hipMemcpyHostToDevice);
+    if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
+    if (rc) return rc;
+    unsigned long long* d_err = h->d_words + 1;
+    HIPCHK(h, hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    k_predict_ids<<<(unsigned)div_up(n * N, kBlock), kBlock, 0, h->stream>>>(h->d_clusters, n, N, K, h->d_kid, d_err);
+    HIPCHK(h, hipGetLastError());
+    k_predict_validate<<<(unsigned)div_up(n * F * (1 + R), kBlock), kBlock, 0, h->stream>>>(h->d_weights, h->d_tables, n, (int)F, S, C, R, d_err);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long key = kNoError;
+    HIPCHK(h, hipMemcpyAsync(&key, d_err, sizeof key, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (key != kNoError) return data_error(h, key);
+
+    AccArgs args{};
+    args.codes = h->d_codes;
+    args.groups = h->d_groups;
+    args.kid = h->d_kid;
+    args.weights = h->d_weights;
+    args.tables = h->d_tables;
+    args.pred = h->pred();
+    args.resp = h->resp();
+    args.lik = lik_out ? h->d_lik : nullptr;
+    args.n_zero = h->d_words;
+    args.N = N;
+    args.F = (int)F;
+    args.S = S;
+    args.C = C;
+    args.R = R;
+    args.n = (int)n;
+    args.Ft = Ft;
+    args.Nt = kBlock / Ft;
+    args.f_tiles = div_up(F, Ft);
+    std::copy(h->row_off, h->row_off + kMaxC, args.row_off);
+    const AccKernel kernel = acc_kernel(S, C);
+    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+    const int64_t blocks = (int64_t)args.f_tiles * ((N + args.Nt - 1) / args.Nt);
+    rc = unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
+        args.block0 = first;
+        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
+        HIPCHK(h, hipGetLastError());
+        return SBE_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    if (lik_out) rc = copy_pieces(h, lik_out, h->d_lik, (size_t)n * N * F * sizeof(float), hipMemcpyDeviceToHost);
+    if (!rc) rc = unit_sync_timed(h);
+    if (rc) return rc;
+    h->n_samples += n;
+    return SBE_OK;
+}
+
+int sbe_predict_read(sbe_predict* h, double* pred_sum, double* resp_sum, int64_t* n_samples_out, int64_t* n_zero_out) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    if (!n_samples_out || !n_zero_out) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !n_samples_out ? "n_samples_out" : "n_zero_out");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = SBE_OK;
+    if (pred_sum) rc = copy_pieces(h, pred_sum, h->pred(), (size_t)h->N * h->F * h->S * sizeof(double), hipMemcpyDeviceToHost);
+    if (!rc && resp_sum) rc = copy_pieces(h, resp_sum, h->resp(), (size_t)h->N * h->F * h->C * sizeof(double), hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    unsigned long long zeros = 0;
+    HIPCHK(h, hipMemcpyAsync(&zeros, h->d_words, sizeof zeros, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_samples_out = h->n_samples;
+    *n_zero_out = (int64_t)zeros;
+    return SBE_OK;
+}
+
+}  // extern "C"
