@@ -95,6 +95,7 @@ struct sbe_engine : sbe::MixShape {
     sbe::MixTuning tune;           // SBE_OPT_MIXTURE_KERNEL and the launch decision's experiment values
     int opt_log = SBE_LOG_PRODUCT;
     int opt_fuse_tables = fuse_tables_default();   // SBE_OPT_FUSE_TABLES
+    bool ws_lds_allowed[2] = {false, false};       // k_cluster_marginals_ws / k_jump_lh_ws were granted their largest block (allow_ws_lds)
 
     // resident data
     uint8_t* d_onehot = nullptr;   // [N][rs_pitch]

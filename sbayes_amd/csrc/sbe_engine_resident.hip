@@ -545,6 +545,19 @@ int sbe_given_unchanged_gibbs_apply(sbe_engine* e, int slot, int update_probs, i
                                       diff_rows_out, 1, update_probs);
 }
 
+// A wave-specialised operator kernel whose tables and static log table together pass 64 KB of LDS (tables from 62 KB up) asks
+// for the larger block before its first such launch, once per engine, as the side units' kernels do (the runtime's documented
+// way past a block's default grant: the launch does not count on a lenient runtime).  Smaller launches, the usual ones, never
+// come here.
+namespace {
+int allow_ws_lds(sbe_engine* e, int which, const void* kernel, size_t table_bytes) {
+    if (table_bytes + kWsStaticLds <= ((size_t)64 << 10) || e->ws_lds_allowed[which]) return SBE_OK;
+    HIPCHK(e, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsMaxTableLds));
+    e->ws_lds_allowed[which] = true;
+    return SBE_OK;
+}
+}  // namespace
+
 int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, double temperature, double prior_temperature,
                                     const int32_t* objects, int n_objects_av, double* out) {
     CHECK_ENGINE(e); CHECK_SLOT(e, slot); CHECK_PTR(e, out);
@@ -569,7 +582,7 @@ int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, doub
     // waves of every block put it into LDS while the block's object waves run their load chains; otherwise -- table beyond
     // 64 KB, more than kWsC components, SBE_OPT_FUSE_TABLES off -- a table kernel in front of the block-per-object kernel.
     const size_t cand_bytes = (size_t)fs * sizeof(float);
-    const bool fused = e->opt_fuse_tables && C <= kWsC && cand_bytes <= ((size_t)64 << 10);
+    const bool fused = e->opt_fuse_tables && C <= kWsC && cand_bytes <= kWsMaxTableLds;
     const size_t ob = al256((size_t)n_objects_av * sizeof(int32_t));
     const size_t out_bytes = (size_t)2 * n_objects_av * sizeof(double);
     rc = ensure_io(e, ob + out_bytes);
@@ -585,6 +598,8 @@ int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, doub
         tin.row[0] = RowSource{cnt + (int64_t)i_cluster * fs, e->d_conc + (int64_t)i_cluster * fs};
         tin.unif = e->d_unif_res; tin.temperature = temperature; tin.prior_temperature = prior_temperature; tin.status = e->d_status;
         tin.n_rows = F;
+        rc = allow_ws_lds(e, 0, (const void*)k_cluster_marginals_ws, cand_bytes);
+        if (rc) return rc;
         const unsigned blocks = (unsigned)div_up(n_objects_av, kWsObjWaves);
         done = next_done(e, blocks);
         k_cluster_marginals_ws<<<blocks, kWsBlock, cand_bytes, e->stream>>>(
@@ -639,7 +654,7 @@ int sbe_jump_lh_resident(sbe_engine* e, int slot, int i_source, int i_target, do
     // prior's uniform concentration for every component (operators.py:1352).  Fused form (k_jump_lh_ws): builder waves
     // put them into LDS, one launch; otherwise (tables beyond 64 KB, C > kWsC, option off) three table kernels in front.
     const size_t built_bytes = (size_t)(2 + n_conf) * fs * sizeof(float);
-    const bool fused = e->opt_fuse_tables && C <= kWsC && built_bytes <= ((size_t)64 << 10);
+    const bool fused = e->opt_fuse_tables && C <= kWsC && built_bytes <= kWsMaxTableLds;
     const size_t ob = al256((size_t)n_members * sizeof(int32_t));
     const size_t out_bytes = (size_t)2 * n_members * sizeof(double);
     rc = ensure_io(e, ob + out_bytes);
@@ -657,6 +672,8 @@ int sbe_jump_lh_resident(sbe_engine* e, int slot, int i_source, int i_target, do
         tin.counts = cnt; tin.conc = e->d_conc; tin.first_conf_group = K;
         tin.unif = e->d_unif_res; tin.temperature = temperature; tin.prior_temperature = prior_temperature; tin.status = e->d_status;
         tin.n_rows = (2 + n_conf) * F;
+        rc = allow_ws_lds(e, 1, (const void*)k_jump_lh_ws, built_bytes);
+        if (rc) return rc;
         const unsigned blocks = (unsigned)div_up(n_members, kWsObjWaves);
         done = next_done(e, blocks);
         k_jump_lh_ws<<<blocks, kWsBlock, built_bytes, e->stream>>>(

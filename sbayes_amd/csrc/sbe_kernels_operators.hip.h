@@ -46,6 +46,9 @@ struct InlineTables {
 };
 constexpr int kWsObjWaves = 4, kWsWaves = 16, kWsBlock = kWsWaves * kWave, kWsC = 4;   // (object waves; components held in registers)
 static_assert(kLogTabEntries == 2 * kWave, "the first builder wave copies the log table with two loads per lane");
+// LDS of a wave-specialised block: the call's tables (dynamic, at most kWsMaxTableLds) NEXT TO the log table (static, 2 KB) --
+// up to 66 KB together, past the 64 KB a block is granted without asking (the launchers ask: allow_ws_lds).
+constexpr size_t kWsMaxTableLds = (size_t)64 << 10, kWsStaticLds = kLogTabEntries * sizeof(f64x2_t);
 
 // Builder waves of a wave-specialised operator kernel: rows (wave - kWsObjWaves) * 64 + lane, + 768, ... into `built` (LDS).
 __device__ __forceinline__ void ws_build_rows(const InlineTables& tin, float* __restrict__ built, int F, int S) {
