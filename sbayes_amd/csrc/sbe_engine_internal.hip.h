@@ -1305,7 +1305,24 @@ int check_objects(sbe_engine* e, const int32_t* objects, int n) {
     return SBE_OK;
 }
 
+// The slot-derived kernel arguments of the source-posterior family (k_source_posterior, k_sample_source, k_source_logprob)
+// and of the cluster operators' four kernels (k_cluster_marginals[_ws], k_jump_lh[_ws]): each filled in ONE place.
+SrcPostArgs src_post_args(sbe_engine* e, int slot, const int32_t* d_objects, int n_sub, double temperature, double prior_temperature,
+                          int from_prior) {
+    const double inv_t = 1.0 / temperature, inv_tp = 1.0 / prior_temperature;
+    return SrcPostArgs{e->d_state, e->d_gid + (int64_t)slot * e->C * e->Np, e->d_pid + (int64_t)slot * e->Np,
+                       e->d_probs + (int64_t)slot * e->table_elems(), e->d_wpat + (int64_t)slot * e->Pmax * e->F * e->C,
+                       d_objects, n_sub, e->Np, e->F, e->S, e->C, e->Fp, inv_t, (float)inv_tp, inv_t != 1.0, inv_tp != 1.0,
+                       from_prior != 0};
+}
 
+ClusterOpArgs cluster_op_args(sbe_engine* e, int slot, double prior_temperature, const int32_t* d_objects, int n, double* d_out) {
+    const double inv = 1.0 / prior_temperature;
+    return ClusterOpArgs{e->d_state, e->d_gid + (int64_t)slot * e->C * e->Np, e->d_pid + (int64_t)slot * e->Np,
+                         e->d_weights + (int64_t)slot * e->F * e->C, e->d_patbits + (int64_t)slot * e->Pmax, (float)inv,
+                         inv != 1.0 ? 1 : 0, d_objects, n, d_out, reinterpret_cast<const f64x2_t*>(e->d_logtab),
+                         e->Np, e->F, e->S, e->C, e->Fp};
+}
 
 // k_given_unchanged_fused: LDS image of a 16-feature tile and the arguments both forms share
 constexpr size_t kGuFusedLdsMax = (size_t)96 << 10;

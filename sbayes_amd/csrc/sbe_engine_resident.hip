@@ -591,7 +591,8 @@ int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, doub
     rc = clear_status_word(e, ST_BAD_NORMALIZE);
     if (rc) return rc;
     const int32_t* cnt = e->d_counts + (int64_t)slot * e->table_elems();
-    const double inv = 1.0 / prior_temperature;
+    const float* probs = e->d_probs + (int64_t)slot * e->table_elems();
+    const ClusterOpArgs ca = cluster_op_args(e, slot, prior_temperature, (const int32_t*)e->d_io, n_objects_av, (double*)(e->d_io + ob));
     DoneSig done;
     if (fused) {
         InlineTables tin{};
@@ -602,11 +603,7 @@ int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, doub
         if (rc) return rc;
         const unsigned blocks = (unsigned)div_up(n_objects_av, kWsObjWaves);
         done = next_done(e, blocks);
-        k_cluster_marginals_ws<<<blocks, kWsBlock, cand_bytes, e->stream>>>(
-            e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-            e->d_probs + (int64_t)slot * e->table_elems(), e->d_weights + (int64_t)slot * F * C,
-            e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0, (const int32_t*)e->d_io, n_objects_av,
-            (double*)(e->d_io + ob), reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C, e->Fp, done, tin);
+        k_cluster_marginals_ws<<<blocks, kWsBlock, cand_bytes, e->stream>>>(ca, probs, done, tin);
     } else {
         rc = ensure_scratch(e, cand_bytes);
         if (rc) return rc;
@@ -616,11 +613,7 @@ int sbe_cluster_posterior_marginals(sbe_engine* e, int slot, int i_cluster, doub
             temperature, prior_temperature, 1, e->d_status, -(int64_t)i_cluster * fs);
         HIPCHK(e, hipGetLastError());
         done = next_done(e, (unsigned)n_objects_av);
-        k_cluster_marginals<<<n_objects_av, kBlock, 0, e->stream>>>(
-            e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-            e->d_probs + (int64_t)slot * e->table_elems(), d_tab, e->d_weights + (int64_t)slot * F * C,
-            e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0, (const int32_t*)e->d_io, n_objects_av,
-            (double*)(e->d_io + ob), reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C, e->Fp, done);
+        k_cluster_marginals<<<n_objects_av, kBlock, 0, e->stream>>>(ca, probs, d_tab, done);
     }
     HIPCHK(e, hipGetLastError());
     rc = sync_and_report(e, done);
@@ -663,7 +656,7 @@ int sbe_jump_lh_resident(sbe_engine* e, int slot, int i_source, int i_target, do
     rc = clear_status_word(e, ST_BAD_NORMALIZE);
     if (rc) return rc;
     const int32_t* cnt = e->d_counts + (int64_t)slot * e->table_elems();
-    const double inv = 1.0 / prior_temperature;
+    const ClusterOpArgs ca = cluster_op_args(e, slot, prior_temperature, (const int32_t*)e->d_io, n_members, (double*)(e->d_io + ob));
     DoneSig done;
     if (fused) {
         InlineTables tin{};
@@ -676,11 +669,7 @@ int sbe_jump_lh_resident(sbe_engine* e, int slot, int i_source, int i_target, do
         if (rc) return rc;
         const unsigned blocks = (unsigned)div_up(n_members, kWsObjWaves);
         done = next_done(e, blocks);
-        k_jump_lh_ws<<<blocks, kWsBlock, built_bytes, e->stream>>>(
-            e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-            e->d_weights + (int64_t)slot * F * C, e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0,
-            (const int32_t*)e->d_io, n_members, (double*)(e->d_io + ob), reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C,
-            e->Fp, K, done, tin);
+        k_jump_lh_ws<<<blocks, kWsBlock, built_bytes, e->stream>>>(ca, K, done, tin);
     } else {
         rc = ensure_scratch(e, (size_t)(2 + std::max(n_conf, 1)) * fs * sizeof(float));
         if (rc) return rc;
@@ -699,11 +688,7 @@ int sbe_jump_lh_resident(sbe_engine* e, int slot, int i_source, int i_target, do
             HIPCHK(e, hipGetLastError());
         }
         done = next_done(e, (unsigned)n_members);
-        k_jump_lh<<<n_members, kBlock, 0, e->stream>>>(
-            e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np, d_pc, d_ps, d_pt,
-            e->d_weights + (int64_t)slot * F * C, e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0,
-            (const int32_t*)e->d_io, n_members, (double*)(e->d_io + ob), reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C,
-            e->Fp, K, done);
+        k_jump_lh<<<n_members, kBlock, 0, e->stream>>>(ca, d_pc, d_ps, d_pt, K, done);
     }
     HIPCHK(e, hipGetLastError());
     rc = sync_and_report(e, done);

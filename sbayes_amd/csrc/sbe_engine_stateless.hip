@@ -165,16 +165,15 @@ int sbe_cluster_marginals(sbe_engine* e, int slot, const float* table, const int
     if (n_objects_av == 0) return SBE_OK;
     CHECK_PTR(e, objects);
     if (!(prior_temperature > 0.0)) return fail(e, SBE_ERR_ARG, "prior_temperature must be positive");
-    for (int i = 0; i < n_objects_av; ++i)
-        if (objects[i] < 0 || objects[i] >= e->N) return fail(e, SBE_ERR_ARG, "object index %d out of range", objects[i]);
-    int rc = check_slot_ready(e, slot, true);
+    int rc = check_objects(e, objects, n_objects_av);
+    if (rc) return rc;
+    rc = check_slot_ready(e, slot, true);
     if (rc) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     Slot& s = e->slots[slot];
     if (s.patterns_dirty) { rc = upload_patterns_and_weights(e, slot); if (rc) return rc; }
-    const int F = e->F, S = e->S, C = e->C;
-    const size_t tb = ((size_t)F * S * sizeof(float) + 255) / 256 * 256;
-    const size_t ob = ((size_t)n_objects_av * sizeof(int32_t) + 255) / 256 * 256;
+    const int F = e->F, S = e->S;
+    const size_t tb = al256((size_t)F * S * sizeof(float)), ob = al256((size_t)n_objects_av * sizeof(int32_t));
     const size_t out_bytes = (size_t)2 * n_objects_av * sizeof(double);
     // table, object list and the result live in host-mapped memory (a few KB each): ONE kernel and one
     // synchronisation, no copy-engine operation in the chain
@@ -182,16 +181,10 @@ int sbe_cluster_marginals(sbe_engine* e, int slot, const float* table, const int
     if (rc) return rc;
     memcpy(e->h_io, table, (size_t)F * S * sizeof(float));
     memcpy(e->h_io + tb, objects, (size_t)n_objects_av * sizeof(int32_t));
-    const float* d_tab = (const float*)e->d_io;
-    const int32_t* d_obj = (const int32_t*)(e->d_io + tb);
-    double* d_out = (double*)(e->d_io + tb + ob);
-    const double inv = 1.0 / prior_temperature;
     const DoneSig done = next_done(e, (unsigned)n_objects_av);
     k_cluster_marginals<<<n_objects_av, kBlock, 0, e->stream>>>(
-        e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-        e->d_probs + (int64_t)slot * e->table_elems(), d_tab, e->d_weights + (int64_t)slot * F * C,
-        e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0, d_obj, n_objects_av, d_out,
-        reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C, e->Fp, done);
+        cluster_op_args(e, slot, prior_temperature, (const int32_t*)(e->d_io + tb), n_objects_av, (double*)(e->d_io + tb + ob)),
+        e->d_probs + (int64_t)slot * e->table_elems(), (const float*)e->d_io, done);
     HIPCHK(e, hipGetLastError());
     rc = wait_done(e, done);
     if (rc) return rc;
@@ -207,20 +200,16 @@ int sbe_jump_lh(sbe_engine* e, int slot, const float* pconf, const float* p_sour
     if (n_members == 0) return SBE_OK;
     CHECK_PTR(e, objects);
     if (!(prior_temperature > 0.0)) return fail(e, SBE_ERR_ARG, "prior_temperature must be positive");
-    for (int i = 0; i < n_members; ++i)
-        if (objects[i] < 0 || objects[i] >= e->N) return fail(e, SBE_ERR_ARG, "object index %d out of range", objects[i]);
+    int rc = check_objects(e, objects, n_members);
+    if (rc) return rc;
     Slot& s = e->slots[slot];
     if (!s.groups_set || !s.weights_set) return fail(e, SBE_ERR_STATE, "slot %d: groups / weights not set", slot);
     const int n_conf_groups = e->Gtot - e->G[0];
     if (n_conf_groups > 0) CHECK_PTR(e, pconf);
     HIPCHK(e, hipSetDevice(e->device));
-    int rc = SBE_OK;
     if (s.patterns_dirty) { rc = upload_patterns_and_weights(e, slot); if (rc) return rc; }
-    const int F = e->F, S = e->S, C = e->C;
-    const size_t fs = (size_t)F * S * sizeof(float);
-    const size_t cb = ((size_t)std::max(n_conf_groups, 1) * fs + 255) / 256 * 256;
-    const size_t tb = (fs + 255) / 256 * 256;
-    const size_t ob = ((size_t)n_members * sizeof(int32_t) + 255) / 256 * 256;
+    const size_t fs = (size_t)e->F * e->S * sizeof(float);
+    const size_t cb = al256((size_t)std::max(n_conf_groups, 1) * fs), tb = al256(fs), ob = al256((size_t)n_members * sizeof(int32_t));
     const size_t out_bytes = (size_t)2 * n_members * sizeof(double);
     // tables, member list and result in host-mapped memory: ONE kernel, one synchronisation (as sbe_cluster_marginals)
     rc = ensure_io(e, cb + 2 * tb + ob + out_bytes);
@@ -229,14 +218,10 @@ int sbe_jump_lh(sbe_engine* e, int slot, const float* pconf, const float* p_sour
     memcpy(e->h_io + cb, p_source, fs);
     memcpy(e->h_io + cb + tb, p_target, fs);
     memcpy(e->h_io + cb + 2 * tb, objects, (size_t)n_members * sizeof(int32_t));
-    const double inv = 1.0 / prior_temperature;
     const DoneSig done = next_done(e, (unsigned)n_members);
     k_jump_lh<<<n_members, kBlock, 0, e->stream>>>(
-        e->d_state, e->d_gid + (int64_t)slot * C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-        (const float*)e->d_io, (const float*)(e->d_io + cb), (const float*)(e->d_io + cb + tb),
-        e->d_weights + (int64_t)slot * F * C, e->d_patbits + (int64_t)slot * e->Pmax, (float)inv, inv != 1.0 ? 1 : 0,
-        (const int32_t*)(e->d_io + cb + 2 * tb), n_members, (double*)(e->d_io + cb + 2 * tb + ob),
-        reinterpret_cast<const f64x2_t*>(e->d_logtab), e->Np, F, S, C, e->Fp, e->G[0], done);
+        cluster_op_args(e, slot, prior_temperature, (const int32_t*)(e->d_io + cb + 2 * tb), n_members, (double*)(e->d_io + cb + 2 * tb + ob)),
+        (const float*)e->d_io, (const float*)(e->d_io + cb), (const float*)(e->d_io + cb + tb), e->G[0], done);
     HIPCHK(e, hipGetLastError());
     rc = wait_done(e, done);
     if (rc) return rc;
@@ -295,11 +280,7 @@ int source_posterior_setup(sbe_engine* e, int slot, const int32_t* objects, int 
     const int32_t* d_obj = (const int32_t*)v_obj;
     rc = clear_status_word(e, ST_BAD_NORMALIZE);
     if (rc) return rc;
-    const double inv_t = 1.0 / temperature, inv_tp = 1.0 / prior_temperature;
-    *a = SrcPostArgs{e->d_state, e->d_gid + (int64_t)slot * e->C * e->Np, e->d_pid + (int64_t)slot * e->Np,
-                     e->d_probs + (int64_t)slot * e->table_elems(), e->d_wpat + (int64_t)slot * e->Pmax * e->F * e->C,
-                     d_obj, n_sub, e->Np, e->F, e->S, e->C, e->Fp, inv_t, (float)inv_tp, inv_t != 1.0, inv_tp != 1.0,
-                     from_prior != 0};
+    *a = src_post_args(e, slot, d_obj, n_sub, temperature, prior_temperature, from_prior);
     return SBE_OK;
 }
 

@@ -1057,16 +1057,13 @@ int sbe_step_delta(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* mo
     return read_step_results(e, cand_slot, group_logliks_out, mixture_out, changed_groups_out, "rows");
 }
 
-// ---- one-call Gibbs source step (GibbsSampleSource._propose, operators.py:495-552, on the resident state) ------
-// candidate = current with the source of the listed objects redrawn from its posterior ON THE DEVICE; count delta,
-// every table, both transition log-probabilities, collapsed per-group and mixture log-likelihood of the candidate:
-// five launches, one synchronisation; objects (and the caller's uniforms) are read from host-mapped memory, all
-// results arrive through host-mapped memory.
-int sbe_gibbs_step(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* objects, int n_sub, double temperature,
-                   double prior_temperature, int from_prior, const double* z, double* log_q_out, double* log_q_back_out,
-                   double* group_logliks_out, double* mixture_out, uint8_t* changed_groups_out) {
-    CHECK_ENGINE(e); CHECK_SLOT(e, cur_slot); CHECK_SLOT(e, cand_slot);
-    CHECK_PTR(e, log_q_out); CHECK_PTR(e, log_q_back_out); CHECK_PTR(e, group_logliks_out); CHECK_PTR(e, mixture_out);
+// ---- the Gibbs chain on the resident state, shared by sbe_gibbs_step and the chain form of sbe_gibbs_propose: the draw into the
+// candidate slot (k_sample_source), the rest of that slot with its count delta and every table (k_step_core), the backward
+// probabilities (k_source_logprob).  What the two callers do differently stands at their call sites: which outputs they check,
+// their own "tables too large" message, whether ST_BAD_NORMALIZE is cleared first, where the selected probabilities go (scratch /
+// the mapped result block) and how the call finishes (StepFinish + launch_mixture / k_gibbs_fetch).
+static int gibbs_chain_check(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* objects, int n_sub, double temperature,
+                             double prior_temperature) {
     if (cur_slot == cand_slot) return fail(e, SBE_ERR_ARG, "current and candidate slot must differ");
     if (n_sub < 1) return fail(e, SBE_ERR_ARG, "n_sub=%d (nothing to resample)", n_sub);
     CHECK_PTR(e, objects);
@@ -1077,83 +1074,113 @@ int sbe_gibbs_step(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* ob
     for (int c = 0; c < e->C; ++c)
         if (!cur.counts_set[c] || !e->conc_set[c] || !cur.probs_set[c])
             return fail(e, SBE_ERR_STATE, "slot %d: counts / concentration / probability tables of component %d not set", cur_slot, c);
-    for (int i = 0; i < n_sub; ++i)
-        if (objects[i] < 0 || objects[i] >= e->N) return fail(e, SBE_ERR_ARG, "object index %d out of range", objects[i]);
-    if ((int64_t)e->Gtot * e->S * 28 > 60 * 1024)
-        return fail(e, SBE_ERR_ARG, "one-call Gibbs step: tables too large for the fused table kernel (G_total=%d, S=%d)", e->Gtot, e->S);
+    return check_objects(e, objects, n_sub);
+}
+
+static int gibbs_chain_ready(sbe_engine* e, int cur_slot) {            // the device, before the call's first launch
     HIPCHK(e, hipSetDevice(e->device));
-    if (cur.patterns_dirty) { int rc = upload_patterns_and_weights(e, cur_slot); if (rc) return rc; }
-    if (e->status_pending) {                  // deliver a deferred data check before this step reuses the words
+    if (e->slots[cur_slot].patterns_dirty) { int rc = upload_patterns_and_weights(e, cur_slot); if (rc) return rc; }
+    if (e->status_pending) {                  // deliver a deferred data check before this call reuses the words
         HIPCHK(e, hipStreamSynchronize(e->stream));
-        int rc = synced(e);
-        if (rc) return rc;
+        return synced(e);
     }
-    const int N = e->N, Np = e->Np, F = e->F, C = e->C;
-    const int64_t n_obs = (int64_t)n_sub * F;
-    // host-mapped inputs: objects | row_of marks | uniforms (when they are few; a large block is copied instead)
-    const size_t ob = ((size_t)n_sub * sizeof(int32_t) + 255) / 256 * 256;
-    const size_t rb = ((size_t)Np * sizeof(int16_t) + 255) / 256 * 256;
-    const size_t zbytes = z ? (size_t)n_obs * sizeof(double) : 0;
+    return SBE_OK;
+}
+
+// The chain's host-mapped input block: objects | row_of marks | `xb` bytes of the caller's (at ob + rb) | uniforms (mapped if
+// they are at most 512 KB, else uploaded to scratch; z == nullptr: none); `out_bytes` of mapped results follow at in_bytes.
+// Device scratch: `front_bytes` of the caller's | the two kernels' per-block log-sum partials | uploaded uniforms.
+struct GibbsChainBlock { size_t ob, rb, in_bytes; const int32_t* d_obj; const double* d_z; int nblk; double* d_part[2]; };
+
+static int gibbs_chain_stage(sbe_engine* e, const int32_t* objects, int n_sub, const double* z, size_t xb, size_t out_bytes,
+                             size_t front_bytes, GibbsChainBlock* b) {
+    const int64_t n_obs = (int64_t)n_sub * e->F;
+    b->ob = al256((size_t)n_sub * sizeof(int32_t)); b->rb = al256((size_t)e->Np * sizeof(int16_t));
+    const size_t zbytes = z ? (size_t)n_obs * sizeof(double) : 0, z_at = b->ob + b->rb + xb;
     const bool z_mapped = zbytes <= ((size_t)1 << 19);
-    int rc = ensure_io(e, ob + rb + (z_mapped ? zbytes : 0));
+    b->in_bytes = z_at + (z_mapped ? al256(zbytes) : 0);
+    int rc = ensure_io(e, b->in_bytes + out_bytes);
     if (rc) return rc;
     memcpy(e->h_io, objects, (size_t)n_sub * sizeof(int32_t));
-    int16_t* row_of = reinterpret_cast<int16_t*>(e->h_io + ob);
-    std::fill(row_of, row_of + Np, (int16_t)-1);
+    int16_t* row_of = reinterpret_cast<int16_t*>(e->h_io + b->ob);
+    std::fill(row_of, row_of + e->Np, (int16_t)-1);
     for (int i = 0; i < n_sub; ++i) row_of[objects[i]] = 0;
-    const int32_t* d_obj = reinterpret_cast<const int32_t*>(e->d_io);
-    // device scratch: selected probabilities (forward / back), their partial log sums, uniforms if copied
-    const size_t pb = ((size_t)n_obs * sizeof(float) + 255) / 256 * 256;
-    const size_t zb = (z && !z_mapped) ? (zbytes + 255) / 256 * 256 : 0;
-    const int nblk = div_up(n_obs, kBlock);                   // one log-sum partial per block of the two posterior kernels
-    const size_t qb_bytes = ((size_t)nblk * sizeof(double) + 255) / 256 * 256;
-    rc = ensure_scratch(e, 2 * pb + 2 * qb_bytes + zb);
+    b->d_obj = reinterpret_cast<const int32_t*>(e->d_io);
+    b->nblk = div_up(n_obs, kBlock);                          // one log-sum partial per block of the two posterior kernels
+    const size_t qb_bytes = al256((size_t)b->nblk * sizeof(double));
+    rc = ensure_scratch(e, front_bytes + 2 * qb_bytes + (z_mapped ? 0 : al256(zbytes)));
     if (rc) return rc;
-    float* d_psel_f = (float*)e->d_scratch;
-    float* d_psel_b = (float*)(e->d_scratch + pb);
-    double* d_part_f = (double*)(e->d_scratch + 2 * pb);
-    double* d_part_b = (double*)(e->d_scratch + 2 * pb + qb_bytes);
-    const double* d_z = nullptr;
-    if (z && z_mapped) { memcpy(e->h_io + ob + rb, z, zbytes); d_z = reinterpret_cast<const double*>(e->d_io + ob + rb); }
+    b->d_part[0] = (double*)(e->d_scratch + front_bytes);
+    b->d_part[1] = (double*)(e->d_scratch + front_bytes + qb_bytes);
+    b->d_z = nullptr;
+    if (z && z_mapped) { memcpy(e->h_io + z_at, z, zbytes); b->d_z = reinterpret_cast<const double*>(e->d_io + z_at); }
     else if (z) {
-        double* dz = (double*)(e->d_scratch + 2 * pb + 2 * qb_bytes);
-        int _urc = upload(e, dz, z, zbytes); if (_urc) return _urc;
-        d_z = dz;
+        double* dz = (double*)(e->d_scratch + front_bytes + 2 * qb_bytes);
+        rc = upload(e, dz, z, zbytes); if (rc) return rc;
+        b->d_z = dz;
     }
-    const double inv_t = 1.0 / temperature, inv_tp = 1.0 / prior_temperature;
-    auto post_args = [&](int slot) {
-        return SrcPostArgs{e->d_state, e->d_gid + (int64_t)slot * C * Np, e->d_pid + (int64_t)slot * Np,
-                           e->d_probs + (int64_t)slot * e->table_elems(), e->d_wpat + (int64_t)slot * e->Pmax * F * C,
-                           d_obj, n_sub, Np, F, e->S, C, e->Fp, inv_t, (float)inv_tp, inv_t != 1.0, inv_tp != 1.0,
-                           from_prior != 0};
-    };
-    uint8_t* src_cand = e->d_src + (int64_t)cand_slot * N * e->Fp;
-    bump_src(e, cand_slot);                  // (the Gibbs step draws into the candidate's array and copies the rest in full)
+    return SBE_OK;
+}
+
+// draw -> step core -> backward probabilities; the selected probabilities of the two passes go to d_psel_f / d_psel_b
+static int gibbs_chain_run(sbe_engine* e, int cur_slot, int cand_slot, const GibbsChainBlock& b, int n_sub, double temperature,
+                           double prior_temperature, int from_prior, float* d_psel_f, float* d_psel_b) {
+    uint8_t* src_cand = e->d_src + (int64_t)cand_slot * e->N * e->Fp;
+    bump_src(e, cand_slot);                  // (the chain draws into the candidate's array and copies the rest in full)
     bump_ids(e, cand_slot);
-    // 1: the draw (posterior from the current tables) -> the candidate's source rows of the listed objects, and the
+    // 1: the draw (posterior from the current tables) -> the candidate's source rows of the listed objects, p[drawn] and the
     //    per-block partial sums of log_q
-    k_sample_source<<<nblk, kBlock, 0, e->stream>>>(post_args(cur_slot), d_z, e->rng_seed, e->rng_draw, src_cand, d_psel_f, e->d_status, d_part_f);
-    if (!z) ++e->rng_draw;
+    k_sample_source<<<b.nblk, kBlock, 0, e->stream>>>(src_post_args(e, cur_slot, b.d_obj, n_sub, temperature, prior_temperature, from_prior),
+                                                      b.d_z, e->rng_seed, e->rng_draw, src_cand, d_psel_f, e->d_status, b.d_part[0]);
+    if (!b.d_z) ++e->rng_draw;               // (the engine's own stream: sbe_gibbs_step without uniforms -- the proposal insists on them)
     HIPCHK(e, hipGetLastError());
     // 2: the rest of the candidate slot, its count delta and every one of its tables
-    Slot cd = cur;
+    Slot cd = e->slots[cur_slot];
     {
         CoreInputs in;
-        in.row_of = reinterpret_cast<const int16_t*>(e->d_io + ob);
+        in.row_of = reinterpret_cast<const int16_t*>(e->d_io + b.ob);
         in.src_new = src_cand;
-        in.subset = d_obj; in.n_subset = n_sub;
+        in.subset = b.d_obj; in.n_subset = n_sub;
         in.P = (int)cd.patterns.size();
-        rc = launch_step_core(e, cur_slot, cand_slot, in);
+        int rc = launch_step_core(e, cur_slot, cand_slot, in);
         if (rc) return rc;
     }
     std::fill(cd.probs_set.begin(), cd.probs_set.end(), 1);
     e->slots[cand_slot] = cd;
-    // 3: log_q_back -- the candidate's posterior evaluated at the CURRENT source assignment (+ its partial sums)
-    k_source_logprob<<<nblk, kBlock, 0, e->stream>>>(post_args(cand_slot), e->d_src + (int64_t)cur_slot * N * e->Fp, d_psel_b, e->d_status, d_part_b);
+    // 3: log_q_back -- the candidate's posterior evaluated at the CURRENT source assignment: p_back[old source] (+ its partial sums)
+    k_source_logprob<<<b.nblk, kBlock, 0, e->stream>>>(src_post_args(e, cand_slot, b.d_obj, n_sub, temperature, prior_temperature, from_prior),
+                                                       e->d_src + (int64_t)cur_slot * e->N * e->Fp, d_psel_b, e->d_status, b.d_part[1]);
     HIPCHK(e, hipGetLastError());
+    return SBE_OK;
+}
+
+// ---- one-call Gibbs source step (GibbsSampleSource._propose, operators.py:495-552, on the resident state) ------
+// candidate = current with the source of the listed objects redrawn from its posterior ON THE DEVICE; count delta,
+// every table, both transition log-probabilities, collapsed per-group and mixture log-likelihood of the candidate:
+// five launches, one synchronisation; objects (and the caller's uniforms) are read from host-mapped memory, all
+// results arrive through host-mapped memory.
+int sbe_gibbs_step(sbe_engine* e, int cur_slot, int cand_slot, const int32_t* objects, int n_sub, double temperature,
+                   double prior_temperature, int from_prior, const double* z, double* log_q_out, double* log_q_back_out,
+                   double* group_logliks_out, double* mixture_out, uint8_t* changed_groups_out) {
+    CHECK_ENGINE(e); CHECK_SLOT(e, cur_slot); CHECK_SLOT(e, cand_slot);
+    CHECK_PTR(e, log_q_out); CHECK_PTR(e, log_q_back_out); CHECK_PTR(e, group_logliks_out); CHECK_PTR(e, mixture_out);
+    int rc = gibbs_chain_check(e, cur_slot, cand_slot, objects, n_sub, temperature, prior_temperature);
+    if (rc) return rc;
+    if (!sbe_gibbs_propose_supported(e))
+        return fail(e, SBE_ERR_ARG, "one-call Gibbs step: tables too large for the fused table kernel (G_total=%d, S=%d)", e->Gtot, e->S);
+    rc = gibbs_chain_ready(e, cur_slot);
+    if (rc) return rc;
+    // 1 - 3: the chain (z == nullptr: the engine's own stream); the selected probabilities (forward / back) stay in device scratch
+    const size_t pb = al256((size_t)n_sub * e->F * sizeof(float));
+    GibbsChainBlock b;
+    rc = gibbs_chain_stage(e, objects, n_sub, z, 0, 0, 2 * pb, &b);
+    if (rc) return rc;
+    rc = gibbs_chain_run(e, cur_slot, cand_slot, b, n_sub, temperature, prior_temperature, from_prior, (float*)e->d_scratch,
+                         (float*)(e->d_scratch + pb));
+    if (rc) return rc;
     // 4 + 5: fused mixture eval, reduction + epilogue (per-group collapsed values, flags, checks, log_q / log_q_back)
     StepFinish fin = make_step_finish(e);
-    fin.lq_partials[0] = d_part_f; fin.lq_partials[1] = d_part_b; fin.lq_n[0] = fin.lq_n[1] = nblk;
+    fin.lq_partials[0] = b.d_part[0]; fin.lq_partials[1] = b.d_part[1]; fin.lq_n[0] = fin.lq_n[1] = b.nblk;
     fin.lq_out = reinterpret_cast<double*>(e->d_step_host + step_host_lq_offset(e));
     DoneSig done;
     MixCall mix;
@@ -1256,18 +1283,9 @@ static int gibbs_propose_impl(sbe_engine* e, int cur_slot, int cand_slot, const 
     CHECK_ENGINE(e); CHECK_SLOT(e, cur_slot); CHECK_SLOT(e, cand_slot);
     CHECK_PTR(e, src_new_out); CHECK_PTR(e, sel_out); CHECK_PTR(e, sel_back_out); CHECK_PTR(e, touched_out); CHECK_PTR(e, n_touched_out);
     CHECK_PTR(e, diff_rows_out); CHECK_PTR(e, z);
-    if (cur_slot == cand_slot) return fail(e, SBE_ERR_ARG, "current and candidate slot must differ");
-    if (n_sub < 1) return fail(e, SBE_ERR_ARG, "n_sub=%d (nothing to resample)", n_sub);
-    CHECK_PTR(e, objects);
-    if (!(temperature > 0.0) || !(prior_temperature > 0.0)) return fail(e, SBE_ERR_ARG, "temperatures must be positive");
-    Slot& cur = e->slots[cur_slot];
-    if (!cur.groups_set || !cur.source_set || !cur.weights_set) return fail(e, SBE_ERR_STATE, "slot %d: groups / source / weights not set", cur_slot);
-    { int orc = reject_overlap(e, cur_slot, "one-call step"); if (orc) return orc; }
-    for (int c = 0; c < e->C; ++c)
-        if (!cur.counts_set[c] || !e->conc_set[c] || !cur.probs_set[c])
-            return fail(e, SBE_ERR_STATE, "slot %d: counts / concentration / probability tables of component %d not set", cur_slot, c);
-    int rc = check_objects(e, objects, n_sub);
+    int rc = gibbs_chain_check(e, cur_slot, cand_slot, objects, n_sub, temperature, prior_temperature);
     if (rc) return rc;
+    Slot& cur = e->slots[cur_slot];
     const int N = e->N, Np = e->Np, F = e->F, C = e->C, S = e->S;
     const int64_t n_obs = (int64_t)n_sub * F, fs = (int64_t)F * S;
     // the groups the subset's objects are in (their count rows are the only ones the redraw can change), ascending
@@ -1280,13 +1298,8 @@ static int gibbs_propose_impl(sbe_engine* e, int cur_slot, int cand_slot, const 
     int n_touched = 0;
     for (int g = 0; g < e->Gtot; ++g) if (seen[g]) touched_out[n_touched++] = g;
     *n_touched_out = n_touched;
-    HIPCHK(e, hipSetDevice(e->device));
-    if (cur.patterns_dirty) { rc = upload_patterns_and_weights(e, cur_slot); if (rc) return rc; }
-    if (e->status_pending) {                  // deliver a deferred data check before this call reuses the words
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        rc = synced(e);
-        if (rc) return rc;
-    }
+    rc = gibbs_chain_ready(e, cur_slot);
+    if (rc) return rc;
     // ---- tile form: the whole proposal in ONE kernel (k_gibbs_propose_tile), no candidate slot built ----
     {
         const size_t t_ob = al256((size_t)n_sub * sizeof(int32_t)), t_gb = al256((size_t)C * n_sub * sizeof(int32_t));
@@ -1364,79 +1377,33 @@ static int gibbs_propose_impl(sbe_engine* e, int cur_slot, int cand_slot, const 
     if (!sbe_gibbs_propose_supported(e))
         return fail(e, SBE_ERR_ARG, "sbe_gibbs_propose: tables too large for the fused table kernel (G_total=%d, S=%d)", e->Gtot, e->S);
     // host-mapped block: objects | row_of marks | touched | uniforms (when few) || ids | sel | sel_back | count rows
-    const size_t ob = al256((size_t)n_sub * sizeof(int32_t)), rb = al256((size_t)Np * sizeof(int16_t));
     const size_t tb = al256((size_t)std::max(n_touched, 1) * sizeof(int32_t));
-    const size_t zbytes = (size_t)n_obs * sizeof(double);
-    const bool z_mapped = zbytes <= ((size_t)1 << 19);
-    const size_t zb = z_mapped ? al256(zbytes) : 0;
     const size_t idb = al256((size_t)n_obs), selb = al256((size_t)n_obs * sizeof(float));
     const size_t rowb = al256((size_t)std::max(n_touched, 1) * fs * sizeof(float));
-    const size_t in_bytes = ob + rb + tb + zb, out_bytes = idb + 2 * selb + rowb;
+    const size_t out_bytes = idb + 2 * selb + rowb;
     if (out_bytes > ((size_t)8 << 20)) return fail(e, SBE_ERR_ARG, "sbe_gibbs_propose: %d objects x %d features exceed the mapped result block", n_sub, F);
-    rc = ensure_io(e, in_bytes + out_bytes);
+    GibbsChainBlock b;
+    rc = gibbs_chain_stage(e, objects, n_sub, z, tb, out_bytes, 0, &b);
     if (rc) return rc;
+    const size_t in_bytes = b.in_bytes;
     uint8_t* h = e->h_io;
-    memcpy(h, objects, (size_t)n_sub * sizeof(int32_t));
-    int16_t* row_of = reinterpret_cast<int16_t*>(h + ob);
-    std::fill(row_of, row_of + Np, (int16_t)-1);
-    for (int i = 0; i < n_sub; ++i) row_of[objects[i]] = 0;
-    memcpy(h + ob + rb, touched_out, (size_t)n_touched * sizeof(int32_t));
-    const int32_t* d_obj = reinterpret_cast<const int32_t*>(e->d_io);
-    const int nblk = div_up(n_obs, kBlock);
-    const size_t qb_bytes = al256((size_t)nblk * sizeof(double));
-    rc = ensure_scratch(e, 2 * qb_bytes + (z_mapped ? 0 : al256(zbytes)));
-    if (rc) return rc;
-    double* d_part_f = (double*)e->d_scratch;
-    double* d_part_b = (double*)(e->d_scratch + qb_bytes);
-    const double* d_z;
-    if (z_mapped) { memcpy(h + ob + rb + tb, z, zbytes); d_z = reinterpret_cast<const double*>(e->d_io + ob + rb + tb); }
-    else {
-        double* dz = (double*)(e->d_scratch + 2 * qb_bytes);
-        int urc = upload(e, dz, z, zbytes); if (urc) return urc;
-        d_z = dz;
-    }
+    memcpy(h + b.ob + b.rb, touched_out, (size_t)n_touched * sizeof(int32_t));
     uint8_t* d_ids = e->d_io + in_bytes;
-    float* d_psel_f = (float*)(d_ids + idb);
-    float* d_psel_b = (float*)(d_ids + idb + selb);
     float* d_rows = (float*)(d_ids + idb + 2 * selb);
     rc = clear_status_word(e, ST_BAD_NORMALIZE);
     if (rc) return rc;
-    const double inv_t = 1.0 / temperature, inv_tp = 1.0 / prior_temperature;
-    auto post_args = [&](int slot) {
-        return SrcPostArgs{e->d_state, e->d_gid + (int64_t)slot * C * Np, e->d_pid + (int64_t)slot * Np,
-                           e->d_probs + (int64_t)slot * e->table_elems(), e->d_wpat + (int64_t)slot * e->Pmax * F * C,
-                           d_obj, n_sub, Np, F, S, C, e->Fp, inv_t, (float)inv_tp, inv_t != 1.0, inv_tp != 1.0,
-                           from_prior != 0};
-    };
-    uint8_t* src_cand = e->d_src + (int64_t)cand_slot * N * e->Fp;
-    bump_src(e, cand_slot);
-    bump_ids(e, cand_slot);
-    // 1: the draw (posterior from the current tables) -> the candidate's source rows of the listed objects; p[drawn] out
-    k_sample_source<<<nblk, kBlock, 0, e->stream>>>(post_args(cur_slot), d_z, e->rng_seed, e->rng_draw, src_cand, d_psel_f, e->d_status, d_part_f);
-    HIPCHK(e, hipGetLastError());
-    // 2: the rest of the candidate slot, its count delta and every one of its tables
-    Slot cd = cur;
-    {
-        CoreInputs in;
-        in.row_of = reinterpret_cast<const int16_t*>(e->d_io + ob);
-        in.src_new = src_cand;
-        in.subset = d_obj; in.n_subset = n_sub;
-        in.P = (int)cd.patterns.size();
-        rc = launch_step_core(e, cur_slot, cand_slot, in);
-        if (rc) return rc;
-    }
-    std::fill(cd.probs_set.begin(), cd.probs_set.end(), 1);
-    e->slots[cand_slot] = cd;
-    // 3: the candidate's posterior evaluated at the CURRENT source assignment; p_back[old source] out
-    k_source_logprob<<<nblk, kBlock, 0, e->stream>>>(post_args(cand_slot), e->d_src + (int64_t)cur_slot * N * e->Fp, d_psel_b, e->d_status, d_part_b);
-    HIPCHK(e, hipGetLastError());
+    // 1 - 3: the chain; p[drawn] and p_back[old source] go straight into the mapped result block
+    rc = gibbs_chain_run(e, cur_slot, cand_slot, b, n_sub, temperature, prior_temperature, from_prior, (float*)(d_ids + idb),
+                         (float*)(d_ids + idb + selb));
+    if (rc) return rc;
     // 4: drawn ids and changed count rows, completion
     const int64_t n_el = n_obs + (int64_t)n_touched * fs;
     const unsigned blocks = (unsigned)std::min<int64_t>(div_up(n_el, 256), 256);
     const DoneSig done = next_done(e, blocks);
-    k_gibbs_fetch<<<blocks, 256, 0, e->stream>>>(src_cand, d_obj, n_sub, d_ids, e->d_counts + (int64_t)cur_slot * e->table_elems(),
+    k_gibbs_fetch<<<blocks, 256, 0, e->stream>>>(e->d_src + (int64_t)cand_slot * N * e->Fp, b.d_obj, n_sub, d_ids,
+                                                e->d_counts + (int64_t)cur_slot * e->table_elems(),
                                                 e->d_counts + (int64_t)cand_slot * e->table_elems(),
-                                                reinterpret_cast<const int32_t*>(e->d_io + ob + rb), n_touched, d_rows, F, S, e->Fp, done);
+                                                reinterpret_cast<const int32_t*>(e->d_io + b.ob + b.rb), n_touched, d_rows, F, S, e->Fp, done);
     HIPCHK(e, hipGetLastError());
     rc = sync_and_report(e, done);
     if (rc) return rc;

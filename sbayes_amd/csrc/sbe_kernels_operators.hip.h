@@ -105,80 +105,152 @@ __device__ __forceinline__ void weight_tables_z_row_reg(const float* __restrict_
     }
 }
 
+// What a call of the four kernels below takes from its slot and its caller, the same for all four (the host fills it in one
+// place: cluster_op_args).  What differs stays beside it: table0 / probs, the three jump tables and G0, InlineTables.
+struct ClusterOpArgs {
+    const uint8_t* state; const uint16_t* gid; const uint8_t* pid;
+    const float* weights; const uint32_t* pattern_bits; float inv_tp; int use_pow;
+    const int32_t* objects; int n; double* out;          // the listed objects; out [2][n]
+    const f64x2_t* logtab;
+    int Np, F, S, C, Fp;
+};
+
+// ---- the arithmetic and the steps the block forms and the wave-specialised forms share: written once, so that "the same
+// ---- bits in every form" (tests/test_gpu_clusterop_range.py) is what the code says and not only what a comment promises ----
+__device__ __forceinline__ uint32_t log_tab_addr(const f64x2_t* tab) {
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const f64x2_t*)tab;
+}
+
+// One observation's term of the marginals: the fp64 chains over the components in order, then the two table-driven logs.
+template <int CM>
+__device__ __forceinline__ void marginals_term(const float (&lh)[CM], const float (&wc)[CM], const float (&wf)[CM], int C, bool inside,
+                                               uint32_t tab_addr, double& acc0, double& acc1) {
+    double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+        if (c < C) {
+            const double l = (double)lh[c], a = (double)wc[c], b = (double)wf[c];
+            const double w1 = inside ? a : b, w0 = inside ? b : a;   // z = 1: the object is (or becomes) a cluster member
+            v1 = v1 + l * w1;
+            v0 = v0 + l * w0;
+        }
+    }
+    acc0 += tab_log_pos(v0, tab_addr);
+    acc1 += tab_log_pos(v1, tab_addr);
+}
+
+// One observation's term of the jump scores: the reference's float32 chain over the confounder groups the object is in (gg[c] !=
+// kNoGroup; c = 0 is the cluster), then stay / jump and their logs.  The table entries come in as VALUES (pcf[c], e_src, e_tgt):
+// the caller has asked for every one of them before the first is used here.
+template <int CM>
+__device__ __forceinline__ void jump_term(const float (&wc)[CM], const float (&pcf)[CM], const uint16_t (&gg)[CM], float e_src, float e_tgt,
+                                          uint32_t tab_addr, double& acc0, double& acc1) {
+    float pc = 0.0f;
+#pragma unroll
+    for (int c = 1; c < CM; ++c)
+        if (gg[c] != kNoGroup) pc = pc + wc[c] * pcf[c];
+    const float ps = pc + wc[0] * e_src;
+    const float pt = pc + wc[0] * e_tgt;
+    acc0 += tab_log_pos((double)ps, tab_addr);
+    acc1 += tab_log_pos((double)pt, tab_addr);
+}
+
+// Object i's two results from four partial sums each -- the four waves' of the block forms, the four feature columns' of
+// the wave-specialised forms, which are the same four numbers -- added in one fixed order.
+__device__ __forceinline__ void store_pair(const ClusterOpArgs& a, int i, const double (&r0)[4], const double (&r1)[4]) {
+    a.out[i] = (r0[0] + r0[1]) + (r0[2] + r0[3]);
+    a.out[(int64_t)a.n + i] = (r1[0] + r1[1]) + (r1[2] + r1[3]);
+}
+
+// Block forms: the log table into LDS (returns its address); the fixed-order block reduction of the two accumulators.
+__device__ __forceinline__ uint32_t block_log_table(f64x2_t* tab, const f64x2_t* __restrict__ logtab) {
+    if (threadIdx.x < kLogTabEntries) tab[threadIdx.x] = logtab[threadIdx.x];
+    __syncthreads();
+    return log_tab_addr(tab);
+}
+__device__ __forceinline__ void block_finish(const ClusterOpArgs& a, int i, double acc0, double acc1, double (&red)[2][4]) {
+    acc0 = wave_sum(acc0);
+    acc1 = wave_sum(acc1);
+    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wid] = acc0; red[1][wid] = acc1; }
+    __syncthreads();
+    if (threadIdx.x == 0) store_pair(a, i, red[0], red[1]);
+}
+
+// Wave-specialised forms.  The first builder wave copies the log table; an object wave's preamble loads the object, its
+// pattern bits, its groups in the components 1.. (kNoGroup beyond C) and the state bytes of its first four features
+// (w * 64 + lane); its finish reduces the four accumulators kept apart by the block form's wave tree, in that form's order.
+__device__ __forceinline__ void ws_copy_log_table(f64x2_t* tab, const f64x2_t* __restrict__ logtab, int lane) {
+    tab[lane] = logtab[lane]; tab[lane + kWave] = logtab[lane + kWave];      // (kLogTabEntries = 128)
+}
+__device__ __forceinline__ void ws_object_preamble(const ClusterOpArgs& a, int i, int lane, int& n, uint32_t& bits, uint16_t (&gg)[kWsC],
+                                                   uint8_t (&x)[4]) {
+    n = a.objects[i];
+    bits = a.pattern_bits[a.pid[n]];
+#pragma unroll
+    for (int c = 0; c < kWsC; ++c) gg[c] = (c >= 1 && c < a.C) ? a.gid[(int64_t)c * a.Np + n] : kNoGroup;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int f = w * kWave + lane;
+        x[w] = f < a.F ? a.state[(int64_t)n * a.Fp + f] : kNA;
+    }
+}
+__device__ __forceinline__ void ws_finish(const ClusterOpArgs& a, int i, int lane, const double (&a0)[4], const double (&a1)[4]) {
+    double r0[4], r1[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { r0[w] = wave_sum(a0[w]); r1[w] = wave_sum(a1[w]); }
+    if (lane == 0) store_pair(a, i, r0, r1);
+}
+
 // One BLOCK per available object, thread <-> feature: the with/without weight row of the object's pattern is
 // computed in place (no table kernel in front), a lane's loads (state byte, weights, table entries of every
 // component) are all in flight together and there is one dependent-load chain per object instead of one per
 // 64 features; the two fp64 logs per observation are table-driven (tab_log_pos; the sums of logs carry far more
 // accuracy than the reference's linear-space products).  Fixed-order block reduction: deterministic.
-static __global__ __launch_bounds__(kBlock) void k_cluster_marginals(
-    const uint8_t* __restrict__ state, const uint16_t* __restrict__ gid, const uint8_t* __restrict__ pid,
-    const float* __restrict__ probs, const float* __restrict__ table0, const float* __restrict__ weights,
-    const uint32_t* __restrict__ pattern_bits, float inv_tp, int use_pow, const int32_t* __restrict__ objects,
-    int n_av, double* __restrict__ out, const f64x2_t* __restrict__ logtab, int Np, int F, int S, int C, int Fp,
-    DoneSig done = DoneSig{}) {
+static __global__ __launch_bounds__(kBlock) void k_cluster_marginals(ClusterOpArgs a, const float* __restrict__ probs,
+                                                                     const float* __restrict__ table0, DoneSig done = DoneSig{}) {
     __shared__ f64x2_t tab[kLogTabEntries];
-    __shared__ double red[8];
-    if (threadIdx.x < kLogTabEntries) tab[threadIdx.x] = logtab[threadIdx.x];
-    __syncthreads();
-    const uint32_t tab_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) f64x2_t*)tab;
+    __shared__ double red[2][4];
+    const uint32_t tab_addr = block_log_table(tab, a.logtab);
+    const int F = a.F, S = a.S, C = a.C;
     const int i = blockIdx.x;
-    const int n = objects[i];
-    const bool inside = gid[n] != kNoGroup;                                  // component 0 = clusters
-    const uint32_t bits = pattern_bits[pid[n]];
+    const int n = a.objects[i];
+    const bool inside = a.gid[n] != kNoGroup;                                // component 0 = clusters
+    const uint32_t bits = a.pattern_bits[a.pid[n]];
     double acc0 = 0.0, acc1 = 0.0;
     for (int f = threadIdx.x; f < F; f += kBlock) {
-        const uint8_t x = state[(int64_t)n * Fp + f];
+        const uint8_t x = a.state[(int64_t)n * a.Fp + f];
         float wc[kMaxComponents], wf[kMaxComponents], lhc[kMaxComponents];
-        weight_tables_z_row_reg<kMaxComponents>(weights + (int64_t)f * C, bits, C, inv_tp, use_pow, wc, wf);   // this object's pattern
+        weight_tables_z_row_reg<kMaxComponents>(a.weights + (int64_t)f * C, bits, C, a.inv_tp, a.use_pow, wc, wf);   // this object's pattern
 #pragma unroll
         for (int c = 0; c < kMaxComponents; ++c) {                           // (every entry asked for before any is used)
             lhc[c] = 1.0f;
             if (c < C && x != kNA) {
                 if (c == 0) lhc[c] = table0[(int64_t)f * S + x];
                 else {
-                    const uint16_t gg = gid[(int64_t)c * Np + n];
+                    const uint16_t gg = a.gid[(int64_t)c * a.Np + n];
                     lhc[c] = gg == kNoGroup ? 0.0f : probs[((int64_t)gg * F + f) * S + x];
                 }
             }
         }
-        double v0 = 0.0, v1 = 0.0;
-#pragma unroll
-        for (int c = 0; c < kMaxComponents; ++c) {
-            if (c < C) {
-                const double lh = (double)lhc[c], a = (double)wc[c], b = (double)wf[c];
-                v1 = v1 + lh * (inside ? a : b);     // z = 1: the object is (or becomes) a cluster member
-                v0 = v0 + lh * (inside ? b : a);
-            }
-        }
-        acc0 += tab_log_pos(v0, tab_addr);
-        acc1 += tab_log_pos(v1, tab_addr);
+        marginals_term<kMaxComponents>(lhc, wc, wf, C, inside, tab_addr, acc0, acc1);
     }
-    acc0 = wave_sum(acc0);
-    acc1 = wave_sum(acc1);
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
-    if (lane == 0) { red[wid] = acc0; red[4 + wid] = acc1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[i] = (red[0] + red[1]) + (red[2] + red[3]);
-        out[(int64_t)n_av + i] = (red[4] + red[5]) + (red[6] + red[7]);
-    }
+    block_finish(a, i, acc0, acc1, red);
     signal_done(done);
 }
 
 // The same marginals with the candidate table built by the block's builder waves (InlineTables above;
 // sbe_cluster_posterior_marginals).  An object wave holds, per lane, the four features the four waves of the block form
 // above would have given that lane (w * 64 + lane, + 256 k beyond), keeps the block form's four accumulators and reduces
-// them by the same wave tree in the same order: the result is that form's bit for bit.  C <= kWsC.
-static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
-    const uint8_t* __restrict__ state, const uint16_t* __restrict__ gid, const uint8_t* __restrict__ pid,
-    const float* __restrict__ probs, const float* __restrict__ weights, const uint32_t* __restrict__ pattern_bits, float inv_tp,
-    int use_pow, const int32_t* __restrict__ objects, int n_av, double* __restrict__ out, const f64x2_t* __restrict__ logtab,
-    int Np, int F, int S, int C, int Fp, DoneSig done, InlineTables tin) {
+// them by the same wave tree in the same order -- marginals_term and ws_finish are that form's own: its bits.  C <= kWsC.
+static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(ClusterOpArgs a, const float* __restrict__ probs, DoneSig done,
+                                                                          InlineTables tin) {
     __shared__ f64x2_t tab[kLogTabEntries];
     extern __shared__ float cand[];                                          // the candidate table [F][S]
+    const int F = a.F, S = a.S, C = a.C;
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
     const int i = blockIdx.x * kWsObjWaves + wid;
-    const bool object_wave = wid < kWsObjWaves, active = object_wave && i < n_av;
+    const bool object_wave = wid < kWsObjWaves, active = object_wave && i < a.n;
     uint8_t x[4];
     float lhc[4][kWsC], wc[4][kWsC], wf[4][kWsC];
     int n = 0;
@@ -186,8 +258,8 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
     uint32_t bits = 0;
     uint16_t gg[kWsC];
     // one (object, feature): the other components' entries and the weight rows, into registers
-    auto fetch = [&](int f, uint8_t xx, float (&l)[kWsC], float (&a)[kWsC], float (&b)[kWsC]) {
-        weight_tables_z_row_reg<kWsC>(weights + (int64_t)f * C, bits, C, inv_tp, use_pow, a, b);   // this object's pattern
+    auto fetch = [&](int f, uint8_t xx, float (&l)[kWsC], float (&wa)[kWsC], float (&wb)[kWsC]) {
+        weight_tables_z_row_reg<kWsC>(a.weights + (int64_t)f * C, bits, C, a.inv_tp, a.use_pow, wa, wb);   // this object's pattern
 #pragma unroll
         for (int c = 0; c < kWsC; ++c) {
             l[c] = 1.0f;
@@ -195,19 +267,11 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
         }
     };
     if (!object_wave) {
-        if (wid == kWsObjWaves) { tab[lane] = logtab[lane]; tab[lane + kWave] = logtab[lane + kWave]; }     // (kLogTabEntries = 128)
+        if (wid == kWsObjWaves) ws_copy_log_table(tab, a.logtab, lane);
         ws_build_rows(tin, cand, F, S);
     } else if (active) {
-        n = objects[i];
-        inside = gid[n] != kNoGroup;                                         // component 0 = clusters
-        bits = pattern_bits[pid[n]];
-#pragma unroll
-        for (int c = 0; c < kWsC; ++c) gg[c] = (c >= 1 && c < C) ? gid[(int64_t)c * Np + n] : kNoGroup;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int f = w * kWave + lane;
-            x[w] = f < F ? state[(int64_t)n * Fp + f] : kNA;
-        }
+        ws_object_preamble(a, i, lane, n, bits, gg, x);
+        inside = a.gid[n] != kNoGroup;                                       // component 0 = clusters
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const int f = w * kWave + lane;
@@ -216,27 +280,14 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
     }
     __syncthreads();
     if (active) {
-        const uint32_t tab_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) f64x2_t*)tab;
-        auto term = [&](const float (&l)[kWsC], const float (&a)[kWsC], const float (&b)[kWsC], double& acc0, double& acc1) {
-            double v0 = 0.0, v1 = 0.0;
-#pragma unroll
-            for (int c = 0; c < kWsC; ++c) {
-                if (c < C) {
-                    const double lh = (double)l[c], wa = (double)a[c], wb = (double)b[c];
-                    v1 = v1 + lh * (inside ? wa : wb);   // z = 1: the object is (or becomes) a cluster member
-                    v0 = v0 + lh * (inside ? wb : wa);
-                }
-            }
-            acc0 += tab_log_pos(v0, tab_addr);
-            acc1 += tab_log_pos(v1, tab_addr);
-        };
+        const uint32_t tab_addr = log_tab_addr(tab);
         double a0[4] = {0.0, 0.0, 0.0, 0.0}, a1[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const int f = w * kWave + lane;
             if (f < F) {
                 lhc[w][0] = x[w] != kNA ? cand[(int64_t)f * S + x[w]] : 1.0f;
-                term(lhc[w], wc[w], wf[w], a0[w], a1[w]);
+                marginals_term<kWsC>(lhc[w], wc[w], wf[w], C, inside, tab_addr, a0[w], a1[w]);
             }
         }
         for (int fb = kBlock; fb < F; fb += kBlock) {                        // (F > 256: the block form's later passes, in order)
@@ -244,21 +295,15 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
             for (int w = 0; w < 4; ++w) {
                 const int f = fb + w * kWave + lane;
                 if (f < F) {
-                    const uint8_t xx = state[(int64_t)n * Fp + f];
-                    float l[kWsC], a[kWsC], b[kWsC];
-                    fetch(f, xx, l, a, b);
+                    const uint8_t xx = a.state[(int64_t)n * a.Fp + f];
+                    float l[kWsC], wa[kWsC], wb[kWsC];
+                    fetch(f, xx, l, wa, wb);
                     l[0] = xx != kNA ? cand[(int64_t)f * S + xx] : 1.0f;
-                    term(l, a, b, a0[w], a1[w]);
+                    marginals_term<kWsC>(l, wa, wb, C, inside, tab_addr, a0[w], a1[w]);
                 }
             }
         }
-        double r0[4], r1[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { r0[w] = wave_sum(a0[w]); r1[w] = wave_sum(a1[w]); }
-        if (lane == 0) {
-            out[i] = (r0[0] + r0[1]) + (r0[2] + r0[3]);
-            out[(int64_t)n_av + i] = (r1[0] + r1[1]) + (r1[2] + r1[3]);
-        }
+        ws_finish(a, i, lane, a0, a1);
     }
     signal_done(done);
 }
@@ -277,109 +322,76 @@ static __global__ __launch_bounds__(kWsBlock) void k_cluster_marginals_ws(
 // `p_target` the two clusters' tempered tables (conditional_effect_mean, conditionals.py:105-122).
 // One block per member, thread <-> feature, fixed-order reduction (as k_cluster_marginals).
 // ------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(kBlock) void k_jump_lh(
-    const uint8_t* __restrict__ state, const uint16_t* __restrict__ gid, const uint8_t* __restrict__ pid,
-    const float* __restrict__ pconf /* [Gtot - G0][F][S] */, const float* __restrict__ p_source,
-    const float* __restrict__ p_target, const float* __restrict__ weights, const uint32_t* __restrict__ pattern_bits,
-    float inv_tp, int use_pow, const int32_t* __restrict__ objects, int n_members, double* __restrict__ out,
-    const f64x2_t* __restrict__ logtab, int Np, int F, int S, int C, int Fp, int G0,
-    DoneSig done = DoneSig{}) {
+static __global__ __launch_bounds__(kBlock) void k_jump_lh(ClusterOpArgs a, const float* __restrict__ pconf /* [Gtot - G0][F][S] */,
+                                                           const float* __restrict__ p_source, const float* __restrict__ p_target, int G0,
+                                                           DoneSig done = DoneSig{}) {
     __shared__ f64x2_t tab[kLogTabEntries];
-    __shared__ double red[8];
-    if (threadIdx.x < kLogTabEntries) tab[threadIdx.x] = logtab[threadIdx.x];
-    __syncthreads();
-    const uint32_t tab_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) f64x2_t*)tab;
+    __shared__ double red[2][4];
+    const uint32_t tab_addr = block_log_table(tab, a.logtab);
+    const int F = a.F, S = a.S, C = a.C;
     const int i = blockIdx.x;
-    const int n = objects[i];
-    const uint32_t bits = pattern_bits[pid[n]];
+    const int n = a.objects[i];
+    const uint32_t bits = a.pattern_bits[a.pid[n]];
     double acc0 = 0.0, acc1 = 0.0;
     for (int f = threadIdx.x; f < F; f += kBlock) {
-        const uint8_t x = state[(int64_t)n * Fp + f];
+        const uint8_t x = a.state[(int64_t)n * a.Fp + f];
         if (x == kNA) continue;                                       // np.prod(..., where=~NAs): factor 1
         float wc[kMaxComponents], wf[kMaxComponents], pcf[kMaxComponents];
         uint16_t gg[kMaxComponents];
-        weight_tables_z_row_reg<kMaxComponents>(weights + (int64_t)f * C, bits, C, inv_tp, use_pow, wc, wf);   // wc = weights_heated row
+        weight_tables_z_row_reg<kMaxComponents>(a.weights + (int64_t)f * C, bits, C, a.inv_tp, a.use_pow, wc, wf);   // wc = weights_heated row
 #pragma unroll
-        for (int c = 1; c < kMaxComponents; ++c) gg[c] = c < C ? gid[(int64_t)c * Np + n] : kNoGroup;
-#pragma unroll
-        for (int c = 1; c < kMaxComponents; ++c)                              // (every entry asked for before any is used)
-            pcf[c] = gg[c] != kNoGroup ? pconf[((int64_t)(gg[c] - G0) * F + f) * S + x] : 0.0f;
+        for (int c = 1; c < kMaxComponents; ++c) gg[c] = c < C ? a.gid[(int64_t)c * a.Np + n] : kNoGroup;
+        // (every entry asked for before any is used; the two cluster entries first: behind the confounder entries the
+        //  compiler sinks their loads below the wait for those)
         const float e_src = p_source[(int64_t)f * S + x], e_tgt = p_target[(int64_t)f * S + x];
-        float pc = 0.0f;
 #pragma unroll
         for (int c = 1; c < kMaxComponents; ++c)
-            if (gg[c] != kNoGroup) pc = pc + wc[c] * pcf[c];
-        const float ps = pc + wc[0] * e_src;
-        const float pt = pc + wc[0] * e_tgt;
-        acc0 += tab_log_pos((double)ps, tab_addr);
-        acc1 += tab_log_pos((double)pt, tab_addr);
+            pcf[c] = gg[c] != kNoGroup ? pconf[((int64_t)(gg[c] - G0) * F + f) * S + x] : 0.0f;
+        jump_term<kMaxComponents>(wc, pcf, gg, e_src, e_tgt, tab_addr, acc0, acc1);
     }
-    acc0 = wave_sum(acc0);
-    acc1 = wave_sum(acc1);
-    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
-    if (lane == 0) { red[wid] = acc0; red[4 + wid] = acc1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[i] = (red[0] + red[1]) + (red[2] + red[3]);
-        out[(int64_t)n_members + i] = (red[4] + red[5]) + (red[6] + red[7]);
-    }
+    block_finish(a, i, acc0, acc1, red);
     signal_done(done);
 }
 
 // The same scores with the tempered tables of the two clusters and of every confounder group built by the block's builder
 // waves from the slot's resident counts (InlineTables: rows 0..F-1 source, F..2F-1 target, then the confounder groups in
-// order; sbe_jump_lh_resident).  Object waves as in k_cluster_marginals_ws: the block form's bits.  C <= kWsC.
-static __global__ __launch_bounds__(kWsBlock) void k_jump_lh_ws(
-    const uint8_t* __restrict__ state, const uint16_t* __restrict__ gid, const uint8_t* __restrict__ pid,
-    const float* __restrict__ weights, const uint32_t* __restrict__ pattern_bits, float inv_tp, int use_pow,
-    const int32_t* __restrict__ objects, int n_members, double* __restrict__ out, const f64x2_t* __restrict__ logtab, int Np, int F,
-    int S, int C, int Fp, int G0, DoneSig done, InlineTables tin) {
+// order; sbe_jump_lh_resident).  Object waves as in k_cluster_marginals_ws, jump_term the block form's own: its bits.  C <= kWsC.
+static __global__ __launch_bounds__(kWsBlock) void k_jump_lh_ws(ClusterOpArgs a, int G0, DoneSig done, InlineTables tin) {
     __shared__ f64x2_t tab[kLogTabEntries];
     extern __shared__ float built[];                                         // source | target | confounder tables
+    const int F = a.F, S = a.S, C = a.C;
     const int64_t fs = (int64_t)F * S;
     const float* ps = built;
     const float* pt = built + fs;
     const float* pc = built + 2 * fs;
     const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x >> 6;
     const int i = blockIdx.x * kWsObjWaves + wid;
-    const bool object_wave = wid < kWsObjWaves, active = object_wave && i < n_members;
+    const bool object_wave = wid < kWsObjWaves, active = object_wave && i < a.n;
     uint8_t x[4];
     float wc[4][kWsC];
     uint16_t gg[kWsC];
     int n = 0;
     uint32_t bits = 0;
     if (!object_wave) {
-        if (wid == kWsObjWaves) { tab[lane] = logtab[lane]; tab[lane + kWave] = logtab[lane + kWave]; }     // (kLogTabEntries = 128)
+        if (wid == kWsObjWaves) ws_copy_log_table(tab, a.logtab, lane);
         ws_build_rows(tin, built, F, S);
     } else if (active) {
-        n = objects[i];
-        bits = pattern_bits[pid[n]];
-#pragma unroll
-        for (int c = 0; c < kWsC; ++c) gg[c] = (c >= 1 && c < C) ? gid[(int64_t)c * Np + n] : kNoGroup;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int f = w * kWave + lane;
-            x[w] = f < F ? state[(int64_t)n * Fp + f] : kNA;
-        }
+        ws_object_preamble(a, i, lane, n, bits, gg, x);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const int f = w * kWave + lane;
             float unused[kWsC];
-            if (f < F && x[w] != kNA) weight_tables_z_row_reg<kWsC>(weights + (int64_t)f * C, bits, C, inv_tp, use_pow, wc[w], unused);
+            if (f < F && x[w] != kNA) weight_tables_z_row_reg<kWsC>(a.weights + (int64_t)f * C, bits, C, a.inv_tp, a.use_pow, wc[w], unused);
         }
     }
     __syncthreads();
     if (active) {
-        const uint32_t tab_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) f64x2_t*)tab;
-        auto term = [&](uint8_t xx, int f, const float (&a)[kWsC], double& acc0, double& acc1) {
-            float p = 0.0f;
+        const uint32_t tab_addr = log_tab_addr(tab);
+        auto term = [&](uint8_t xx, int f, const float (&wa)[kWsC], double& acc0, double& acc1) {    // (the entries: out of LDS)
+            float pcf[kWsC];
 #pragma unroll
-            for (int c = 1; c < kWsC; ++c)
-                if (c < C && gg[c] != kNoGroup) p = p + a[c] * pc[((int64_t)(gg[c] - G0) * F + f) * S + xx];
-            const float s_ = p + a[0] * ps[(int64_t)f * S + xx];
-            const float t_ = p + a[0] * pt[(int64_t)f * S + xx];
-            acc0 += tab_log_pos((double)s_, tab_addr);
-            acc1 += tab_log_pos((double)t_, tab_addr);
+            for (int c = 1; c < kWsC; ++c) pcf[c] = gg[c] != kNoGroup ? pc[((int64_t)(gg[c] - G0) * F + f) * S + xx] : 0.0f;
+            jump_term<kWsC>(wa, pcf, gg, ps[(int64_t)f * S + xx], pt[(int64_t)f * S + xx], tab_addr, acc0, acc1);
         };
         double a0[4] = {0.0, 0.0, 0.0, 0.0}, a1[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -392,22 +404,16 @@ static __global__ __launch_bounds__(kWsBlock) void k_jump_lh_ws(
             for (int w = 0; w < 4; ++w) {
                 const int f = fb + w * kWave + lane;
                 if (f < F) {
-                    const uint8_t xx = state[(int64_t)n * Fp + f];
+                    const uint8_t xx = a.state[(int64_t)n * a.Fp + f];
                     if (xx != kNA) {
-                        float a[kWsC], unused[kWsC];
-                        weight_tables_z_row_reg<kWsC>(weights + (int64_t)f * C, bits, C, inv_tp, use_pow, a, unused);
-                        term(xx, f, a, a0[w], a1[w]);
+                        float wa[kWsC], unused[kWsC];
+                        weight_tables_z_row_reg<kWsC>(a.weights + (int64_t)f * C, bits, C, a.inv_tp, a.use_pow, wa, unused);
+                        term(xx, f, wa, a0[w], a1[w]);
                     }
                 }
             }
         }
-        double r0[4], r1[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { r0[w] = wave_sum(a0[w]); r1[w] = wave_sum(a1[w]); }
-        if (lane == 0) {
-            out[i] = (r0[0] + r0[1]) + (r0[2] + r0[3]);
-            out[(int64_t)n_members + i] = (r1[0] + r1[1]) + (r1[2] + r1[3]);
-        }
+        ws_finish(a, i, lane, a0, a1);
     }
     signal_done(done);
 }

@@ -105,6 +105,33 @@ __device__ __forceinline__ void block_log_partial(float sel, bool active, double
     if (threadIdx.x == 0) log_partials[blockIdx.x] = total;
 }
 
+// The draw and the selection, written ONCE for k_sample_source, k_gibbs_propose_tile and gu_gibbs_obs (draw) and for
+// k_source_logprob and the tile kernel's backward pass (selection).  Register form: unrolled over CM, guarded by c < C.
+// draw_source: sample_categorical's arithmetic on the row p[0..C) with the uniform zz -- the drawn component, kNA (0xFF) for
+// an NA observation.  select_by_id: p[id], 1 if no component is `id` -- so an NA observation's selected probability is 1.
+template <int CM>
+__device__ __forceinline__ uint8_t draw_source(const float (&p)[CM], int C, double zz, bool na) {
+    float cdf[CM];
+    float run = p[0];
+    cdf[0] = run;
+#pragma unroll
+    for (int c = 1; c < CM; ++c) { if (c < C) run = run + p[c]; cdf[c] = run; }
+    const float last = run;                                         // (= cdf[C - 1])
+    int k = 0;
+#pragma unroll
+    for (int c = CM - 1; c >= 0; --c)
+        if (c < C && zz < (double)(cdf[c] / last)) k = c;
+    return na ? (uint8_t)kNA : (uint8_t)k;
+}
+
+template <int CM>
+__device__ __forceinline__ float select_by_id(const float (&p)[CM], int C, int id) {
+    float sel = 1.0f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) if (c < C) sel = (c == id) ? p[c] : sel;
+    return sel;
+}
+
 static __global__ __launch_bounds__(kBlock) void k_sample_source(SrcPostArgs a, const double* __restrict__ z, uint64_t seed,
                                                          uint64_t draw, uint8_t* __restrict__ src_dst,
                                                          float* __restrict__ p_sel, int* __restrict__ status,
@@ -117,18 +144,10 @@ static __global__ __launch_bounds__(kBlock) void k_sample_source(SrcPostArgs a, 
         const int n = a.objects[r];
         float p[kMaxComponents];
         if (!source_posterior_row(a, n, f, p)) raise_status(status, ST_BAD_NORMALIZE, 1);
-        float cdf[kMaxComponents];
-        float run = p[0];
-        cdf[0] = run;
-        for (int c = 1; c < a.C; ++c) { run = run + p[c]; cdf[c] = run; }
-        const float last = cdf[a.C - 1];
         const double zz = z ? z[i] : philox_uniform(seed, draw, (uint64_t)i);     // z == nullptr: the engine's own stream
-        int k = 0;
-        for (int c = a.C - 1; c >= 0; --c)
-            if (zz < (double)(cdf[c] / last)) k = c;
-        const bool na = a.state[(int64_t)n * a.Fp + f] == kNA;
-        src_dst[(int64_t)n * a.Fp + f] = na ? (uint8_t)kNA : (uint8_t)k;
-        for (int c = 0; c < a.C; ++c) sel = (!na && c == k) ? p[c] : sel;
+        const uint8_t id = draw_source(p, a.C, zz, a.state[(int64_t)n * a.Fp + f] == kNA);
+        src_dst[(int64_t)n * a.Fp + f] = id;
+        sel = select_by_id(p, a.C, id);
         p_sel[i] = sel;
     }
     block_log_partial(sel, active, log_partials);        // (one convergent call: it contains a barrier)
@@ -146,8 +165,7 @@ static __global__ __launch_bounds__(kBlock) void k_source_logprob(SrcPostArgs a,
         const int n = a.objects[r];
         float p[kMaxComponents];
         if (!source_posterior_row(a, n, f, p)) raise_status(status, ST_BAD_NORMALIZE, 1);
-        const int id = src[(int64_t)n * a.Fp + f];
-        for (int c = 0; c < a.C; ++c) sel = (c == id) ? p[c] : sel;
+        sel = select_by_id(p, a.C, (int)src[(int64_t)n * a.Fp + f]);
         p_sel[i] = sel;
     }
     block_log_partial(sel, active, log_partials);        // (one convergent call: it contains a barrier)
@@ -267,29 +285,11 @@ __device__ __forceinline__ int gu_gibbs_obs(const GuGibbsArgs& a, int64_t i, int
         for (int c = 0; c < CM; ++c) p[side][c] = t[c] / tot;
     }
     if (!ok) raise_status(status, ST_BAD_NORMALIZE, 1);
-    // sample_categorical (preprocessing.py:224-256): float32 cumulative sums, divided by the last, first c with z < cdf[c]
-    float cdf[CM];
-    float run = p[0][0];
-    cdf[0] = run;
-#pragma unroll
-    for (int c = 1; c < CM; ++c) { if (c < C) run = run + p[0][c]; cdf[c] = run; }
-    const float last = run;                                         // (= cdf[C - 1])
-    int k = 0;
-#pragma unroll
-    for (int c = CM - 1; c >= 0; --c)
-        if (c < C && zz < (double)(cdf[c] / last)) k = c;
-    src_new[i] = na ? (uint8_t)kNA : (uint8_t)k;
-    float sn = 1.0f, sb = 1.0f;
-#pragma unroll
-    for (int c = 0; c < CM; ++c) {
-        if (c < C) {
-            sn = (!na && c == k) ? p[0][c] : sn;
-            sb = (c == id_old) ? p[1][c] : sb;
-        }
-    }
-    sel_new[i] = sn;
-    sel_back[i] = sb;
-    return na ? -1 : k;
+    const uint8_t id = draw_source(p[0], C, zz, na);
+    src_new[i] = id;
+    sel_new[i] = select_by_id(p[0], C, id);
+    sel_back[i] = select_by_id(p[1], C, id_old);
+    return na ? -1 : (int)id;
 }
 
 static __global__ __launch_bounds__(kBlock) void k_given_unchanged_gibbs(GuGibbsArgs a, uint8_t* __restrict__ src_new,
@@ -347,6 +347,87 @@ constexpr int kTileBlock = 1024;                 // (= kUnchangedBlock below: th
 struct DeltaFollow { int32_t* counts; const double* conc; float* probs; float* probs_t; int* status; int ft;
                      uint8_t* src; /* or nullptr: the slot's [N][Fp] source ids take the subset's new rows */ };
 
+// What the 16-feature-tile kernels share (k_gibbs_propose_tile, k_given_unchanged_fused, k_counts_delta_tile and
+// follow_tile_rows); a block of `nthr` threads owns the features f0 .. f0 + 15, every thread of it calls.
+constexpr int kTileFT = 16;
+// The call's host-mapped input block into LDS, word for word, in ONE PCIe round trip: every thread's loads are issued before
+// the first LDS store waits for one (two loops over two mapped arrays were two round trips).
+__device__ __forceinline__ void stage_mapped_block(const uint32_t* __restrict__ mapped_in, uint32_t* stage, int in_words, int nthr) {
+    for (int i0 = threadIdx.x; i0 < in_words; i0 += 4 * nthr) {
+        uint32_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = i0 + j * nthr; v[j] = i < in_words ? mapped_in[i] : 0u; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = i0 + j * nthr; if (i < in_words) stage[i] = v[j]; }
+    }
+}
+
+// update_feature_counts (counts.py:55-95), one drawn observation's share of the LDS delta [T][16][S]: one more in the
+// object's NEW group of the drawn component k, one less in its OLD group of the old source component (none: id_old >= C).
+// gid_new / gid_old [C][n_sub]: global group ids of subset row r (-1 none); pos [Gtot]: touched index of a group (-1 none).
+__device__ __forceinline__ void obs_count_delta(int32_t* dhist, const int32_t* pos, const int32_t* gid_new, const int32_t* gid_old,
+                                                int n_sub, int r, int tf, int S, int C, uint8_t x, int k, int id_old) {
+    const int gn = gid_new[k * n_sub + r];
+    if (gn >= 0 && pos[gn] >= 0) atomicAdd(&dhist[(pos[gn] * kTileFT + tf) * S + x], 1);
+    if (id_old < C) {
+        const int go = gid_old[id_old * n_sub + r];
+        if (go >= 0 && pos[go] >= 0) atomicAdd(&dhist[(pos[go] * kTileFT + tf) * S + x], -1);
+    }
+}
+
+// The delta rows [T][16][S] (LDS) -> rows_out [T][F][S], float32.
+__device__ __forceinline__ void write_delta_rows(const int32_t* dhist, int T, int f0, int F, int S, float* __restrict__ rows_out, int nthr) {
+    for (int e = threadIdx.x; e < T * kTileFT * S; e += nthr) {
+        const int t = e / (kTileFT * S), q = e % (kTileFT * S), ff = f0 + q / S;
+        if (ff < F) rows_out[((int64_t)t * F + ff) * S + q % S] = (float)dhist[e];
+    }
+}
+
+// The tile's counts -> probability rows: for each of the T * 16 rows (row = tt * 16 + tf: group g = group_of(tt), feature ff = f0 + tf)
+// count(row, at, s) is state s' count (at = the row's offset (g F + ff) S in the [Gtot][F][S] tables), `store` -- unless
+// null -- takes it at store[at + s], and, if `rows`, emit(row, ff, g, s, v) receives the row's probabilities (probs_row's
+// arithmetic; unif: the [F][S] uniform concentration of a tempered prior, or null).  Eight or sixteen consecutive lanes per
+// row while the states fit them (probs_row_x16), else one thread per row; `count` is pure (the one-thread form asks twice).
+template <class GroupOf, class Count, class Emit>
+__device__ __forceinline__ void tile_probs_rows(int T, int f0, int F, int S, int nthr, GroupOf group_of, Count count, int32_t* store,
+                                                bool rows, const double* conc, const double* unif, double temperature,
+                                                double prior_temperature, int* status, Emit emit) {
+    auto rows_by_lane_groups = [&](auto width) {
+        constexpr int W = decltype(width)::value;
+        for (int row0 = 0; row0 < T * kTileFT; row0 += nthr / W) {
+            const int row = row0 + (int)threadIdx.x / W, j = threadIdx.x & (W - 1);
+            const int tt = row / kTileFT, tf = row % kTileFT, ff = f0 + tf;
+            const bool row_on = row < T * kTileFT && ff < F;
+            const int g = row_on ? group_of(tt) : 0;
+            const int64_t at = row_on ? ((int64_t)g * F + ff) * S : 0;
+            float cj = 0.0f;
+            if (row_on && j < S) {
+                const int32_t v = count(row, at, j);
+                if (store) store[at + j] = v;                         // (this block owns the row)
+                cj = (float)v;
+            }
+            if (rows)
+                probs_row_x16<W>(j, row_on, [&](int) { return cj; }, conc + at, unif ? unif + (row_on ? (int64_t)ff * S : 0) : nullptr, S,
+                                 temperature, prior_temperature, status, [&](int s, float v) { emit(row, ff, g, s, v); });
+        }
+    };
+    if (S <= 8) rows_by_lane_groups(std::integral_constant<int, 8>{});
+    else if (S <= 16) rows_by_lane_groups(std::integral_constant<int, 16>{});
+    else {
+        for (int t = threadIdx.x; t < T * kTileFT; t += nthr) {
+            const int tt = t / kTileFT, tf = t % kTileFT, ff = f0 + tf;
+            if (ff >= F) continue;
+            const int g = group_of(tt);
+            const int64_t at = ((int64_t)g * F + ff) * S;
+            if (store) for (int s = 0; s < S; ++s) store[at + s] = count(t, at, s);
+            if (rows)
+                probs_row([&](int s) { return (float)(store ? store[at + s] : count(t, at, s)); }, conc + at,
+                          unif ? unif + (int64_t)ff * S : nullptr, S, temperature, prior_temperature, status,
+                          [&](int s, float v) { emit(t, ff, g, s, v); });
+        }
+    }
+}
+
 struct GibbsTileArgs {
     const uint8_t* state; const uint16_t* gid; const uint8_t* pid; const uint8_t* src; const float* probs; const float* wpat;
     const int32_t* counts; const double* conc;
@@ -371,13 +452,7 @@ static __global__ __launch_bounds__(kTileBlock) void k_gibbs_propose_tile(GibbsT
     const int32_t* gidl = reinterpret_cast<const int32_t*>(stage + a.gid_word);
     const int32_t* touched = reinterpret_cast<const int32_t*>(stage + a.touched_word);
     const int f0 = blockIdx.x * FTU;
-    for (int i0 = threadIdx.x; i0 < a.in_words; i0 += 4 * kTileBlock) {       // one PCIe round trip (k_given_unchanged_fused)
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int i = i0 + j * kTileBlock; v[j] = i < a.in_words ? a.mapped_in[i] : 0u; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int i = i0 + j * kTileBlock; if (i < a.in_words) stage[i] = v[j]; }
-    }
+    stage_mapped_block(a.mapped_in, stage, a.in_words, kTileBlock);
     // the uniform of the observation this thread draws first: asked for now (host-mapped or device memory)
     double z_first = 0.0;
     {
@@ -402,78 +477,21 @@ static __global__ __launch_bounds__(kTileBlock) void k_gibbs_propose_tile(GibbsT
                                            [&](int c) { const int g = gidl[c * n_sub + r]; return g < 0 ? (uint32_t)kNoGroup : (uint32_t)g; },
                                            [&](int, uint32_t g) { return a.probs[((int64_t)g * a.F + ff) * S + x]; }, p);
         if (!ok) raise_status(a.status, ST_BAD_NORMALIZE, 1);
-        // sample_categorical (preprocessing.py:224-256), as k_sample_source draws: float32 cumulative sums / the last, first c with z < cdf[c]
-        float cdf[kMaxComponents];
-        float run = p[0];
-        cdf[0] = run;
-#pragma unroll
-        for (int c = 1; c < kMaxComponents; ++c) { if (c < C) run = run + p[c]; cdf[c] = run; }
-        const float last = run;
-        const double zz = t == (int)threadIdx.x ? z_first : a.z[i];
-        int k = 0;
-#pragma unroll
-        for (int c = kMaxComponents - 1; c >= 0; --c)
-            if (c < C && zz < (double)(cdf[c] / last)) k = c;
-        const bool na = x == kNA;
-        float sel = 1.0f;
-#pragma unroll
-        for (int c = 0; c < kMaxComponents; ++c) if (c < C) sel = (!na && c == k) ? p[c] : sel;
-        a.ids_out[i] = na ? (uint8_t)kNA : (uint8_t)k;
-        a.sel_out[i] = sel;
-        knew[t] = na ? (uint8_t)kNA : (uint8_t)k;
-        if (!na) {
-            const int g_new = gidl[k * n_sub + r];
-            if (g_new >= 0 && pos[g_new] >= 0) atomicAdd(&dhist[(pos[g_new] * FTU + tf) * S + x], 1);
-            const int so = a.src[(int64_t)n * a.Fp + ff];
-            if (so < C) {
-                const int g_old = gidl[so * n_sub + r];
-                if (g_old >= 0 && pos[g_old] >= 0) atomicAdd(&dhist[(pos[g_old] * FTU + tf) * S + x], -1);
-            }
-        }
+        const uint8_t id = draw_source(p, C, t == (int)threadIdx.x ? z_first : a.z[i], x == kNA);
+        a.ids_out[i] = id;
+        a.sel_out[i] = select_by_id(p, C, id);
+        knew[t] = id;
+        if (id != kNA) obs_count_delta(dhist, pos, gidl, gidl, n_sub, r, tf, S, C, x, id, a.src[(int64_t)n * a.Fp + ff]);
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < T * FTU * S; e += kTileBlock) {
-        const int tt = e / (FTU * S), q = e % (FTU * S), ff = f0 + q / S;
-        if (ff < a.F) a.rows_out[((int64_t)tt * a.F + ff) * S + q % S] = (float)dhist[e];
-    }
+    write_delta_rows(dhist, T, f0, a.F, S, a.rows_out, kTileBlock);
     __syncthreads();
-    // 3: the touched groups' tables from counts + delta, in place (update_probs' arithmetic: untempered)
-    auto rows_by_lane_groups = [&](auto width) {
-        constexpr int W = decltype(width)::value;
-        for (int row0 = 0; row0 < T * FTU; row0 += kTileBlock / W) {
-            const int row = row0 + (int)threadIdx.x / W, j = threadIdx.x & (W - 1);
-            const int tt = row / FTU, tf = row % FTU, ff = f0 + tf;
-            const bool row_on = row < T * FTU && ff < a.F;
-            const int64_t at = row_on ? ((int64_t)touched[tt] * a.F + ff) * S : 0;
-            int32_t* h = dhist + (row_on ? (tt * FTU + tf) * S : 0);
-            float cj = 0.0f;
-            if (row_on && j < S) {
-                const int32_t v = a.counts[at + j] + h[j];
-                if (a.follow.counts) a.follow.counts[at + j] = v;         // (the following slot: this block owns the row)
-                cj = (float)v;
-            }
-            probs_row_x16<W>(j, row_on, [&](int) { return cj; }, a.conc + at, nullptr, S, 0.0, 0.0, a.status,
-                             [&](int s, float v) { h[s] = __float_as_int(v); });
-        }
-    };
-    if (S <= 8) rows_by_lane_groups(std::integral_constant<int, 8>{});
-    else if (S <= 16) rows_by_lane_groups(std::integral_constant<int, 16>{});
-    else {
-        for (int t = threadIdx.x; t < T * FTU; t += kTileBlock) {
-            const int tt = t / FTU, tf = t % FTU, ff = f0 + tf;
-            if (ff >= a.F) continue;
-            const int64_t at = ((int64_t)touched[tt] * a.F + ff) * S;
-            int32_t* h = dhist + (tt * FTU + tf) * S;
-            if (a.follow.counts) {
-                for (int s = 0; s < S; ++s) a.follow.counts[at + s] = a.counts[at + s] + h[s];
-                probs_row([&](int s) { return (float)a.follow.counts[at + s]; }, a.conc + at, nullptr, S, 0.0, 0.0, a.status,
-                          [&](int s, float v) { h[s] = __float_as_int(v); });
-                continue;
-            }
-            probs_row([&](int s) { return (float)(a.counts[at + s] + h[s]); }, a.conc + at, nullptr, S, 0.0, 0.0, a.status,
-                      [&](int s, float v) { h[s] = __float_as_int(v); });
-        }
-    }
+    // 3: the touched groups' tables from counts + delta, in place (update_probs' arithmetic: untempered); the following slot's
+    //    counts take the new values here
+    tile_probs_rows(T, f0, a.F, S, kTileBlock, [&](int tt) { return touched[tt]; },
+                    [&](int row, int64_t at, int s) { return a.counts[at + s] + dhist[row * S + s]; }, a.follow.counts, true,
+                    a.conc, nullptr, 0.0, 0.0, a.status,
+                    [&](int row, int, int, int s, float v) { dhist[row * S + s] = __float_as_int(v); });
     __syncthreads();
     // 4: the backward probabilities under the new tables
     const float* tab = reinterpret_cast<const float*>(dhist);
@@ -488,11 +506,7 @@ static __global__ __launch_bounds__(kTileBlock) void k_gibbs_propose_tile(GibbsT
                                            [&](int c) { const int g = gidl[c * n_sub + r]; return g < 0 ? (uint32_t)kNoGroup : (uint32_t)g; },
                                            [&](int, uint32_t g) { return tab[(pos[g] * FTU + tf) * S + x]; }, p);
         if (!ok) raise_status(a.status, ST_BAD_NORMALIZE, 1);
-        const int id = a.src[(int64_t)n * a.Fp + ff];
-        float sel = 1.0f;
-#pragma unroll
-        for (int c = 0; c < kMaxComponents; ++c) if (c < C) sel = (c == id) ? p[c] : sel;
-        a.back_out[(int64_t)r * a.F + ff] = sel;
+        a.back_out[(int64_t)r * a.F + ff] = select_by_id(p, C, (int)a.src[(int64_t)n * a.Fp + ff]);
     }
     signal_done(done);
     if (a.follow.counts) {                               // behind the flag: the touched groups' new tables (LDS) and the drawn ids
@@ -822,6 +836,7 @@ static __global__ void k_tile_probs(const float* __restrict__ probs, float* __re
 // axis gets the lanes, and every step of a lane's walk is a chain of dependent loads); LDS histogram [16][S].
 // ------------------------------------------------------------------------------------------
 constexpr int kDeltaFT = 16;
+static_assert(kDeltaFT == kTileFT, "k_counts_delta_tile writes its rows with write_delta_rows and follows with follow_tile_rows");
 static __global__ __launch_bounds__(kBlock) void k_counts_delta(
     const uint8_t* __restrict__ state, const int32_t* __restrict__ objects, int n,
     const int32_t* __restrict__ gid_old /* [C][n] */, const int32_t* __restrict__ gid_new,
@@ -886,51 +901,16 @@ constexpr int kDeltaTileMaxN = 256;
 // The following slot's rows of one 16-feature tile (the calling block owns these features of every touched group): counts +=
 // the LDS histograms `hist` [T][16][S], and -- follow.probs -- the probability rows of those groups rebuilt (update_probs'
 // arithmetic in k_set_count_rows_probs_x's row form).  `tgl` [T]: the touched groups (LDS).  Every thread of the block calls.
-__device__ __forceinline__ void follow_tile_rows(const DeltaFollow& follow, const int32_t* hist, const int32_t* tgl, int n_touched, int f0,
+// (`follow` by value: taken by reference, k_given_unchanged_fused<true>'s frame grows by a 16-byte spill slot.)
+__device__ __forceinline__ void follow_tile_rows(const DeltaFollow follow, const int32_t* hist, const int32_t* tgl, int n_touched, int f0,
                                                  int F, int S, int Gtot) {
-    constexpr int FTU = 16;
     if (!follow.counts) return;
-    const int nthr = blockDim.x;
-    auto rows_by_lane_groups = [&](auto width) {
-        constexpr int W = decltype(width)::value;
-        for (int row0 = 0; row0 < n_touched * FTU; row0 += nthr / W) {
-            const int row = row0 + (int)threadIdx.x / W, j = threadIdx.x & (W - 1);
-            const int tt = row / FTU, tf = row % FTU, ff = f0 + tf;
-            const bool row_on = row < n_touched * FTU && ff < F;
-            const int g = row_on ? tgl[tt] : 0;
-            const int64_t at = row_on ? ((int64_t)g * F + ff) * S : 0;
-            float cj = 0.0f;
-            if (row_on && j < S) {
-                const int32_t v = follow.counts[at + j] + hist[(tt * FTU + tf) * S + j];
-                follow.counts[at + j] = v;
-                cj = (float)v;
-            }
-            if (follow.probs) {
-                float* out_row = follow.probs + at;
-                float* out_t = follow.probs_t + (((int64_t)(ff / follow.ft) * (Gtot + 1) + g) * S) * follow.ft + ff % follow.ft;   // (k_probs' tile layout)
-                probs_row_x16<W>(j, row_on, [&](int) { return cj; }, follow.conc + at, nullptr, S, 0.0, 0.0, follow.status,
-                                 [&](int s, float v) { out_row[s] = v; out_t[(int64_t)s * follow.ft] = v; });
-            }
-        }
-    };
-    if (S <= 8) rows_by_lane_groups(std::integral_constant<int, 8>{});
-    else if (S <= 16) rows_by_lane_groups(std::integral_constant<int, 16>{});
-    else {
-        for (int t = threadIdx.x; t < n_touched * FTU; t += nthr) {
-            const int tt = t / FTU, tf = t % FTU, ff = f0 + tf;
-            if (ff >= F) continue;
-            const int g = tgl[tt];
-            const int64_t at = ((int64_t)g * F + ff) * S;
-            const int32_t* h = hist + (tt * FTU + tf) * S;
-            for (int k = 0; k < S; ++k) follow.counts[at + k] += h[k];
-            if (follow.probs) {
-                float* out_row = follow.probs + at;
-                float* out_t = follow.probs_t + (((int64_t)(ff / follow.ft) * (Gtot + 1) + g) * S) * follow.ft + ff % follow.ft;
-                probs_row([&](int k) { return (float)follow.counts[at + k]; }, follow.conc + at, nullptr, S, 0.0, 0.0, follow.status,
-                          [&](int k, float v) { out_row[k] = v; out_t[(int64_t)k * follow.ft] = v; });
-            }
-        }
-    }
+    tile_probs_rows(n_touched, f0, F, S, blockDim.x, [&](int tt) { return tgl[tt]; },
+                    [&](int row, int64_t at, int s) { return follow.counts[at + s] + hist[row * S + s]; }, follow.counts,
+                    follow.probs != nullptr, follow.conc, nullptr, 0.0, 0.0, follow.status, [&](int, int ff, int g, int s, float v) {
+                        follow.probs[((int64_t)g * F + ff) * S + s] = v;
+                        follow.probs_t[(((int64_t)(ff / follow.ft) * (Gtot + 1) + g) * S + s) * follow.ft + ff % follow.ft] = v;   // (k_probs' tile layout)
+                    });
 }
 
 static __global__ __launch_bounds__(kBlock) void k_counts_delta_tile(
@@ -1021,10 +1001,7 @@ static __global__ __launch_bounds__(kBlock) void k_counts_delta_tile(
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < n_touched * FTU * S; e += kBlock) {
-        const int t = e / (FTU * S), r = e % (FTU * S), ff = f0 + r / S;
-        if (ff < F) out[((int64_t)t * F + ff) * S + r % S] = (float)hist[e];
-    }
+    write_delta_rows(hist, n_touched, f0, F, S, out, kBlock);
     // the caller waits for the difference only: the flag goes out before the following slot is brought up to date (the
     // next operation of the stream is ordered behind this kernel's end anyway; nothing below reads the mapped block)
     signal_done(done);
@@ -1305,15 +1282,7 @@ __global__ __launch_bounds__(kUnchangedBlock) void k_given_unchanged_fused(GuFus
     const int32_t* sub = reinterpret_cast<const int32_t*>(stage + a.objects_word);       // [n_sub]
     const int32_t* gidx = reinterpret_cast<const int32_t*>(stage + a.group_idx_word);    // [C][n_sub]
     const int f0 = blockIdx.x * FTU;
-    // the whole input block (object list, table rows, has_components rows) crosses PCIe in ONE round trip: every thread's
-    // loads are issued before the first LDS store waits for one (two loops over two mapped arrays were two round trips)
-    for (int i0 = threadIdx.x; i0 < a.in_words; i0 += 4 * kUnchangedBlock) {
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int i = i0 + j * kUnchangedBlock; v[j] = i < a.in_words ? a.mapped_in[i] : 0u; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int i = i0 + j * kUnchangedBlock; if (i < a.in_words) stage[i] = v[j]; }
-    }
+    stage_mapped_block(a.mapped_in, stage, a.in_words, kUnchangedBlock);   // (object list, table rows, has_components rows)
     // Gibbs form: the uniform and the old source id of the observation this thread serves first (the consumer loop below:
     // t = threadIdx.x) are asked for now -- they sit in host-mapped staging, and their round trip hides behind the rest
     double z_first = 0.0;
@@ -1377,36 +1346,12 @@ __global__ __launch_bounds__(kUnchangedBlock) void k_given_unchanged_fused(GuFus
         }
     }
     __syncthreads();
-    // conditional_effect_mean (conditionals.py:105-122) of the kept counts, in place: sixteen lanes per (row, feature) when
-    // S <= 16 (probs_row_x16), else one thread per row
-    auto rows_by_lane_groups = [&](auto width) {
-        constexpr int W = decltype(width)::value;
-        for (int row0 = 0; row0 < R * FTU; row0 += kUnchangedBlock / W) {
-            const int row = row0 + (int)threadIdx.x / W, j = threadIdx.x & (W - 1);
-            const int r = row / FTU, tf = row % FTU, ff = f0 + tf;
-            const bool row_on = row < R * FTU && ff < a.F;
-            const int gg = r == 0 ? a.i_cluster : a.K + r - 1;       // rows 1.. are the confounder groups in global order
-            const int64_t at = row_on ? ((int64_t)gg * a.F + ff) * S : 0;
-            int32_t* h = hist + (row_on ? (r * FTU + tf) * S : 0);
-            probs_row_x16<W>(j, row_on, [&](int s) { return (float)((r == 0 ? 0 : a.counts[at + s]) + h[s]); }, a.conc + at,
-                             a.unif + (row_on ? (int64_t)ff * S : 0), S, a.temperature, a.prior_temperature, a.status,
-                             [&](int s, float v) { h[s] = __float_as_int(v); });
-        }
-    };
-    if (S <= 8) rows_by_lane_groups(std::integral_constant<int, 8>{});
-    else if (S <= 16) rows_by_lane_groups(std::integral_constant<int, 16>{});
-    else {
-        for (int t = threadIdx.x; t < R * FTU; t += kUnchangedBlock) {
-            const int r = t / FTU, tf = t % FTU, ff = f0 + tf;
-            if (ff >= a.F) continue;
-            const int gg = r == 0 ? a.i_cluster : a.K + r - 1;
-            const int32_t* base = a.counts + ((int64_t)gg * a.F + ff) * S;
-            int32_t* h = hist + (r * FTU + tf) * S;
-            probs_row([&](int s) { return (float)((r == 0 ? 0 : base[s]) + h[s]); }, a.conc + ((int64_t)gg * a.F + ff) * S,
-                      a.unif + (int64_t)ff * S, S, a.temperature, a.prior_temperature, a.status,
-                      [&](int s, float v) { h[s] = __float_as_int(v); });
-        }
-    }
+    // conditional_effect_mean (conditionals.py:105-122) of the kept counts, in place; rows 1.. are the confounder groups in
+    // global order
+    tile_probs_rows(R, f0, a.F, S, kUnchangedBlock, [&](int r) { return r == 0 ? a.i_cluster : a.K + r - 1; },
+                    [&](int row, int64_t at, int s) { return (row < FTU ? 0 : a.counts[at + s]) + hist[row * S + s]; }, nullptr, true,
+                    a.conc, a.unif, a.temperature, a.prior_temperature, a.status,
+                    [&](int row, int, int, int s, float v) { hist[row * S + s] = __float_as_int(v); });
     __syncthreads();
     const float* tab = reinterpret_cast<const float*>(hist);
     GuGibbsArgs g2 = gb;
@@ -1427,18 +1372,9 @@ __global__ __launch_bounds__(kUnchangedBlock) void k_given_unchanged_fused(GuFus
                                        [&](int c, int g) { return tab[((a.table_offsets[c] + g) * FTU + tf) * S + x]; },
                                        src_new, sel_new, sel_back, a.status);
             if (following) knew[r * FTU + tf] = k >= 0 ? (uint8_t)k : (uint8_t)0xFF;
-            if (a.n_touched > 0 && k >= 0) {
-                // update_feature_counts (counts.py:55-95) of the proposal, this observation's share: one more in its NEW group of
-                // the drawn component, one less in its OLD group of the old source component
-                const int32_t* gid_new = reinterpret_cast<const int32_t*>(stage + a.gid_new_word);
-                const int32_t* gid_old = reinterpret_cast<const int32_t*>(stage + a.gid_old_word);
-                const int gn = gid_new[k * n_sub + r];
-                if (gn >= 0 && dpos[gn] >= 0) atomicAdd(&dhist[(dpos[gn] * FTU + tf) * S + x], 1);
-                if (id_old < C) {
-                    const int go = gid_old[id_old * n_sub + r];
-                    if (go >= 0 && dpos[go] >= 0) atomicAdd(&dhist[(dpos[go] * FTU + tf) * S + x], -1);
-                }
-            }
+            if (a.n_touched > 0 && k >= 0)                               // (the proposal's count delta, this observation's share)
+                obs_count_delta(dhist, dpos, reinterpret_cast<const int32_t*>(stage + a.gid_new_word),
+                                reinterpret_cast<const int32_t*>(stage + a.gid_old_word), n_sub, r, tf, S, C, x, k, id_old);
         } else {
             float* o = a.out + i * C;
             for (int c = 0; c < C; ++c) {
@@ -1454,10 +1390,7 @@ __global__ __launch_bounds__(kUnchangedBlock) void k_given_unchanged_fused(GuFus
     if constexpr (kGibbs) {
         if (a.n_touched > 0) {
             __syncthreads();
-            for (int e = threadIdx.x; e < a.n_touched * FTU * S; e += kUnchangedBlock) {
-                const int t = e / (FTU * S), q = e % (FTU * S), ff = f0 + q / S;
-                if (ff < a.F) a.rows_out[((int64_t)t * a.F + ff) * S + q % S] = (float)dhist[e];
-            }
+            write_delta_rows(dhist, a.n_touched, f0, a.F, S, a.rows_out, kUnchangedBlock);
         }
     }
     signal_done(done);
