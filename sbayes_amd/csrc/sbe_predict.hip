@@ -16,84 +16,18 @@
 //                       is computed from the other buffer, one barrier per sample.  The weight normalisation is computed
 //                       per cell from the object's h flags (no table over the 2^C patterns).  Threads along the tile's
 //                       features are adjacent, so a sample's lik row is written in runs of Ft floats.
-// The first offender travels as one uint64 key (sample, kind, position) through an integer atomicMin.  No floating-point
-// atomics: a cell belongs to one thread, which adds the samples in order.
+// The first two kernels, the staging of a slice and the row arithmetic of a cell are sbe_predict_row.hip.h's, shared with
+// sbe_ppc.hip.  The first offender travels as one uint64 key (sample, kind, position) through an integer atomicMin.  No
+// floating-point atomics: a cell belongs to one thread, which adds the samples in order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "sbe_unit.hip.h"
-#include "../../include/sbe_predict.h"
+#include "sbe_predict_row.hip.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kMaxS = SBE_PREDICT_MAX_STATES;
-constexpr int kMaxC = SBE_PREDICT_MAX_COMPONENTS;
-constexpr int kMaxR = SBE_PREDICT_MAX_ROWS;
-constexpr int kMaxTile = SBE_PREDICT_MAX_TILE;
-constexpr uint16_t kNoCluster = 0xFFFF;
-constexpr uint8_t kNA = SBE_PREDICT_NA;
-constexpr unsigned long long kNoError = ~0ull;
-constexpr int kDefaultTile = 16;                     // features per tile, where the slice allows it
-constexpr size_t kSmallSlices = (size_t)40 << 10;    // the default plan keeps the two slices under this: four workgroups per CU
-static_assert(kMaxTile <= kBlock, "a tile of Ft features gives every thread of a row of Ft a feature");
-
-// kinds of offender, in the order the header lists them
-enum : int { kOverlap = 0, kWeightEntry = 1, kWeightSum = 2, kTableEntry = 3, kTableRowEmpty = 4, kTableSum = 5 };
-
-__host__ __device__ inline unsigned long long error_key(int64_t sample, int kind, int64_t at) {
-    return ((unsigned long long)sample << 40) | ((unsigned long long)kind << 36) | (unsigned long long)at;
-}
-
-// ---- preparation: cluster rows -> cluster id per object --------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_predict_ids(const uint8_t* clusters, int64_t n, int64_t N, int K, uint16_t* kid,
-                                                        unsigned long long* err) {
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (q >= n * N) return;
-    const int64_t t = q / N, obj = q - t * N;
-    const uint8_t* rows = clusters + t * K * N + obj;
-    int found = 0;
-    uint16_t id = kNoCluster;
-    for (int k = 0; k < K; ++k)
-        if (rows[(int64_t)k * N]) {
-            if (!found) id = (uint16_t)k;
-            ++found;
-        }
-    kid[q] = id;
-    if (found > 1) atomicMin(err, error_key(t, kOverlap, obj));
-}
-
-// ---- validation: one thread per row (a sample's F weight rows, then its R F table rows) -----------------------------------
-__global__ __launch_bounds__(kBlock) void k_predict_validate(const double* weights, const double* tables, int64_t n, int F, int S, int C, int R,
-                                                             unsigned long long* err) {
-    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t per_sample = (int64_t)F * (1 + R);
-    if (q >= n * per_sample) return;
-    const int64_t t = q / per_sample, j = q - t * per_sample;
-    const bool is_weight = j < F;
-    const int64_t row = is_weight ? j : j - F;               // f, or r F + f
-    const int len = is_weight ? C : S;
-    const double* v = is_weight ? weights + (t * F + row) * C : tables + (t * (int64_t)R * F + row) * S;
-    double sum = 0.0;
-    bool positive = false;
-    for (int i = 0; i < len; ++i) {
-        const double x = v[i];
-        if (!(x >= 0.0) || isinf(x)) {                       // negative, NaN or infinite
-            atomicMin(err, error_key(t, is_weight ? kWeightEntry : kTableEntry, row * len + i));
-            return;
-        }
-        positive |= x > 0.0;
-        sum += x;
-    }
-    if (!is_weight && !positive) {
-        atomicMin(err, error_key(t, kTableRowEmpty, row));
-        return;
-    }
-    if (fabs(sum - 1.0) > SBE_PREDICT_SUM_TOL) atomicMin(err, error_key(t, is_weight ? kWeightSum : kTableSum, row));
-}
 
 // ---- the accumulation -------------------------------------------------------------------------------------------------------
 struct AccArgs {
@@ -114,90 +48,43 @@ struct AccArgs {
     int row_off[kMaxC];            // first table row of a component's groups (row_off[0] = 0: the clusters)
 };
 
-// the tile's slice of sample t into `buf`: [R][Ft][S] of the tables, then [Ft][C] of the weights; the features of the last
-// tile behind F are zero
-__device__ inline void stage_slice(double* buf, const AccArgs& g, int t, int f0, int fw) {
-    const int row_len = g.Ft * g.S, have = fw * g.S, total = g.R * row_len;
-    const double* tab = g.tables + ((int64_t)t * g.R * g.F + f0) * g.S;
-    for (int j = threadIdx.x; j < total; j += kBlock) {
-        const int r = j / row_len, q = j - r * row_len;
-        buf[j] = q < have ? tab[(int64_t)r * g.F * g.S + q] : 0.0;
-    }
-    const double* w = g.weights + ((int64_t)t * g.F + f0) * g.C;
-    for (int j = threadIdx.x; j < g.Ft * g.C; j += kBlock) buf[total + j] = j < fw * g.C ? w[j] : 0.0;
-}
-
 template <int SP, int CP>
 __global__ __launch_bounds__(kBlock) void k_predict_accumulate(const AccArgs g) {
     extern __shared__ double lds[];                            // two slices
-    const int64_t b = g.block0 + blockIdx.x;
-    const int ft = (int)(b % g.f_tiles);
-    const int64_t nt = b / g.f_tiles;
-    const int f0 = ft * g.Ft, fw = min(g.Ft, g.F - f0);
-    const int fl = threadIdx.x % g.Ft, nl = threadIdx.x / g.Ft;
-    const int64_t obj = nt * g.Nt + nl;
-    const int f = f0 + fl;
-    const bool live = nl < g.Nt && obj < g.N && f < g.F;
-    const int slice = g.R * g.Ft * g.S + g.Ft * g.C;
-    const int w_at = g.R * g.Ft * g.S + fl * g.C;
+    const TileCell tc = tile_cell(g);
+    const bool live = tc.live;
+    const int64_t cell = tc.cell;
 
     double pred[SP], resp[CP];
     int row[CP];                                               // the object's table row per component (0: not applicable)
     bool has[CP];
     int x = kNA;
-    const int64_t cell = live ? obj * g.F + f : 0;
 #pragma unroll
     for (int s = 0; s < SP; ++s) pred[s] = live && s < g.S ? g.pred[cell * g.S + s] : 0.0;
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
         resp[c] = live && c < g.C ? g.resp[cell * g.C + c] : 0.0;
-        has[c] = false;
-        row[c] = 0;
-        if (live && c >= 1 && c < g.C) {
-            const int grp = g.groups[(int64_t)(c - 1) * g.N + obj];
-            has[c] = grp != kNA;
-            row[c] = has[c] ? g.row_off[c] + grp : 0;
-        }
+        cell_group(g, tc, c, row[c], has[c]);
     }
     if (live) x = g.codes[cell];
     unsigned long long zeros = 0;
 
-    stage_slice(lds, g, 0, f0, fw);
+    stage_slice(lds, g, 0, tc.f0, tc.fw);
     __syncthreads();
     for (int t = 0; t < g.n; ++t) {
-        const double* cur = lds + (t & 1) * slice;
-        if (t + 1 < g.n) stage_slice(lds + ((t + 1) & 1) * slice, g, t + 1, f0, fw);
+        const double* cur = lds + (t & 1) * tc.slice;
+        if (t + 1 < g.n) stage_slice(lds + ((t + 1) & 1) * tc.slice, g, t + 1, tc.f0, tc.fw);
         if (live) {
-            const uint16_t id = g.kid[(int64_t)t * g.N + obj];
-            has[0] = id != kNoCluster;
-            row[0] = has[0] ? id : 0;
-            double wn[CP], wsum = 0.0;
+            double wn[CP];
             const double* base[CP];
-#pragma unroll
-            for (int c = 0; c < CP; ++c) {
-                wn[c] = c < g.C && has[c] ? cur[w_at + c] : 0.0;
-                if (c < g.C) wsum += wn[c];
-                base[c] = cur + (row[c] * g.Ft + fl) * g.S;
-            }
-#pragma unroll
-            for (int c = 0; c < CP; ++c) wn[c] = wsum > 0.0 ? wn[c] / wsum : 0.0;
+            cell_weights(g, tc, cur, t, row, has, wn, base);
 #pragma unroll
             for (int s = 0; s < SP; ++s)
-                if (s < g.S) {
-                    double m = 0.0;
-#pragma unroll
-                    for (int c = 0; c < CP; ++c)
-                        if (c < g.C) m += wn[c] * base[c][s];
-                    pred[s] += m;
-                }
+                if (s < g.S) pred[s] += cell_state(g.C, wn, base, s);
             float lik = 1.0f;
             if (x != kNA) {
-                double part[CP], mx = 0.0;
-#pragma unroll
-                for (int c = 0; c < CP; ++c) {
-                    part[c] = c < g.C ? wn[c] * base[c][x] : 0.0;
-                    if (c < g.C) mx += part[c];
-                }
+                double part[CP];
+                const double mx = cell_state(g.C, wn, base, x, part);
                 if (mx > 0.0) {
 #pragma unroll
                     for (int c = 0; c < CP; ++c) resp[c] += part[c] / mx;
@@ -274,22 +161,8 @@ namespace {
 
 constexpr char kNullHandle[] = "null handle";
 
-bool shape_ok(int64_t N, int64_t F, int S, int C, int K, int R) {
-    return N >= 1 && N <= SBE_PREDICT_MAX_OBJECTS && F >= 1 && F <= SBE_PREDICT_MAX_FEATURES && S >= 1 && S <= kMaxS && C >= 1 && C <= kMaxC &&
-           K >= 1 && R >= K && R <= kMaxR && N * F * (S + C) * 8 <= SBE_PREDICT_MAX_ACC_BYTES;
-}
-
 int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R, bool lik) {
     return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + (lik ? 4 * N * F : 0);
-}
-
-size_t slices_bytes(const sbe_predict* h, int Ft) { return 2 * (size_t)Ft * ((size_t)h->R * h->S + h->C) * sizeof(double); }
-
-// host bytes <-> device in pieces of at most kStageBytes, on the handle's stream
-int copy_pieces(sbe_predict* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    for (size_t at = 0; at < bytes; at += (size_t)kStageBytes)
-        HIPCHK(h, hipMemcpyAsync((char*)dst + at, (const char*)src + at, std::min((size_t)kStageBytes, bytes - at), kind, h->stream));
-    return SBE_OK;
 }
 
 int zero_accumulators(sbe_predict* h) {
@@ -298,22 +171,6 @@ int zero_accumulators(sbe_predict* h) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_samples = 0;
     return SBE_OK;
-}
-
-// the message of a validation failure
-int data_error(sbe_predict* h, unsigned long long key) {
-    const long long t = (long long)(key >> 40), at = (long long)(key & ((1ull << 36) - 1));
-    const int F = h->F, S = h->S, C = h->C;
-    switch ((int)((key >> 36) & 15)) {
-    case kOverlap: return fail(h, SBE_ERR_DATA, "sample %lld: object %lld is in more than one cluster", t, at);
-    case kWeightEntry: return fail(h, SBE_ERR_DATA, "sample %lld: weights[%lld][%lld] is negative or not finite", t, at / C, at % C);
-    case kWeightSum: return fail(h, SBE_ERR_DATA, "sample %lld: the weights of feature %lld sum further than %g from 1", t, at, SBE_PREDICT_SUM_TOL);
-    case kTableEntry:
-        return fail(h, SBE_ERR_DATA, "sample %lld: tables[%lld][%lld][%lld] (row, feature, state) is negative or not finite", t, at / S / F,
-                    at / S % F, at % S);
-    case kTableRowEmpty: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld has no positive entry", t, at / F, at % F);
-    default: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld sums further than %g from 1", t, at / F, at % F, SBE_PREDICT_SUM_TOL);
-    }
 }
 
 }  // namespace
@@ -345,34 +202,8 @@ int sbe_predict_set_feature_tile(sbe_predict* h, int features) {
 
 int sbe_predict_set_data(sbe_predict* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups) {
     CHECK_HANDLE(h, kNullHandle);
-    if (N < 1 || N > SBE_PREDICT_MAX_OBJECTS) return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d]", (long long)N, SBE_PREDICT_MAX_OBJECTS);
-    if (F < 1 || F > SBE_PREDICT_MAX_FEATURES) return fail(h, SBE_ERR_ARG, "n_features=%lld out of range [1, %d]", (long long)F, SBE_PREDICT_MAX_FEATURES);
-    if (S < 1 || S > kMaxS) return fail(h, SBE_ERR_ARG, "n_states=%d out of range [1, %d]", S, kMaxS);
-    if (C < 1 || C > kMaxC) return fail(h, SBE_ERR_ARG, "n_components=%d out of range [1, %d]", C, kMaxC);
-    if (K < 1 || K > kMaxR) return fail(h, SBE_ERR_ARG, "n_clusters=%d out of range [1, %d]", K, kMaxR);
-    if (!codes) return fail(h, SBE_ERR_ARG, "null pointer argument: codes");
-    if (C > 1 && (!groups || !n_groups)) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !groups ? "groups" : "n_groups");
-    int row_off[kMaxC] = {};
-    int R = K;
-    for (int c = 1; c < C; ++c) {
-        if (n_groups[c - 1] < 1 || n_groups[c - 1] > kMaxR)
-            return fail(h, SBE_ERR_ARG, "n_groups[%d]=%d out of range [1, %d]", c - 1, n_groups[c - 1], kMaxR);
-        row_off[c] = R;
-        R += n_groups[c - 1];
-    }
-    if (R > kMaxR) return fail(h, SBE_ERR_ARG, "%d clusters and the confounders' groups make %d table rows, the limit is %d", K, R, kMaxR);
-    if (N * F * (S + C) * 8 > SBE_PREDICT_MAX_ACC_BYTES)
-        return fail(h, SBE_ERR_ARG, "the accumulators of %lld objects x %lld features x (%d states + %d components) take %lld bytes on the device, the limit is %lld",
-                    (long long)N, (long long)F, S, C, (long long)(N * F * (S + C) * 8), (long long)SBE_PREDICT_MAX_ACC_BYTES);
-    for (int64_t q = 0; q < N * F; ++q)
-        if (codes[q] >= S && codes[q] != kNA)
-            return fail(h, SBE_ERR_DATA, "codes[%lld][%lld]=%d is neither a state below %d nor 255", (long long)(q / F), (long long)(q % F), (int)codes[q], S);
-    for (int c = 1; c < C; ++c)
-        for (int64_t i = 0; i < N; ++i) {
-            const uint8_t g = groups[(int64_t)(c - 1) * N + i];
-            if (g >= n_groups[c - 1] && g != kNA)
-                return fail(h, SBE_ERR_DATA, "groups[%d][%lld]=%d is neither a group below %d nor 255", c - 1, (long long)i, (int)g, n_groups[c - 1]);
-        }
+    int row_off[kMaxC], R;
+    if (const int bad = check_data(h, N, F, S, C, K, codes, groups, n_groups, row_off, R)) return bad;
     h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
     HIPCHK(h, hipSetDevice(h->device));
     int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
@@ -414,16 +245,9 @@ int sbe_predict_accumulate(sbe_predict* h, int64_t n, const uint8_t* clusters, c
     if (n > SBE_PREDICT_MAX_STAGE_BYTES / per_sample)
         return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
                     (long long)n, (long long)per_sample, (long long)SBE_PREDICT_MAX_STAGE_BYTES, (long long)(SBE_PREDICT_MAX_STAGE_BYTES / per_sample));
-    // the tile along the features
-    int Ft = h->forced_tile;
-    if (Ft == 0) {
-        Ft = std::min(kDefaultTile, pow2_at_least((int)F));
-        while (Ft > 1 && slices_bytes(h, Ft) > kSmallSlices) Ft /= 2;
-    }
-    const size_t lds = slices_bytes(h, Ft);
-    if (lds > kLdsBudget)
-        return fail(h, SBE_ERR_ARG, "a tile of %d features takes two slices of %d rows x %d states: %lld bytes of LDS, the limit is %lld", Ft, R, S,
-                    (long long)lds, (long long)kLdsBudget);
+    int Ft;
+    size_t lds;
+    if (const int bad = plan_tile(h, h->forced_tile, F, R, S, C, Ft, lds)) return bad;
     HIPCHK(h, hipSetDevice(h->device));
     const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
     int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
@@ -436,16 +260,11 @@ int sbe_predict_accumulate(sbe_predict* h, int64_t n, const uint8_t* clusters, c
     if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
     if (rc) return rc;
     unsigned long long* d_err = h->d_words + 1;
-    HIPCHK(h, hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    k_predict_ids<<<(unsigned)div_up(n * N, kBlock), kBlock, 0, h->stream>>>(h->d_clusters, n, N, K, h->d_kid, d_err);
-    HIPCHK(h, hipGetLastError());
-    k_predict_validate<<<(unsigned)div_up(n * F * (1 + R), kBlock), kBlock, 0, h->stream>>>(h->d_weights, h->d_tables, n, (int)F, S, C, R, d_err);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, h->d_clusters, h->d_weights, h->d_tables, h->d_kid, d_err))) return rc;
     unsigned long long key = kNoError;
     HIPCHK(h, hipMemcpyAsync(&key, d_err, sizeof key, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (key != kNoError) return data_error(h, key);
+    if (key != kNoError) return data_error(h, key, (int)F, S, C);
 
     AccArgs args{};
     args.codes = h->d_codes;
