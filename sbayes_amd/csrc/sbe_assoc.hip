@@ -6,13 +6,10 @@
 // With X the one-hot matrix [N][F * S_pad] (S_pad: the next power of two >= the largest state count, so that a 32 x 32
 // tile holds (32 / S_pad)^2 whole pairs), all contingency tables at once are X^T X.  k_assoc_pairs computes one 32 x 32
 // tile of it per wave, for the tile pairs I <= J:
-//   1. contraction over objects in steps of 64 with v_mfma_f32_32x32x64_f8f6f4, FP4 operands (0 = 0x0, 1 = 0x2 in e2m1
-//      are exact, and so are the counts in the f32 accumulator while N <= 2^24).  The operands are built in registers
-//      from the feature-major codes [F][N_pad]: a lane owns one one-hot column (feature f, state s) and 32 objects of the
-//      step; four byte-parallel operations turn four codes into four "code == s" bits (an NA object, 255, matches no
-//      state, and neither does the padding behind N).  Both operands put an object at the same (lane half, nibble)
-//      position, so the instruction's internal k order does not matter.  Four steps form a round whose loads are issued
-//      together;
+//   1. the FP4 contraction over objects of sbe_unit_tiles.hip.h (the counts are exact in the f32 accumulator while
+//      N <= 2^24).  The operands are built in registers from the feature-major codes [F][N_pad]: a lane owns one one-hot
+//      column (feature f, state s) and 32 objects of the step; four byte-parallel operations turn four codes into four
+//      "code == s" bits (an NA object, 255, matches no state, and neither does the padding behind N);
 //   2. the accumulator tile goes to LDS; margins of every sub-table along both tile axes, then per pair its total, the
 //      occupied rows R and columns C, dof = (R-1)(C-1);
 //   3. per cell the Pearson term in fp64 (expected r c / n, Yates' correction when dof == 1), into LDS;
@@ -26,24 +23,15 @@
 #include <limits>
 #include <vector>
 
-#include "sbe_unit.hip.h"
+#include "sbe_unit_tiles.hip.h"
 #include "../../include/sbe_assoc.h"
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;                            // one-hot columns per tile edge
-constexpr int kStep = 64;                            // objects per MFMA
-constexpr int kRound = 4;                            // steps per round of the contraction loop
-constexpr int kPad = kRound * kStep;                 // the codes are padded to whole rounds
+constexpr int kPad = 256;                            // the codes are padded to whole rounds: a lane reads a byte per object
 constexpr int kTableBlock = 256;
-// contraction steps per launch of the pair kernel: a launch of one full wave per SIMD then stays in the milliseconds at
-// any N (a tile pair at N = 2^24 takes 2^18 steps: 16 tile pairs per launch)
-constexpr int64_t kStepsPerLaunch = (int64_t)1 << 22;
-constexpr int64_t kMaxLaunchTiles = (int64_t)1 << 16;
 constexpr int kSeriesMaxIter = 5000;                 // (the series and the fraction end long before at dof <= 961)
+static_assert(kPad == kRoundElems, "a round of codes is a round of the contraction");
 
 // ---- Q(a, x), the regularized upper incomplete gamma function ---------------------------------------------------
 // tests/_assoc_oracle.py restates both functions operation for operation.
@@ -158,10 +146,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
 
     const int64_t t = g.t0 + blockIdx.x;
     if (t >= g.t_end) return;
-    int64_t J = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (J * (J + 1) / 2 > t) --J;
-    while ((J + 1) * (J + 2) / 2 <= t) ++J;
-    const int64_t I = t - J * (J + 1) / 2;
+    const TilePair pair = tile_pair(t);
+    const int64_t I = pair.I, J = pair.J;
     const int lane = threadIdx.x, half = lane >> 5;
 
     // ---- 1. the contraction
@@ -184,11 +170,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
         for (int u = 0; u < kRound; ++u) {
             const v8i a = fp4_operand(ca.q[2 * u], ca.q[2 * u + 1], sa);
             const v8i b = fp4_operand(cb.q[2 * u], cb.q[2 * u + 1], sb);
-            acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, 0, 0, 0);
+            acc = mfma_fp4(a, b, acc);
         }
     }
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) cnt[(reg & 3) + 8 * (reg >> 2) + 4 * half][lane & 31] = acc[reg];
+    for_acc_entries(acc, half, lane & 31, [&](int row, int col, float v) { cnt[row][col] = v; });
     __syncthreads();
 
     // ---- 2. margins along both tile axes, then total, R, C and dof per sub-table
@@ -307,7 +292,7 @@ inline size_t pair_lds_bytes(int sub) { return (size_t)kTile * kTile * sizeof(do
 
 }  // namespace
 
-struct sbe_assoc : sbe_unit_handle {             // (sbe_unit.hip.h; ev: around the pair kernel's launches)
+struct sbe_assoc : sbe_unit_handle, unit_tile_launches {   // (sbe_unit.hip.h; ev: around the pair kernel's launches)
     uint8_t* d_xt = nullptr;                     // codes of the last compute call, feature-major [F][n_pad]
     size_t xt_bytes = 0;
     void* d_out = nullptr;                       // the five [F][F] outputs, or the tables of one sbe_assoc_tables call
@@ -316,7 +301,6 @@ struct sbe_assoc : sbe_unit_handle {             // (sbe_unit.hip.h; ev: around 
     size_t pairs_bytes = 0;
     int64_t N = 0, n_pad = 0, F = 0;             // shape of the codes held (F == 0: none yet)
     int s_max = 0, s_pad = 0;
-    int64_t launch_tiles = 0;                    // 0: the default
     int64_t tile_pairs = 0, launches = 0;
     std::vector<void*> buffers() const { return {d_xt, d_out, d_pairs}; }
 };
@@ -337,13 +321,7 @@ int sbe_assoc_create(sbe_assoc** out, int device) { return unit_create_on_device
 
 int sbe_assoc_destroy(sbe_assoc* h) { return unit_destroy(h, kNullHandle); }
 
-int sbe_assoc_set_launch_tiles(sbe_assoc* h, int64_t tile_pairs) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (tile_pairs < 0 || tile_pairs > kMaxLaunchTiles)
-        return fail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
-    h->launch_tiles = tile_pairs;
-    return SBE_OK;
-}
+int sbe_assoc_set_launch_tiles(sbe_assoc* h, int64_t tile_pairs) { return unit_set_launch_tiles(h, tile_pairs, kNullHandle); }
 
 int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t n_features, const int32_t* n_states,
                       double* statistic, double* pvalue, int32_t* dof, int32_t* n, uint8_t* valid) {
@@ -368,7 +346,7 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
         s_max = std::max(s_max, (int)n_states[f]);
     }
     // the codes, checked and turned feature-major, padded to whole rounds of the contraction with NA
-    const int64_t n_pad = (N + kPad - 1) / kPad * kPad;
+    const int64_t n_pad = whole_rounds(N);
     std::vector<uint8_t> xt((size_t)(F * n_pad), (uint8_t)SBE_ASSOC_NA);
     for (int64_t i0 = 0; i0 < N; i0 += kStep) {        // (blocks of objects: the block's rows stay in cache, the writes are contiguous)
         const int64_t i1 = std::min(N, i0 + kStep);
@@ -388,9 +366,7 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
     while ((1 << log_s) < s_max) ++log_s;
     const int sub = kTile >> log_s;
     const int64_t tiles = (F + sub - 1) / sub, tile_pairs = tiles * (tiles + 1) / 2;
-    const int64_t per_launch = h->launch_tiles > 0
-        ? h->launch_tiles
-        : std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / (n_pad / kStep)));
+    const int64_t per_launch = tiles_per_launch(n_pad / kStep, h->launch_tiles);
 
     HIPCHK(h, hipSetDevice(h->device));
     h->F = 0;                                       // (until the new codes are in place)
@@ -408,13 +384,13 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
     HIPCHK(h, hipGetLastError());
     int64_t launches = 0;
     rc = unit_timed(h, [&] {
-        for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch, ++launches) {      // one wave per tile pair
-            const int64_t t_end = std::min(tile_pairs, t0 + per_launch);
+        return unit_for_tile_launches(tile_pairs, per_launch, [&](int64_t t0, int64_t t_end) {      // one wave per tile pair
             const PairArgs args{h->d_xt, n_pad, (int)F, log_s, t0, t_end, d_stat, d_p, d_dof, d_n, d_valid};
             k_assoc_pairs<<<(unsigned)(t_end - t0), 64, pair_lds_bytes(sub), h->stream>>>(args);
             HIPCHK(h, hipGetLastError());
-        }
-        return SBE_OK;
+            ++launches;
+            return SBE_OK;
+        });
     });
     if (!rc) rc = unit_copy_back(h, (const double*)d_stat, ff, {statistic, pvalue});
     if (!rc) rc = unit_copy_back(h, (const int32_t*)d_dof, ff, {dof, n});
@@ -450,7 +426,7 @@ int sbe_assoc_tables(sbe_assoc* h, const int32_t* pairs, int64_t n_pairs, int32_
     if ((rc = unit_ensure(h, h->d_out, h->out_bytes, (size_t)n_pairs * cells * sizeof(int32_t)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_pairs, pairs, (size_t)n_pairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     // a block walks all N objects of its pair: as many pairs per launch as the pair kernel's budget allows steps
-    const int64_t per_launch = std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / (h->n_pad / kStep)));
+    const int64_t per_launch = tiles_per_launch(h->n_pad / kStep);
     for (int64_t p0 = 0; p0 < n_pairs; p0 += per_launch) {
         k_assoc_table<<<(unsigned)std::min(per_launch, n_pairs - p0), kTableBlock, 0, h->stream>>>(h->d_xt, h->n_pad, h->N, h->d_pairs, p0,
                                                                                                h->s_max, (int32_t*)h->d_out);

@@ -4,15 +4,13 @@
 // contract is tests/_consensus_oracle.py; DESIGN.md section 19 has the layout, the structure of the kernels and the limits.
 //
 // With Z the 0/1 matrix of all cluster rows of the selected runs, [T K][N], the similarity counts are Z^T Z.
-// k_consensus_similarity computes one 32 x 32 tile of it per wave, for the tile pairs I <= J, as sbe_assoc.hip computes
-// its contingency tables: contraction in steps of 64 elements with v_mfma_f32_32x32x64_f8f6f4 and FP4 operands (0 = 0x0
-// and 1 = 0x2 in e2m1 are exact, and so are the counts in the f32 accumulator while T K <= 2^24).  Unlike there the
-// operands are not built in registers: the pack kernel has written them, so the loop is loads and MFMAs only.
+// k_consensus_similarity computes one 32 x 32 tile of it per wave, for the tile pairs I <= J, with the FP4 contraction of
+// sbe_unit_tiles.hip.h (the counts are exact in the f32 accumulator while T K <= 2^24).  The pack kernel has written the
+// operands, so the loop is loads and MFMAs only.
 //   image: [N_pad objects][n_runs segments][seg_bytes]; element e = s K + k of a run is nibble e & 7 of dword e >> 3 of
 //   the run's segment; a segment is zero behind the run's last element and padded to whole rounds of 256 elements.
-//   A lane owns one object (lane & 31) and one half of a step (lane >> 5): 32 elements, one 16-byte load.  Both MFMA
-//   operands are read from this one image with the same (lane half, nibble) placement, so the instruction's internal
-//   order of the 64 products does not matter: the same element of the two objects always meets.
+//   A lane owns one object (lane & 31) and one half of a step (lane >> 5): 32 elements, one 16-byte load, and both
+//   operands come from this one image.
 // k_consensus_scores takes one (sample, cluster) row per workgroup from the bit rows, k_consensus_compare one matrix row.
 #include <hip/hip_runtime.h>
 
@@ -20,28 +18,15 @@
 #include <cmath>
 #include <vector>
 
-#include "sbe_unit.hip.h"
+#include "sbe_unit_tiles.hip.h"
 #include "../../include/sbe_consensus.h"
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int kMaxK = SBE_CONSENSUS_MAX_CLUSTERS;
 constexpr int kMaxRuns = SBE_CONSENSUS_MAX_RUNS;
-constexpr int kTile = 32;                            // objects per tile edge
-constexpr int kStep = 64;                            // contraction elements per MFMA
-constexpr int kRound = 4;                            // steps per round: a round's loads are issued together
-constexpr int kRoundElems = kRound * kStep;          // = SBE_CONSENSUS_ROUND
-constexpr int kRoundBytes = kRoundElems / 2;         // of one object's image
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-// contraction steps per launch of the similarity kernel: a launch of one full wave per SIMD then stays in the milliseconds
-// at any T K (a tile pair at T K = 2^24 takes 2^18 steps: 16 tile pairs per launch)
-constexpr int64_t kStepsPerLaunch = (int64_t)1 << 22;
-constexpr int64_t kMaxLaunchTiles = (int64_t)1 << 16;
-// the score kernel's launches are bounded the same way: a row gathers at most N^2 entries, (N / 64)^2 units of 64 x 64, and
+// the score kernel's launches are bounded as the similarity kernel's are: a row gathers at most N^2 entries, (N / 64)^2 units of 64 x 64, and
 // a launch holds at most 2^26 units (1024 rows at N = 16384, every row at N <= 512)
 constexpr int64_t kScoreUnitsPerLaunch = (int64_t)1 << 26;
 static_assert(kRoundElems == SBE_CONSENSUS_ROUND, "the header states the round length");
@@ -76,34 +61,11 @@ struct SimArgs {
     int32_t seg_rounds[kMaxRuns];
 };
 
-// one round of a lane: four steps of 32 elements each
-struct LaneRound {
-    uint4 q[kRound];
-};
-
-__device__ inline LaneRound load_round(const uint8_t* p) {
-    LaneRound c;
-#pragma unroll
-    for (int u = 0; u < kRound; ++u) c.q[u] = *reinterpret_cast<const uint4*>(p + u * (kStep / 2));
-    return c;
-}
-
-__device__ inline v8i fp4_operand(const uint4 q) {
-    v8i v = {};
-    v[0] = (int)q.x;
-    v[1] = (int)q.y;
-    v[2] = (int)q.z;
-    v[3] = (int)q.w;
-    return v;
-}
-
 __global__ __launch_bounds__(64) void k_consensus_similarity(const SimArgs g) {
     const int64_t t = g.t0 + blockIdx.x;
     if (t >= g.t_end) return;
-    int64_t J = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (J * (J + 1) / 2 > t) --J;
-    while ((J + 1) * (J + 2) / 2 <= t) ++J;
-    const int64_t I = t - J * (J + 1) / 2;
+    const TilePair pair = tile_pair(t);
+    const int64_t I = pair.I, J = pair.J;
     const int lane = threadIdx.x, half = lane >> 5;
     // (the image has whole tiles of objects: the rows behind N are zero)
     const uint8_t* pa = g.img + (I * kTile + (lane & 31)) * g.stride + (kStep / 4) * half;
@@ -115,21 +77,22 @@ __global__ __launch_bounds__(64) void k_consensus_similarity(const SimArgs g) {
         for (int r = 0; r < g.seg_rounds[q]; ++r, a += kRoundBytes, b += kRoundBytes) {
             const LaneRound ca = load_round(a), cb = load_round(b);
 #pragma unroll
-            for (int u = 0; u < kRound; ++u)
-                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_operand(ca.q[u]), fp4_operand(cb.q[u]), acc, 4, 4, 0, 0, 0, 0);
+            for (int u = 0; u < kRound; ++u) acc = mfma_fp4(fp4_operand(ca.q[u]), fp4_operand(cb.q[u]), acc);
         }
     }
-    // register reg of a lane is row (reg & 3) + 8 (reg >> 2) + 4 half (an object of tile I), column lane & 31 (of tile J)
+    // the tile's rows are objects of tile I, its columns objects of tile J
     const int64_t j = J * kTile + (lane & 31);
     if (j >= g.N) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int64_t i = I * kTile + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-        if (i >= g.N) continue;
-        const int32_t c = (int32_t)acc[reg];
-        g.counts[i * g.N + j] = c;
-        if (I != J) g.counts[j * g.N + i] = c;               // (a diagonal tile holds both triangles itself)
-    }
+    // (copies for the loop's body, and a 64-bit row: the compiler then forms j N and loads counts once, not per row)
+    int32_t* const counts = g.counts;
+    const int64_t N = g.N;
+    for_acc_entries(acc, (int64_t)half, lane & 31, [=](int64_t row, int, float v) {
+        const int64_t i = I * kTile + row;
+        if (i >= N) return;
+        const int32_t c = (int32_t)v;
+        counts[i * N + j] = c;
+        if (I != J) counts[j * N + i] = c;                   // (a diagonal tile holds both triangles itself)
+    });
 }
 
 // ---- the score kernel: one workgroup per (sample, cluster) row ---------------------------------------------------------
@@ -195,10 +158,9 @@ struct Slot {
 
 }  // namespace
 
-struct sbe_consensus : sbe_unit_handle, unit_bit_store {   // (sbe_unit.hip.h; ev: around the kernels of the last similarity, scores or compare)
+struct sbe_consensus : sbe_unit_handle, unit_bit_store, unit_tile_launches {   // (ev: around the kernels of the last similarity, scores or compare)
     int64_t seg_bytes = 0, stride = 0;
     uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
-    int64_t launch_tiles = 0;           // 0: the default
     Slot slot[2];
     uint8_t* d_img = nullptr;           // [32 W][n_runs][seg_bytes]
     size_t img_bytes = 0;
@@ -214,12 +176,10 @@ namespace {
 constexpr char kNullHandle[] = "null handle";
 constexpr char kLane[] = "run", kReset[] = "sbe_consensus_reset";
 
-int64_t segment_bytes(int K, int64_t cap) { return (cap * K + kRoundElems - 1) / kRoundElems * kRoundBytes; }
+constexpr unit_store_limits kLimits{kMaxRuns, SBE_CONSENSUS_MAX_CLUSTERS, SBE_CONSENSUS_MAX_OBJECTS, SBE_CONSENSUS_MAX_ROWS,
+                                    SBE_CONSENSUS_MAX_IMAGE_BYTES, "(an int32 matrix [N][N] of at most 1 GiB)"};
 
-bool shape_ok(int n_runs, int K, int64_t N, int64_t cap) {
-    return n_runs >= 1 && n_runs <= kMaxRuns && K >= 1 && K <= kMaxK && N >= 1 && N <= SBE_CONSENSUS_MAX_OBJECTS && cap >= 1 &&
-           cap <= SBE_CONSENSUS_MAX_ROWS;
-}
+int64_t segment_bytes(int K, int64_t cap) { return rounds_of(cap * K) * kRoundBytes; }
 
 int64_t store_bytes(int n_runs, int K, int64_t N, int64_t cap) {
     const int64_t W = (N + 31) / 32;
@@ -247,7 +207,7 @@ int sbe_consensus_abi_version(void) { return SBE_CONSENSUS_ABI_VERSION; }
 const char* sbe_consensus_last_error(const sbe_consensus* h) { return unit_last_error(h); }
 
 int64_t sbe_consensus_image_bytes(int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows) {
-    return shape_ok(n_runs, n_clusters, n_objects, capacity_rows) ? store_bytes(n_runs, n_clusters, n_objects, capacity_rows) : 0;
+    return unit_bit_store::shape_ok(kLimits, n_runs, n_clusters, n_objects, capacity_rows) ? store_bytes(n_runs, n_clusters, n_objects, capacity_rows) : 0;
 }
 
 int sbe_consensus_create(sbe_consensus** out, int device) { return unit_create_on_device(out, device, "sbe_consensus_create"); }
@@ -256,27 +216,13 @@ int sbe_consensus_destroy(sbe_consensus* h) { return unit_destroy(h, kNullHandle
 
 int sbe_consensus_last_kernel_ms(const sbe_consensus* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
 
-int sbe_consensus_set_launch_tiles(sbe_consensus* h, int64_t tile_pairs) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (tile_pairs < 0 || tile_pairs > kMaxLaunchTiles)
-        return fail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
-    h->launch_tiles = tile_pairs;
-    return SBE_OK;
-}
+int sbe_consensus_set_launch_tiles(sbe_consensus* h, int64_t tile_pairs) { return unit_set_launch_tiles(h, tile_pairs, kNullHandle); }
 
 int sbe_consensus_reset(sbe_consensus* h, int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows) {
     CHECK_HANDLE(h, kNullHandle);
-    if (n_runs < 1 || n_runs > kMaxRuns) return fail(h, SBE_ERR_ARG, "n_runs=%d out of range [1, %d]", n_runs, kMaxRuns);
-    if (n_clusters < 1 || n_clusters > kMaxK) return fail(h, SBE_ERR_ARG, "n_clusters=%d out of range [1, %d]", n_clusters, kMaxK);
-    if (n_objects < 1 || n_objects > SBE_CONSENSUS_MAX_OBJECTS)
-        return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (an int32 matrix [N][N] of at most 1 GiB)", (long long)n_objects,
-                    SBE_CONSENSUS_MAX_OBJECTS);
-    if (capacity_rows < 1 || capacity_rows > SBE_CONSENSUS_MAX_ROWS)
-        return fail(h, SBE_ERR_ARG, "capacity_rows=%lld out of range [1, %d]", (long long)capacity_rows, SBE_CONSENSUS_MAX_ROWS);
-    const int64_t bytes = store_bytes(n_runs, n_clusters, n_objects, capacity_rows);
-    if (bytes > SBE_CONSENSUS_MAX_IMAGE_BYTES)
-        return fail(h, SBE_ERR_ARG, "a store of %d runs x %lld rows x %d clusters x %lld objects takes %lld bytes on the device, the limit is %lld",
-                    n_runs, (long long)capacity_rows, n_clusters, (long long)n_objects, (long long)bytes, (long long)SBE_CONSENSUS_MAX_IMAGE_BYTES);
+    if (const int rc = h->check_shape(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows)) return rc;
+    if (const int rc = h->check_device_bytes(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows, store_bytes(n_runs, n_clusters, n_objects, capacity_rows)))
+        return rc;
     const int64_t W = (n_objects + 31) / 32, seg = segment_bytes(n_clusters, capacity_rows);
     const size_t img = (size_t)(32 * W * n_runs * seg);
     h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
@@ -306,17 +252,7 @@ int sbe_consensus_append_rows(sbe_consensus* h, int run, const uint8_t* rows, in
     CHECK_HANDLE(h, kNullHandle);
     int rc = h->runs.check_append(h, kLane, kReset, run, rows, n_rows);
     if (rc || n_rows == 0) return rc;
-    const int64_t row_bytes = (int64_t)h->K * h->N;
-    for (int64_t q0 = 0; q0 < n_rows * row_bytes; q0 += 4096) {      // (blocks: the common case is one OR per byte)
-        const int64_t q1 = std::min(n_rows * row_bytes, q0 + 4096);
-        uint8_t any = 0;
-        for (int64_t q = q0; q < q1; ++q) any |= rows[q];
-        if (any <= 1) continue;
-        int64_t q = q0;
-        while (rows[q] <= 1) ++q;
-        return fail(h, SBE_ERR_DATA, "rows[%lld][%lld][%lld]=%d is neither 0 nor 1", (long long)(q / row_bytes), (long long)(q % row_bytes / h->N),
-                    (long long)(q % h->N), (int)rows[q]);
-    }
+    if ((rc = h->check_binary(h, rows, 0, n_rows))) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     uint8_t* seg = h->d_img + (int64_t)run * h->seg_bytes;
     rc = h->append_pieces(h, run, rows, n_rows, [&](int64_t k, int64_t row) {
@@ -346,7 +282,7 @@ int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot
         if (!run_mask[r] || rows == 0) continue;
         T += rows;
         args.seg_off[args.n_seg] = (int64_t)r * h->seg_bytes;
-        args.seg_rounds[args.n_seg] = (int32_t)((rows * h->K + kRoundElems - 1) / kRoundElems);
+        args.seg_rounds[args.n_seg] = (int32_t)rounds_of(rows * h->K);
         steps += (int64_t)args.seg_rounds[args.n_seg] * kRound;
         ++args.n_seg;
     }
@@ -360,20 +296,19 @@ int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot
     s.version = 0;                                        // (until the new matrix is in place)
     int rc = unit_ensure(h, s.d_counts, s.bytes, nn * sizeof(int32_t));
     if (rc) return rc;
-    const int64_t tiles = (h->N + kTile - 1) / kTile, tile_pairs = tiles * (tiles + 1) / 2;
-    const int64_t per_launch = h->launch_tiles > 0 ? h->launch_tiles : std::max<int64_t>(1, std::min(kMaxLaunchTiles, kStepsPerLaunch / steps));
+    const int64_t tiles = tiles_of(h->N), tile_pairs = tiles * (tiles + 1) / 2;
     args.img = h->d_img;
     args.stride = h->stride;
     args.counts = s.d_counts;
     args.N = (int)h->N;
     rc = unit_timed(h, [&] {
-        for (int64_t t0 = 0; t0 < tile_pairs; t0 += per_launch) {      // one wave per tile pair
+        return unit_for_tile_launches(tile_pairs, tiles_per_launch(steps, h->launch_tiles), [&](int64_t t0, int64_t t_end) {      // one wave per tile pair
             args.t0 = t0;
-            args.t_end = std::min(tile_pairs, t0 + per_launch);
-            k_consensus_similarity<<<(unsigned)(args.t_end - t0), 64, 0, h->stream>>>(args);
+            args.t_end = t_end;
+            k_consensus_similarity<<<(unsigned)(t_end - t0), 64, 0, h->stream>>>(args);
             HIPCHK(h, hipGetLastError());
-        }
-        return SBE_OK;
+            return SBE_OK;
+        });
     });
     if (!rc && counts_out) rc = unit_copy_back(h, (const int32_t*)s.d_counts, nn, {counts_out});
     if (!rc) rc = unit_sync_timed(h);

@@ -4,45 +4,31 @@
 // vector pipe.  The contract is tests/_partdist_oracle.py; DESIGN.md section 23 has the layout, the kernels and the limits.
 //
 // With Z the 0/1 matrix of all cluster rows, [T K_pad][N], the contingency tables of all sample pairs are the K_pad x K_pad
-// blocks of Z Z^T.  k_partdist_tiles computes its 32 x 32 tiles as k_consensus_similarity computes its own, a wave a strip
-// of up to four tiles that share their rows of the row side: contraction over the objects in steps of 64 with
-// v_mfma_f32_32x32x64_f8f6f4 and FP4 operands (0 = 0x0 and 1 = 0x2 in e2m1 are exact, and so are counts <= N in the f32
-// accumulator).
+// blocks of Z Z^T.  k_partdist_tiles computes its 32 x 32 tiles with the FP4 contraction of sbe_unit_tiles.hip.h over the
+// objects (counts <= N are exact in the f32 accumulator), a wave a strip of up to four tiles that share their rows of the
+// row side.
 //   image: [run][row K_pad + k][N_pad / 2 bytes]; object i is nibble i & 7 of dword i >> 3 of its row; a run holds
 //   cap K_pad rows rounded up to whole tiles; the rows k >= K, the rows behind a run's last and the objects >= N are zero.
-//   A lane owns one row of a tile (lane & 31) and one half of a step (lane >> 5): 32 objects, one 16-byte load.  Both MFMA
-//   operands are read from this one image with the same (lane half, nibble) placement, so the instruction's internal
-//   order of the 64 products does not matter: the same object of the two rows always meets.
+//   A lane owns one row of a tile (lane & 31) and one half of a step (lane >> 5): 32 objects, one 16-byte load, and both
+//   operands come from this one image.
 // A tile is 32 / K_pad x 32 / K_pad whole sample pairs; the epilogue takes the strip's pairs from LDS, one pair per lane and turn.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "sbe_unit.hip.h"
+#include "sbe_unit_tiles.hip.h"
 #include "../../include/sbe_partdist.h"
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int kMaxK = SBE_PARTDIST_MAX_CLUSTERS;
-constexpr int kMaxRuns = SBE_PARTDIST_MAX_RUNS;
-constexpr int kTile = 32;                            // image rows per tile edge
-constexpr int kStep = 64;                            // objects per MFMA
-constexpr int kRound = 4;                            // steps per round: a round's loads are issued together
-constexpr int kRoundElems = kRound * kStep;          // = SBE_PARTDIST_ROUND
-constexpr int kRoundBytes = kRoundElems / 2;         // of one image row
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 // tiles of the column side a wave holds (a strip): it loads its rows of the row side once for all of them, and the launch
 // has a quarter of the workgroups.  The plain form, one tile per wave, re-read 32 KiB of operands for sixteen MFMAs and was
 // bound by that and by the dispatch of its single-wave workgroups
 constexpr int kStrip = 4;
-// contraction steps and tiles per launch of the tile kernel, as in sbe_assoc.hip and sbe_consensus.hip
-constexpr int64_t kStepsPerLaunch = (int64_t)1 << 22;
-constexpr int64_t kMaxLaunchTiles = (int64_t)1 << 16;
 // entries of the dense block a chunk of the sums holds in scratch: 128 MiB of int32 and 256 MiB of float64
 constexpr int64_t kSumChunkEntries = (int64_t)1 << 25;
 static_assert(kRoundElems == SBE_PARTDIST_ROUND, "the header states the round length");
@@ -97,26 +83,6 @@ struct TileArgs {
     int32_t* sumsq;
 };
 
-struct LaneRound {
-    uint4 q[kRound];
-};
-
-__device__ inline LaneRound load_round(const uint8_t* p) {
-    LaneRound c;
-#pragma unroll
-    for (int u = 0; u < kRound; ++u) c.q[u] = *reinterpret_cast<const uint4*>(p + u * (kStep / 2));
-    return c;
-}
-
-__device__ inline v8i fp4_operand(const uint4 q) {
-    v8i v = {};
-    v[0] = (int)q.x;
-    v[1] = (int)q.y;
-    v[2] = (int)q.z;
-    v[3] = (int)q.w;
-    return v;
-}
-
 __global__ __launch_bounds__(64) void k_partdist_tiles(const TileArgs g) {
     __shared__ uint16_t tile[kStrip][kTile][kTile + 2];          // (a count is at most N <= 16384)
     const int64_t t = g.t0 + blockIdx.x;
@@ -139,15 +105,12 @@ __global__ __launch_bounds__(64) void k_partdist_tiles(const TileArgs g) {
             const LaneRound cb = load_round(b[m]);
             b[m] += kRoundBytes;
 #pragma unroll
-            for (int u = 0; u < kRound; ++u)
-                acc[m] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_operand(ca.q[u]), fp4_operand(cb.q[u]), acc[m], 4, 4, 0, 0, 0, 0);
+            for (int u = 0; u < kRound; ++u) acc[m] = mfma_fp4(fp4_operand(ca.q[u]), fp4_operand(cb.q[u]), acc[m]);
         }
     }
-    // register reg of a lane is row (reg & 3) + 8 (reg >> 2) + 4 half (of tile I), column lane & 31 (of the strip's tile m)
+    // the tile's rows are rows of tile I, its columns rows of the strip's tile m
 #pragma unroll
-    for (int m = 0; m < kStrip; ++m)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) tile[m][(reg & 3) + 8 * (reg >> 2) + 4 * half][lane & 31] = (uint16_t)(int)acc[m][reg];
+    for (int m = 0; m < kStrip; ++m) for_acc_entries(acc[m], half, lane & 31, [&](int row, int col, float v) { tile[m][row][col] = (uint16_t)(int)v; });
     __syncthreads();
     // ---- the epilogue: one sample pair per lane and turn; x is the earlier sample of the pair, y the later --------------
     const int K = g.K, N = g.N;
@@ -281,10 +244,9 @@ struct Buffer {
 
 }  // namespace
 
-struct sbe_partdist : sbe_unit_handle, unit_bit_store {   // (sbe_unit.hip.h; ev: around the kernels of the last block, sums or tables)
+struct sbe_partdist : sbe_unit_handle, unit_bit_store, unit_tile_launches {   // (ev: around the kernels of the last block, sums or tables)
     int K_pad = 0, shift = 0;
     int64_t N_pad = 0, run_rows = 0;    // image rows of one run: cap K_pad rounded up to whole tiles
-    int64_t launch_tiles = 0;           // 0: the default
     Buffer<uint8_t> img;                // [n_runs][run_rows][N_pad / 2]
     Buffer<int32_t> sizes;              // [n_runs][cap][K]
     Buffer<double> xlogx;               // [N + 1]
@@ -306,15 +268,12 @@ namespace {
 constexpr char kNullHandle[] = "null handle";
 constexpr char kLane[] = "run", kReset[] = "sbe_partdist_reset";
 
-int64_t padded_objects(int64_t N) { return (N + kRoundElems - 1) / kRoundElems * kRoundElems; }
-int64_t run_image_rows(int K, int64_t cap) { return (cap * pow2_at_least(K) + kTile - 1) / kTile * kTile; }
+constexpr unit_store_limits kLimits{SBE_PARTDIST_MAX_RUNS, kMaxK, SBE_PARTDIST_MAX_OBJECTS, SBE_PARTDIST_MAX_ROWS, SBE_PARTDIST_MAX_IMAGE_BYTES,
+                                    "(2 N^2 fits an int32)"};
 
-bool shape_ok(int n_runs, int K, int64_t N, int64_t cap) {
-    return n_runs >= 1 && n_runs <= kMaxRuns && K >= 1 && K <= kMaxK && N >= 1 && N <= SBE_PARTDIST_MAX_OBJECTS && cap >= 1 &&
-           cap <= SBE_PARTDIST_MAX_ROWS;
-}
+int64_t run_image_rows(int K, int64_t cap) { return whole_tiles(cap * pow2_at_least(K)); }
 
-int64_t image_only_bytes(int n_runs, int K, int64_t N, int64_t cap) { return n_runs * run_image_rows(K, cap) * (padded_objects(N) / 2); }
+int64_t image_only_bytes(int n_runs, int K, int64_t N, int64_t cap) { return n_runs * run_image_rows(K, cap) * (whole_rounds(N) / 2); }
 
 int64_t store_bytes(int n_runs, int K, int64_t N, int64_t cap) {
     const int64_t W = (N + 31) / 32;
@@ -365,15 +324,14 @@ int launch_block(sbe_partdist* h, int ra, int64_t r0, int64_t nr, int rb, int64_
     g.SJ = (g.TJ + kStrip - 1) / kStrip;
     const int64_t strips = TI * g.SJ, steps = (int64_t)g.rounds * kRound;
     // (tiles per launch, in whole strips)
-    const int64_t tiles_per_launch = h->launch_tiles > 0 ? h->launch_tiles : std::min(kMaxLaunchTiles, kStepsPerLaunch / steps);
-    const int64_t per_launch = std::max<int64_t>(1, tiles_per_launch / kStrip);
-    for (int64_t t0 = 0; t0 < strips; t0 += per_launch) {               // one wave per strip
+    const int64_t per_launch = std::max<int64_t>(1, tiles_per_launch(steps, h->launch_tiles) / kStrip);
+    return unit_for_tile_launches(strips, per_launch, [&](int64_t t0, int64_t t_end) {               // one wave per strip
         g.t0 = t0;
-        g.t_end = std::min(strips, t0 + per_launch);
-        k_partdist_tiles<<<(unsigned)(g.t_end - t0), 64, 0, h->stream>>>(g);
+        g.t_end = t_end;
+        k_partdist_tiles<<<(unsigned)(t_end - t0), 64, 0, h->stream>>>(g);
         HIPCHK(h, hipGetLastError());
-    }
-    return SBE_OK;
+        return SBE_OK;
+    });
 }
 
 // the host scan of an appended call: 0 / 1 bytes and disjoint areas per sample
@@ -382,21 +340,11 @@ int scan_rows(sbe_partdist* h, const uint8_t* rows, int64_t n_rows) {
     const int64_t N = h->N;
     std::vector<uint8_t> held((size_t)N);
     for (int64_t s = 0; s < n_rows; ++s) {
+        if (const int rc = h->check_binary(h, rows, s, 1)) return rc;
         const uint8_t* sample = rows + s * K * N;
         std::fill(held.begin(), held.end(), (uint8_t)0);
-        uint8_t any = 0;
-        for (int k = 0; k < K; ++k) {
-            const uint8_t* row = sample + k * N;
-            for (int64_t i = 0; i < N; ++i) {
-                any |= row[i];
-                held[(size_t)i] = (uint8_t)(held[(size_t)i] + (row[i] != 0));
-            }
-        }
-        if (any > 1) {
-            int64_t q = 0;
-            while (sample[q] <= 1) ++q;
-            return fail(h, SBE_ERR_DATA, "rows[%lld][%lld][%lld]=%d is neither 0 nor 1", (long long)s, (long long)(q / N), (long long)(q % N), (int)sample[q]);
-        }
+        for (int k = 0; k < K; ++k)
+            for (int64_t i = 0; i < N; ++i) held[(size_t)i] = (uint8_t)(held[(size_t)i] + sample[k * N + i]);
         uint8_t most = 0;
         for (int64_t i = 0; i < N; ++i) most = std::max(most, held[(size_t)i]);
         if (most > 1) {
@@ -418,7 +366,7 @@ int sbe_partdist_abi_version(void) { return SBE_PARTDIST_ABI_VERSION; }
 const char* sbe_partdist_last_error(const sbe_partdist* h) { return unit_last_error(h); }
 
 int64_t sbe_partdist_image_bytes(int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows) {
-    return shape_ok(n_runs, n_clusters, n_objects, capacity_rows) ? store_bytes(n_runs, n_clusters, n_objects, capacity_rows) : 0;
+    return unit_bit_store::shape_ok(kLimits, n_runs, n_clusters, n_objects, capacity_rows) ? store_bytes(n_runs, n_clusters, n_objects, capacity_rows) : 0;
 }
 
 int sbe_partdist_create(sbe_partdist** out, int device) { return unit_create_on_device(out, device, "sbe_partdist_create"); }
@@ -427,27 +375,14 @@ int sbe_partdist_destroy(sbe_partdist* h) { return unit_destroy(h, kNullHandle);
 
 int sbe_partdist_last_kernel_ms(const sbe_partdist* h, float* ms_out) { return unit_last_kernel_ms(h, ms_out, kNullHandle); }
 
-int sbe_partdist_set_launch_tiles(sbe_partdist* h, int64_t tile_pairs) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (tile_pairs < 0 || tile_pairs > kMaxLaunchTiles)
-        return fail(h, SBE_ERR_ARG, "tile_pairs=%lld out of range [0, %lld]", (long long)tile_pairs, (long long)kMaxLaunchTiles);
-    h->launch_tiles = tile_pairs;
-    return SBE_OK;
-}
+int sbe_partdist_set_launch_tiles(sbe_partdist* h, int64_t tile_pairs) { return unit_set_launch_tiles(h, tile_pairs, kNullHandle); }
 
 int sbe_partdist_reset(sbe_partdist* h, int n_runs, int n_clusters, int64_t n_objects, int64_t capacity_rows, const double* xlogx) {
     CHECK_HANDLE(h, kNullHandle);
-    if (n_runs < 1 || n_runs > kMaxRuns) return fail(h, SBE_ERR_ARG, "n_runs=%d out of range [1, %d]", n_runs, kMaxRuns);
-    if (n_clusters < 1 || n_clusters > kMaxK) return fail(h, SBE_ERR_ARG, "n_clusters=%d out of range [1, %d]", n_clusters, kMaxK);
-    if (n_objects < 1 || n_objects > SBE_PARTDIST_MAX_OBJECTS)
-        return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (2 N^2 fits an int32)", (long long)n_objects, SBE_PARTDIST_MAX_OBJECTS);
-    if (capacity_rows < 1 || capacity_rows > SBE_PARTDIST_MAX_ROWS)
-        return fail(h, SBE_ERR_ARG, "capacity_rows=%lld out of range [1, %d]", (long long)capacity_rows, SBE_PARTDIST_MAX_ROWS);
+    if (const int rc = h->check_shape(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows)) return rc;
     if (!xlogx) return fail(h, SBE_ERR_ARG, "null pointer argument: xlogx");
-    const int64_t bytes = store_bytes(n_runs, n_clusters, n_objects, capacity_rows);
-    if (bytes > SBE_PARTDIST_MAX_IMAGE_BYTES)
-        return fail(h, SBE_ERR_ARG, "a store of %d runs x %lld rows x %d clusters x %lld objects takes %lld bytes on the device, the limit is %lld",
-                    n_runs, (long long)capacity_rows, n_clusters, (long long)n_objects, (long long)bytes, (long long)SBE_PARTDIST_MAX_IMAGE_BYTES);
+    if (const int rc = h->check_device_bytes(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows, store_bytes(n_runs, n_clusters, n_objects, capacity_rows)))
+        return rc;
     const size_t image = (size_t)image_only_bytes(n_runs, n_clusters, n_objects, capacity_rows);
     h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
     HIPCHK(h, hipSetDevice(h->device));
@@ -462,7 +397,7 @@ int sbe_partdist_reset(sbe_partdist* h, int n_runs, int n_clusters, int64_t n_ob
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->K_pad = pow2_at_least(n_clusters);
     h->shift = h->K_pad == 1 ? 0 : h->K_pad == 2 ? 1 : h->K_pad == 4 ? 2 : 3;
-    h->N_pad = padded_objects(n_objects);
+    h->N_pad = whole_rounds(n_objects);
     h->run_rows = run_image_rows(n_clusters, capacity_rows);
     h->set_shape(n_runs, n_clusters, n_objects, capacity_rows);
     return SBE_OK;

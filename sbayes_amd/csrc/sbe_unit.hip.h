@@ -2,7 +2,7 @@
 // sbe_unit.hip.h -- what the host code of the side units shares (every .hip file that includes this header: each an opaque
 // handle type of its own behind a C header of its own): the handle's common members, error reporting, the HIP check,
 // create, destroy, device buffers that only grow, launches in grid chunks, the row store's lanes and its piece loop, the
-// bit store, the timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes
+// bit store with the host checks of a sample store's shape and bytes, the timed region of a compute call and the copies back.  Host code only and nothing of the engine: a unit that includes
 // this header compiles no kernels but its own (the device side is sbe_unit_device.hip.h, taken from here for its launch
 // limit).  sbe_engine_internal.hip.h takes HIPCHK and div_up from here.  The helpers live in an unnamed namespace, as the
 // engine's do: every unit compiles its own copy.
@@ -223,6 +223,13 @@ struct unit_lanes {
     }
 };
 
+// the most a unit's bit store may be shaped to; objects_why: the unit's reason for max_objects, in parentheses
+struct unit_store_limits {
+    int max_runs, max_clusters;
+    int64_t max_objects, max_rows, max_bytes;
+    const char* objects_why;
+};
+
 // A bit store: runs of cluster samples, host rows [n][K][N] of 0 / 1 bytes, held as bit words [runs][cap][K][W] with
 // W = ceil(N / 32).  A unit's handle derives from it beside sbe_unit_handle and lists d_bits and d_stage in its buffers().
 struct unit_bit_store {
@@ -248,6 +255,47 @@ struct unit_bit_store {
         runs.rows.assign((size_t)n_runs, 0);
     }
     uint32_t* at(int run, int64_t row) const { return d_bits + ((int64_t)run * runs.cap + row) * K * W; }
+
+    // The range checks of <prefix>_reset against the unit's limits.  report = false records no message: shape_ok, by which
+    // <prefix>_image_bytes decides whether there is a size to state
+    static bool shape_ok(const unit_store_limits& lim, int n_runs, int n_clusters, int64_t n_objects, int64_t cap) {
+        return check_shape((sbe_unit_handle*)nullptr, lim, n_runs, n_clusters, n_objects, cap, false) == SBE_OK;
+    }
+    template <class H>
+    static int check_shape(H* h, const unit_store_limits& lim, int n_runs, int n_clusters, int64_t n_objects, int64_t cap, bool report = true) {
+        auto refuse = [&](const char* fmt, auto... a) { return report ? fail(h, SBE_ERR_ARG, fmt, a...) : (int)SBE_ERR_ARG; };
+        if (n_runs < 1 || n_runs > lim.max_runs) return refuse("n_runs=%d out of range [1, %d]", n_runs, lim.max_runs);
+        if (n_clusters < 1 || n_clusters > lim.max_clusters) return refuse("n_clusters=%d out of range [1, %d]", n_clusters, lim.max_clusters);
+        if (n_objects < 1 || n_objects > lim.max_objects)
+            return refuse("n_objects=%lld out of range [1, %lld] %s", (long long)n_objects, (long long)lim.max_objects, lim.objects_why);
+        if (cap < 1 || cap > lim.max_rows) return refuse("capacity_rows=%lld out of range [1, %lld]", (long long)cap, (long long)lim.max_rows);
+        return SBE_OK;
+    }
+    // ... and of what a shape that passed them takes on the device, `bytes` by the unit's count
+    template <class H>
+    static int check_device_bytes(H* h, const unit_store_limits& lim, int n_runs, int n_clusters, int64_t n_objects, int64_t cap, int64_t bytes) {
+        if (bytes <= lim.max_bytes) return SBE_OK;
+        return fail(h, SBE_ERR_ARG, "a store of %d runs x %lld rows x %d clusters x %lld objects takes %lld bytes on the device, the limit is %lld", n_runs,
+                    (long long)cap, n_clusters, (long long)n_objects, (long long)bytes, (long long)lim.max_bytes);
+    }
+
+    // The samples [s0, s0 + n) of a call's host rows [.][K][N] hold only 0 and 1: else the first other byte, by its place in
+    // the call.  (Blocks: the common case is one OR per byte.)
+    template <class H>
+    int check_binary(H* h, const uint8_t* rows, int64_t s0, int64_t n) const {
+        const int64_t row_bytes = (int64_t)K * N, end = (s0 + n) * row_bytes;
+        for (int64_t q0 = s0 * row_bytes; q0 < end; q0 += 4096) {
+            const int64_t q1 = std::min(end, q0 + 4096);
+            uint8_t any = 0;
+            for (int64_t q = q0; q < q1; ++q) any |= rows[q];
+            if (any <= 1) continue;
+            int64_t q = q0;
+            while (rows[q] <= 1) ++q;
+            return fail(h, SBE_ERR_DATA, "rows[%lld][%lld][%lld]=%d is neither 0 nor 1", (long long)(q / row_bytes), (long long)(q % row_bytes / N),
+                        (long long)(q % N), (int)rows[q]);
+        }
+        return SBE_OK;
+    }
 
     // The whole of <prefix>_append_rows: the argument checks, the handle's device, the pieces.
     template <class H, class Hook>
