@@ -1,10 +1,12 @@
 #pragma once
 // sbe_predict_row.hip.h -- the mixture row of a cell, m_t[n,f,.], written once for the units that put the logged samples back
-// on the data: the posterior predictive (sbe_predict.hip) and the posterior predictive check (sbe_ppc.hip).  Both take the data
+// on the data: the posterior predictive (sbe_predict.hip), the posterior predictive check (sbe_ppc.hip) and the per-cluster
+// evidence (sbe_contrib.hip).  All take the data
 // and a sample of include/sbe_predict.h word for word, so they share what reads them: the checks of the data's arguments, the
 // ids kernel, the validation kernel with the offender's key, the plan of the feature tile, the staging of a sample's slice
 // into one of two LDS buffers and the w~ / m arithmetic of a cell.  A unit's kernel
-// calls, per workgroup, tile_cell and cell_group once and, per sample, stage_slice, cell_weights and cell_state.
+// calls, per workgroup, tile_cell and cell_group once and, per sample, stage_slice, cell_weights and cell_state
+// (sbe_contrib.hip: cell_weights_in_and_out, cell_state and cell_state_in, the object placed in every cluster and in none).
 // Everything lives in an unnamed namespace, as the unit layer does: every unit compiles its own copy.
 #include <hip/hip_runtime.h>
 
@@ -165,6 +167,45 @@ __device__ inline void cell_weights(const G& g, const TileCell& c, const double*
     }
 #pragma unroll
     for (int k = 0; k < CP; ++k) wn[k] = wsum > 0.0 ? wn[k] / wsum : 0.0;
+}
+
+// The counterfactual weights of a cell (include/sbe_contrib.h), whatever the object's own membership in sample t: a_0 = w[f][0],
+// a_c = w[f][c] where confounder c applies; w1 = a / (a_0 + a_1 + ..) is cell_weights' w~ of a member of any cluster, w0 = a /
+// (a_1 + a_2 + ..), with w0[0] = 0, its w~ of an object in no cluster -- the same operations in the same order, so the rows
+// they weigh have cell_state's bits.  base[c], c >= 1: where the confounder's table row starts.  False where no confounder
+// applies (a_1 + a_2 + .. is not > 0): w0 is then zero.
+template <int CP, class G>
+__device__ inline bool cell_weights_in_and_out(const G& g, const TileCell& c, const double* cur, const int (&row)[CP], const bool (&has)[CP],
+                                               double (&w1)[CP], double (&w0)[CP], const double* (&base)[CP]) {
+    double wsum1 = 0.0, wsum0 = 0.0;
+#pragma unroll
+    for (int k = 0; k < CP; ++k) {
+        w1[k] = k < g.C && (k == 0 || has[k]) ? cur[c.w_at + k] : 0.0;
+        w0[k] = k == 0 ? 0.0 : w1[k];
+        if (k < g.C) {
+            wsum1 += w1[k];
+            wsum0 += w0[k];
+        }
+        base[k] = cur + (row[k] * g.Ft + c.fl) * g.S;
+    }
+#pragma unroll
+    for (int k = 0; k < CP; ++k) {
+        w1[k] = wsum1 > 0.0 ? w1[k] / wsum1 : 0.0;
+        w0[k] = wsum0 > 0.0 ? w0[k] / wsum0 : 0.0;
+    }
+    return wsum0 > 0.0;
+}
+
+// m_k at state s of an object placed in the cluster whose table row starts at `theta`: cell_state's chain of additions with
+// the cluster's term first, over the confounders' products part[c] = w1_c table_c[s], c >= 1, which do not depend on k
+template <int CP>
+__device__ inline double cell_state_in(int C, double w1_0, const double* theta, int s, const double (&part)[CP]) {
+    double m = 0.0;
+    m += w1_0 * theta[s];
+#pragma unroll
+    for (int k = 1; k < CP; ++k)
+        if (k < C) m += part[k];
+    return m;
 }
 
 // m[s] = sum_c w~_c table_c[s], c in order, every product rounded, then added (the build contracts nothing); part: the products
