@@ -3,18 +3,9 @@
 // scipy.stats.chi2_contingency.  The numerical contract is tests/_assoc_oracle.py; DESIGN.md section 13 has the layout
 // and the limits.
 //
-// With X the one-hot matrix [N][F * S_pad] (S_pad: the next power of two >= the largest state count, so that a 32 x 32
-// tile holds (32 / S_pad)^2 whole pairs), all contingency tables at once are X^T X.  k_assoc_pairs computes one 32 x 32
-// tile of it per wave, for the tile pairs I <= J:
-//   1. the FP4 contraction over objects of sbe_unit_tiles.hip.h (the counts are exact in the f32 accumulator while
-//      N <= 2^24).  The operands are built in registers from the feature-major codes [F][N_pad]: a lane owns one one-hot
-//      column (feature f, state s) and 32 objects of the step; four byte-parallel operations turn four codes into four
-//      "code == s" bits (an NA object, 255, matches no state, and neither does the padding behind N);
-//   2. the accumulator tile goes to LDS; margins of every sub-table along both tile axes, then per pair its total, the
-//      occupied rows R and columns C, dof = (R-1)(C-1);
-//   3. per cell the Pearson term in fp64 (expected r c / n, Yates' correction when dof == 1), into LDS;
-//   4. per pair one lane sums its terms in the fixed order (a major, b minor) -- empty rows and columns add +0.0, which
-//      changes no bit of a non-negative sum -- and evaluates Q(dof/2, statistic/2); the pair and its mirror are stored.
+// All contingency tables at once are X^T X of the one-hot matrix.  k_assoc_pairs computes one 32 x 32 tile of it per wave, for
+// the tile pairs I <= J, by the four steps of sbe_assoc_pair.hip.h (contraction, margins and dof, Pearson terms, ordered
+// sum), evaluates Q(dof/2, statistic/2) per pair and stores the pair and its mirror.
 // No table is written to memory.  k_assoc_table counts one caller-named pair per block with integer atomics in LDS.
 #include <hip/hip_runtime.h>
 
@@ -23,15 +14,13 @@
 #include <limits>
 #include <vector>
 
-#include "sbe_unit_tiles.hip.h"
+#include "sbe_assoc_pair.hip.h"
 #include "../../include/sbe_assoc.h"
 
 namespace {
 
-constexpr int kPad = 256;                            // the codes are padded to whole rounds: a lane reads a byte per object
 constexpr int kTableBlock = 256;
 constexpr int kSeriesMaxIter = 5000;                 // (the series and the fraction end long before at dof <= 961)
-static_assert(kPad == kRoundElems, "a round of codes is a round of the contraction");
 
 // ---- Q(a, x), the regularized upper incomplete gamma function ---------------------------------------------------
 // tests/_assoc_oracle.py restates both functions operation for operation.
@@ -96,158 +85,35 @@ struct PairArgs {
     uint8_t* valid;
 };
 
-// four "code == s" bits of four codes: codes are < 32 or 255, s < 32 (or 0x40 for a column behind the last feature, which
-// matches nothing).  Masked to six bits an NA code is 63; the xor is zero exactly for a match; adding 0x7f sets bit 7 of
-// every non-zero byte without a carry (63 + 127 < 256)
-__device__ inline uint32_t match4(uint32_t codes, uint32_t s4) {
-    return ~(((codes & 0x3f3f3f3fu) ^ s4) + 0x7f7f7f7fu) & 0x80808080u;
-}
-
-// FP4 operand of one lane: 32 objects (32 codes) against the lane's state; 1.0 = 0x2 in e2m1, so a match sets bit 1 of its
-// nibble.  Object 8 d + b of the 32 goes to nibble 2 b (b < 4) or 2 (b - 4) + 1 of dword d
-__device__ inline v8i fp4_operand(const uint4 lo, const uint4 hi, uint32_t s4) {
-    v8i v = {};
-    v[0] = (int)((match4(lo.x, s4) >> 6) | (match4(lo.y, s4) >> 2));
-    v[1] = (int)((match4(lo.z, s4) >> 6) | (match4(lo.w, s4) >> 2));
-    v[2] = (int)((match4(hi.x, s4) >> 6) | (match4(hi.y, s4) >> 2));
-    v[3] = (int)((match4(hi.z, s4) >> 6) | (match4(hi.w, s4) >> 2));
-    return v;
-}
-
-// the codes of one lane for one round of kRound contraction steps: q[2 u], q[2 u + 1] are its 32 objects of step u.  A round's
-// loads are issued together, so their latency is paid once per round
-struct LaneCodes {
-    uint4 q[2 * kRound];
-};
-
-__device__ inline LaneCodes load_codes(const uint8_t* p) {
-    LaneCodes c;
-#pragma unroll
-    for (int u = 0; u < kRound; ++u) {
-        c.q[2 * u] = *reinterpret_cast<const uint4*>(p + u * kStep);
-        c.q[2 * u + 1] = *reinterpret_cast<const uint4*>(p + u * kStep + 16);
-    }
-    return c;
-}
-
 // (at most four waves per SIMD, which the LDS allows anyway: the compiler then keeps a round's sixteen loads in flight instead
 // of trading them for registers)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_assoc_pairs(const PairArgs g) {
-    // dynamic LDS, pair_lds_bytes(sub): the terms (8 KiB) -- whose first half holds the tile of X^T X until step 3 -- then the
-    // margins and the per-pair values, sized by the sub-tables per tile edge, so that four waves fit a SIMD from S_pad = 8 on
-    extern __shared__ double assoc_lds[];
+    extern __shared__ double assoc_lds[];                    // dynamic LDS, pair_lds_bytes(sub)
     const int S = 1 << g.log_s, sub = kTile >> g.log_s;      // states per feature (padded), features per tile edge
-    double (*term)[kTile] = reinterpret_cast<double(*)[kTile]>(assoc_lds);
-    float (*cnt)[kTile] = reinterpret_cast<float(*)[kTile]>(assoc_lds);   // rows = columns of tile I, columns = of tile J
-    float* rm = reinterpret_cast<float*>(assoc_lds + kTile * kTile);       // [row][q]: sum of the row over the states of column feature q
-    float* cm = rm + kTile * sub;                                          // [p][col]: sum of the column over the states of row feature p
-    float* pn = cm + kTile * sub;                                          // per sub-table: total
-    int* pdof = reinterpret_cast<int*>(pn + sub * sub);                    //                dof (0: not valid)
+    const PairLds l = pair_lds(assoc_lds, sub);
 
     const int64_t t = g.t0 + blockIdx.x;
     if (t >= g.t_end) return;
     const TilePair pair = tile_pair(t);
     const int64_t I = pair.I, J = pair.J;
-    const int lane = threadIdx.x, half = lane >> 5;
+    const int lane = threadIdx.x;
 
-    // ---- 1. the contraction
-    auto column = [&](int64_t tile, const uint8_t*& base, uint32_t& s4) {
-        const int64_t col = tile * kTile + (lane & 31);
-        int64_t f = col >> g.log_s;
-        uint32_t s = (uint32_t)(col & (S - 1));
-        if (f >= g.F) { f = 0; s = 0x40u; }
-        base = g.xt + f * g.n_pad + 32 * half;
-        s4 = s * 0x01010101u;
-    };
-    const uint8_t *pa, *pb;
-    uint32_t sa, sb;
-    column(I, pa, sa);
-    column(J, pb, sb);
-    v16f acc = {};
-    for (int64_t n0 = 0; n0 < g.n_pad; n0 += kPad) {
-        const LaneCodes ca = load_codes(pa + n0), cb = load_codes(pb + n0);
-#pragma unroll
-        for (int u = 0; u < kRound; ++u) {
-            const v8i a = fp4_operand(ca.q[2 * u], ca.q[2 * u + 1], sa);
-            const v8i b = fp4_operand(cb.q[2 * u], cb.q[2 * u + 1], sb);
-            acc = mfma_fp4(a, b, acc);
-        }
-    }
-    for_acc_entries(acc, half, lane & 31, [&](int row, int col, float v) { cnt[row][col] = v; });
-    __syncthreads();
-
-    // ---- 2. margins along both tile axes, then total, R, C and dof per sub-table
-    for (int idx = lane; idx < kTile * sub; idx += 64) {
-        const int row = idx / sub, q = idx - row * sub;
-        float s = 0.f;
-        for (int b = 0; b < S; ++b) s += cnt[row][q * S + b];
-        rm[row * sub + q] = s;
-        const int p = idx / kTile, col = idx - p * kTile;
-        s = 0.f;
-        for (int a = 0; a < S; ++a) s += cnt[p * S + a][col];
-        cm[p * kTile + col] = s;
-    }
-    __syncthreads();
-    for (int idx = lane; idx < sub * sub; idx += 64) {
-        const int p = idx / sub, q = idx - p * sub;
-        float n = 0.f;
-        int R = 0, C = 0;
-        for (int a = 0; a < S; ++a) {
-            const float r = rm[(p * S + a) * sub + q];
-            n += r;
-            R += r > 0.f;
-            C += cm[p * kTile + q * S + a] > 0.f;
-        }
-        pn[idx] = n;
-        pdof[idx] = (R > 1 && C > 1) ? (R - 1) * (C - 1) : 0;
-    }
-    __syncthreads();
-
-    // ---- 3. the Pearson terms (each lane takes its 16 counts out of the shared buffer before the terms go in)
-    float obs[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) obs[k] = cnt[2 * k + half][lane & 31];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int row = 2 * k + half, col = lane & 31, p = row >> g.log_s, q = col >> g.log_s;
-        const float r = rm[row * sub + q], c = cm[p * kTile + col];
-        const int dof = pdof[p * sub + q];
-        double v = 0.0;
-        if (dof > 0 && r > 0.f && c > 0.f) {
-            const double o = (double)obs[k];
-            const double e = (double)r * (double)c / (double)pn[p * sub + q];
-            double oc = o;
-            if (dof == 1) {                              // Yates: O + sign(E - O) min(0.5, |E - O|)
-                const double d = e - o;
-                const double sgn = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
-                oc = o + fmin(0.5, fabs(d)) * sgn;
-            }
-            const double diff = oc - e;
-            v = diff * diff / e;
-        }
-        term[row][col] = v;
-    }
-    __syncthreads();
+    // ---- 1. to 3.: the contraction, the margins, the Pearson terms
+    const v16f acc = pair_contract(g.xt, g.n_pad, g.F, g.log_s, I, J, lane);
+    pair_terms(l, acc, g.log_s, lane);
 
     // ---- 4. statistic and p-value per pair; the pair and its mirror
     for (int idx = lane; idx < sub * sub; idx += 64) {
         const int p = idx / sub, q = idx - p * sub;
         const int64_t i = I * sub + p, j = J * sub + q;
         if (i >= j || j >= g.F) continue;                // (i < j: the diagonal tile pairs hold every pair twice)
-        const int dof = pdof[idx];
+        const int dof = l.pdof[idx];
         double stat = 0.0, pv = std::numeric_limits<double>::quiet_NaN();
         if (dof > 0) {
-            for (int a = 0; a < S; ++a)
-#pragma unroll 4
-                for (int b = 0; b < S; b += 2) {           // (S is even; the reads run ahead, the adds keep their order)
-                    const double t0 = term[p * S + a][q * S + b], t1 = term[p * S + a][q * S + b + 1];
-                    stat += t0;
-                    stat += t1;
-                }
+            stat = pair_statistic(l, p, q, S);
             pv = assoc_gamma_q(0.5 * (double)dof, 0.5 * stat);
         }
-        const int n = (int)pn[idx];
+        const int n = (int)l.pn[idx];
         for (int m = 0; m < 2; ++m) {
             const int64_t o = m ? j * g.F + i : i * g.F + j;
             g.statistic[o] = stat;
@@ -288,8 +154,6 @@ __global__ __launch_bounds__(kTableBlock) void k_assoc_table(const uint8_t* xt, 
     for (int c = threadIdx.x; c < S * S; c += kTableBlock) out[p * S * S + c] = tab[c];
 }
 
-inline size_t pair_lds_bytes(int sub) { return (size_t)kTile * kTile * sizeof(double) + (size_t)(2 * kTile * sub + 2 * sub * sub) * 4; }
-
 }  // namespace
 
 struct sbe_assoc : sbe_unit_handle, unit_tile_launches {   // (sbe_unit.hip.h; ev: around the pair kernel's launches)
@@ -329,41 +193,13 @@ int sbe_assoc_compute(sbe_assoc* h, const uint8_t* x, int64_t n_objects, int64_t
     if (!x || !n_states) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !x ? "x" : "n_states");
     if (!statistic || !pvalue || !dof || !n || !valid) return fail(h, SBE_ERR_ARG, "null pointer argument: output");
     const int64_t N = n_objects, F = n_features;
-    if (N < 1 || N > SBE_ASSOC_MAX_OBJECTS)
-        return fail(h, SBE_ERR_ARG, "n_objects=%lld out of range [1, %d] (2^24: counts are exact in the f32 accumulator up to there)",
-                     (long long)N, SBE_ASSOC_MAX_OBJECTS);
-    if (F < 1 || F > SBE_ASSOC_MAX_FEATURES)
-        return fail(h, SBE_ERR_ARG, "n_features=%lld out of range [1, %d] (the [F][F] outputs take 25 bytes per entry)",
-                     (long long)F, SBE_ASSOC_MAX_FEATURES);
-    if (N * F > SBE_ASSOC_MAX_CODES)
-        return fail(h, SBE_ERR_ARG, "n_objects * n_features = %lld exceeds the limit of %lld (2^31) codes", (long long)(N * F),
-                     (long long)SBE_ASSOC_MAX_CODES);
     int s_max = 1;
-    for (int64_t f = 0; f < F; ++f) {
-        if (n_states[f] < 1 || n_states[f] > SBE_ASSOC_MAX_STATES)
-            return fail(h, SBE_ERR_ARG, "n_states[%lld]=%d out of range [1, %d] (this unit's limit: a 32 x 32 tile holds whole pairs)",
-                         (long long)f, n_states[f], SBE_ASSOC_MAX_STATES);
-        s_max = std::max(s_max, (int)n_states[f]);
-    }
+    if (const int rc = pair_check_shape(h, N, F, n_states, s_max)) return rc;
     // the codes, checked and turned feature-major, padded to whole rounds of the contraction with NA
     const int64_t n_pad = whole_rounds(N);
-    std::vector<uint8_t> xt((size_t)(F * n_pad), (uint8_t)SBE_ASSOC_NA);
-    for (int64_t i0 = 0; i0 < N; i0 += kStep) {        // (blocks of objects: the block's rows stay in cache, the writes are contiguous)
-        const int64_t i1 = std::min(N, i0 + kStep);
-        for (int64_t f = 0; f < F; ++f) {
-            const int32_t ns = n_states[f];
-            uint8_t* dst = xt.data() + (size_t)(f * n_pad);
-            for (int64_t i = i0; i < i1; ++i) {
-                const uint8_t c = x[i * F + f];
-                if (c != SBE_ASSOC_NA && c >= ns)
-                    return fail(h, SBE_ERR_DATA, "x[%lld][%lld]=%d is neither below n_states[%lld]=%d nor %d (not observed)", (long long)i,
-                                 (long long)f, (int)c, (long long)f, ns, SBE_ASSOC_NA);
-                dst[i] = c;
-            }
-        }
-    }
-    int log_s = 1;
-    while ((1 << log_s) < s_max) ++log_s;
+    std::vector<uint8_t> xt;
+    if (const int rc = pair_feature_major(h, x, N, F, n_states, n_pad, xt)) return rc;
+    const int log_s = pair_log_s(s_max);
     const int sub = kTile >> log_s;
     const int64_t tiles = (F + sub - 1) / sub, tile_pairs = tiles * (tiles + 1) / 2;
     const int64_t per_launch = tiles_per_launch(n_pad / kStep, h->launch_tiles);

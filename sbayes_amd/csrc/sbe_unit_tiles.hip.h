@@ -1,6 +1,6 @@
 #pragma once
-// sbe_unit_tiles.hip.h -- what the three units on the matrix pipe share beyond sbe_unit.hip.h (sbe_assoc.hip,
-// sbe_consensus.hip, sbe_partdist.hip, and no other file): the FP4 contraction step of a 32 x 32 tile of a 0/1 matrix product,
+// sbe_unit_tiles.hip.h -- what the units on the matrix pipe share beyond sbe_unit.hip.h (sbe_consensus.hip, sbe_partdist.hip,
+// and through sbe_assoc_pair.hip.h sbe_assoc.hip and sbe_pairppc.hip; no other file): the FP4 contraction step of a 32 x 32 tile of a 0/1 matrix product,
 // the walk over a lane's part of the finished tile, and the launches of a range of tiles within the budget.  The numbers
 // are sbe_tile_plan.h's; DESIGN.md section 13 says why the operands are FP4 and why their placement is free.  Everything
 // lives in an unnamed namespace, as in the sibling headers.

@@ -262,6 +262,14 @@ class PpcHandle(_handle.UnitHandle):
             self.n_samples += n
             self.n_skipped += skipped.value
 
+    def drain_replicates(self):
+        """The y_rep blocks of the check() calls since the last drain, in order; the handle forgets them (result().y_rep is then
+        None).  For a consumer that takes the replicates block by block (sbayes_amd/pairppc.py)."""
+        ys = self._rows["y_rep"]
+        out = [y for y in ys if y is not None]
+        ys[:] = [None] * len(ys)
+        return out
+
     def result(self) -> PpcResult:
         _N, _F, S, _C, _K, _R = self._with_data()
         if self.n_samples == 0:
