@@ -3,81 +3,23 @@
 // per-observation WAIC terms.  The numerical contract is tests/_elpd_oracle.py; DESIGN.md section 11 has the layout,
 // the selection and the limits.
 //
-// Per column (S samples of float32 lh > 0, ll = log(double(lh))):
-//   1. min of the bit patterns (positive floats order as uint32) and the data check; column staged in LDS when
-//      it fits the budget, else every pass below reads global memory (same code, same order of operations);
-//   2. sum of ll (mean, for the variance) and sum of lh (= sum exp(ll): lppd_i);
-//   3. _psislw's cutoff: x = -ll - max(-ll) orders as the reverse of lh, so the element at ascending x position S-T-1
-//      is the (T+1)-th smallest lh -- found exactly by an 8-bit radix select over the bit patterns (LDS histograms);
-//   4. the tail (lh strictly below the cutoff: at most T elements) compacted into LDS and bitonic-sorted;
-//   5. _gpdfit in fp64 (the m_est candidates spread over the waves), _gpinv smoothing, the tail's sums;
-//   6. variance of ll (second pass about the mean) and the body's sums, then loo_i.
-// Every sum is a fixed tree over fixed per-thread partial sums: results do not depend on the store's capacity or on
-// how the store was filled, so the host path and the engine path give the same bits.
+// The column's steps (min and check, sums, radix-select cutoff, tail sort, _gpdfit, _gpinv, the tail's and the body's sums) are
+// sbe_psis_column.hip.h's, shared with sbe_loopred.hip.  Every sum is a fixed tree over fixed per-thread partial sums: results
+// do not depend on the store's capacity or on how the store was filled, so the host path and the engine path give the same bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "sbe_psis_column.hip.h"
 #include "sbe_unit.hip.h"
 #include "sbe_engine_internal.hip.h"   // sbe_elpd_append_engine reads the engine's row on the device
 #include "../../include/sbe_elpd.h"
 
 namespace {
 
-constexpr int kElpdBlock = 256;                      // 4 waves per column
-constexpr int kElpdWaves = kElpdBlock / 64;
-constexpr int kMaxM = 96;                            // _gpdfit candidates: 30 + sqrt(T) <= 85 for S <= 2^20 (T <= 3072)
-constexpr size_t kStaticLds = 8192;                  // headroom for the kernel's static LDS (histogram, reductions, fit)
-
-inline int tail_count(int64_t s) { return (int)std::ceil(std::min(0.2 * (double)s, 3.0 * std::sqrt((double)s))); }
-// dynamic LDS of a column of S samples: [tail exceedances Tp x f64][tail keys Tp x u32][staged column S x u32]
-inline size_t tail_lds_bytes(int64_t s) { return (size_t)pow2_at_least(std::max(tail_count(s), 1)) * (sizeof(uint32_t) + sizeof(double)); }
-inline size_t staged_lds_bytes(int64_t s) { return (size_t)s * sizeof(uint32_t) + tail_lds_bytes(s); }
-inline bool column_staged(int64_t s) { return staged_lds_bytes(s) + kStaticLds <= kLdsBudget; }
-
-int64_t lds_max_samples() {
-    int64_t s = 2;
-    while (column_staged(s + 1)) ++s;
-    return s;
-}
-
-__device__ inline double ll_of(uint32_t bits) { return log((double)__uint_as_float(bits)); }
-
-// rank-th smallest (0-based) of the S keys: MSB-first 8-bit radix select with an LDS histogram per digit
-__device__ uint32_t radix_select(const uint32_t* v, int s, int rank, uint32_t* hist, uint32_t* wave_tot, uint32_t* found) {
-    uint32_t prefix = 0, mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[threadIdx.x] = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < s; i += kElpdBlock) {
-            const uint32_t u = v[i];
-            if ((u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 0xFF], 1u);
-        }
-        __syncthreads();
-        // exclusive prefix sum over the 256 bins: one bin per thread, a wave scan, then the wave totals
-        const uint32_t own = hist[threadIdx.x];
-        uint32_t inc = own;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)inc, o, 64);
-            if (lane >= o) inc += up;
-        }
-        if (lane == 63) wave_tot[wave] = inc;
-        __syncthreads();
-        uint32_t base = 0;
-        for (int w = 0; w < wave; ++w) base += wave_tot[w];
-        const uint32_t lo = base + inc - own, hi = base + inc;
-        if ((uint32_t)rank >= lo && (uint32_t)rank < hi) { found[0] = (uint32_t)threadIdx.x; found[1] = lo; }
-        __syncthreads();
-        prefix |= found[0] << shift;
-        mask |= 0xFFu << shift;
-        rank -= (int)found[1];
-        __syncthreads();
-    }
-    return prefix;
-}
+using ElpdKey = psis_key_plain;                      // equal likelihoods are interchangeable here: the bit pattern alone is sorted
 
 struct ElpdArgs {
     const float* lh;          // store: [M][cap]
@@ -91,180 +33,22 @@ struct ElpdArgs {
     int* bad;                 // device word: count of columns holding a value that is not positive and finite
 };
 
-__global__ __launch_bounds__(kElpdBlock) void k_elpd_column(ElpdArgs a) {
+__global__ __launch_bounds__(kPsisBlock) void k_elpd_column(ElpdArgs a) {
     extern __shared__ __align__(16) unsigned char dyn[];
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t ured[kElpdWaves], found[2], n_cand;
-    __shared__ double red[kElpdWaves];
-    __shared__ double fit_b[kMaxM], fit_k[kMaxM], fit_ls[kMaxM], fit_w[kMaxM];
-    __shared__ double fit_post[1];                  // b_post
+    __shared__ PsisScratch sc;
     const int64_t j = a.j0 + blockIdx.x;
-    const int s = a.s, tid = threadIdx.x;
     const uint32_t* g = reinterpret_cast<const uint32_t*>(a.lh + (int64_t)a.cols[j] * a.cap + a.burn);
-    double* ary = reinterpret_cast<double*>(dyn);                            // [tail_p] tail exceedances
-    uint32_t* keys = reinterpret_cast<uint32_t*>(ary + a.tail_p);            // [tail_p] candidate bit patterns
-    uint32_t* staged = keys + a.tail_p;                                      // [S] when staged
-
-    // 1. stage, min, data check
-    uint32_t umin = 0xFFFFFFFFu, bad = 0;
-    for (int i = tid; i < s; i += kElpdBlock) {
-        const uint32_t u = g[i];
-        if (a.staged) staged[i] = u;
-        bad |= (u == 0u || u >= 0x7F800000u);        // zero, negative (sign bit), inf, NaN
-        umin = min(umin, u);
-    }
-    umin = unit_block_reduce<kElpdWaves>(umin, ured, unit_min{});
-    bad = unit_block_reduce<kElpdWaves>(bad, ured, unit_max{});
-    const uint32_t* v = a.staged ? staged : g;
-    if (bad) {                                       // (uniform over the block)
-        if (tid == 0) {
-            atomicAdd(a.bad, 1);
-            for (int q = 0; q < 4; ++q) a.out[q * a.n_kept + j] = NAN;
-        }
+    const PsisColumn c = psis_column<ElpdKey>(g, a.s, a.tail_n, a.tail_p, a.staged != 0, dyn, sc, psis_no_sink{});
+    if (threadIdx.x != 0) return;
+    if (c.bad) {
+        atomicAdd(a.bad, 1);
+        for (int q = 0; q < 4; ++q) a.out[q * a.n_kept + j] = NAN;
         return;
     }
-    const double ll_min = ll_of(umin);               // max(-ll) = -ll_min
-
-    // 2. sum ll, sum lh
-    double sum_ll = 0.0, sum_lh = 0.0;
-    for (int i = tid; i < s; i += kElpdBlock) {
-        const uint32_t u = v[i];
-        sum_ll += ll_of(u);
-        sum_lh += (double)__uint_as_float(u);
-    }
-    sum_ll = unit_block_reduce<kElpdWaves>(sum_ll, red, unit_sum{});
-    sum_lh = unit_block_reduce<kElpdWaves>(sum_lh, red, unit_sum{});
-    const double mean = sum_ll / s;
-    const double lppd = log(sum_lh) - log((double)s);        // logsumexp(ll) - log S: float32 lh neither over- nor underflows
-
-    // 3. cutoff: the (T+1)-th smallest lh
-    const uint32_t ucut = radix_select(v, s, a.tail_n, hist, ured, found);
-    const double x_cut = -ll_of(ucut) + ll_min;              // x = -ll - max(-ll)
-    const double xcutoff = fmax(x_cut, log(2.2250738585072014e-308));   // (never binds for float32 data: x >= -192)
-    const double expxcutoff = exp(xcutoff);
-
-    // 4. candidates (lh < cutoff: at most T of them), sorted by lh ascending = x descending; pads sort last
-    if (tid == 0) n_cand = 0;
-    for (int i = tid; i < a.tail_p; i += kElpdBlock) keys[i] = 0xFFFFFFFFu;
-    __syncthreads();
-    for (int i = tid; i < s; i += kElpdBlock) {
-        const uint32_t u = v[i];
-        if (u < ucut) keys[atomicAdd(&n_cand, 1u)] = u;
-    }
-    __syncthreads();
-    const int nc = (int)n_cand;
-    for (int k = 2; k <= a.tail_p; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int i = tid; i < a.tail_p; i += kElpdBlock) {
-                const int p = i ^ jj;
-                if (p > i) {
-                    const uint32_t ki = keys[i], kp = keys[p];
-                    const bool up = (i & k) == 0;
-                    if ((ki > kp) == up) { keys[i] = kp; keys[p] = ki; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // x-ascending position t of candidate keys[nc - 1 - t]; the tail is the x > xcutoff suffix (all candidates here)
-    double in_tail = 0.0;
-    for (int t = tid; t < nc; t += kElpdBlock) in_tail += (-ll_of(keys[nc - 1 - t]) + ll_min) > xcutoff;
-    const int tail_len = (int)unit_block_reduce<kElpdWaves>(in_tail, red, unit_sum{});
-    const int t0 = nc - tail_len;                            // x-ascending index of the first tail element
-
-    // 5. _gpdfit on the exceedances exp(x) - exp(cutoff), ascending
-    double k_hat = INFINITY, sigma = 0.0;
-    const int n = tail_len;
-    if (n > 4) {
-        for (int i = tid; i < n; i += kElpdBlock) {
-            const double x = -ll_of(keys[nc - 1 - (t0 + i)]) + ll_min;
-            ary[i] = exp(x) - expxcutoff;
-        }
-        __syncthreads();
-        const int m = 30 + (int)sqrt((double)n);
-        const double q = 3 * ary[(int)(n / 4.0 + 0.5) - 1], inv_last = 1 / ary[n - 1];
-        const int lane = tid & 63, wave = tid >> 6;
-        for (int c = wave; c < m; c += kElpdWaves) {          // k_ary[c] = mean(log1p(-b[c] * ary)): one wave per candidate
-            double b = 1 - sqrt(m / ((double)(c + 1) - 0.5));
-            b /= q;
-            b += inv_last;
-            double acc = 0.0;
-            for (int i = lane; i < n; i += 64) acc += log1p(-b * ary[i]);
-            acc = unit_wave_reduce(acc, unit_sum{});
-            if (lane == 0) { fit_b[c] = b; fit_k[c] = acc / n; }
-        }
-        __syncthreads();
-        if (tid < m) fit_ls[tid] = n * (log(-(fit_b[tid] / fit_k[tid])) - fit_k[tid] - 1);
-        __syncthreads();
-        if (tid < m) {
-            double z = 0.0;
-            for (int c = 0; c < m; ++c) z += exp(fit_ls[c] - fit_ls[tid]);
-            fit_w[tid] = 1 / z;
-        }
-        __syncthreads();
-        if (tid == 0) {                                       // prune negligible weights (NaN included), normalise, posterior b
-            double wsum = 0.0;
-            for (int c = 0; c < m; ++c) if (fit_w[c] >= 10 * 2.220446049250313e-16) wsum += fit_w[c];
-            double b_post = 0.0;
-            for (int c = 0; c < m; ++c) if (fit_w[c] >= 10 * 2.220446049250313e-16) b_post += fit_b[c] * (fit_w[c] / wsum);
-            fit_post[0] = b_post;
-        }
-        __syncthreads();
-        const double b_post = fit_post[0];
-        double acc = 0.0;
-        for (int i = tid; i < n; i += kElpdBlock) acc += log1p(-b_post * ary[i]);
-        const double k_post = unit_block_reduce<kElpdWaves>(acc, red, unit_sum{}) / n;
-        sigma = -k_post / b_post;
-        k_hat = (n * k_post + 10 * 0.5) / (n + 10);
-    }
-
-    // the tail's terms of logsumexp(x') and logsumexp(x' + ll): smoothed (_gpinv, clamped to 0) when k is finite
-    const bool smooth = n > 4 && isfinite(k_hat);
-    double a_tail = 0.0, b_tail = 0.0;
-    for (int i = tid; i < n; i += kElpdBlock) {
-        const double ll = ll_of(keys[nc - 1 - (t0 + i)]);
-        double x = -ll + ll_min;
-        if (smooth) {
-            const double p = (0.5 + i) / n;
-            double gq = NAN;                                   // _gpinv: NaN when sigma <= 0, not repaired
-            if (!(sigma <= 0)) {
-                gq = fabs(k_hat) < 2.220446049250313e-16 ? -log1p(-p) : expm1(-k_hat * log1p(-p)) / k_hat;
-                gq *= sigma;
-            }
-            x = log(gq + expxcutoff);
-            if (x > 0) x = 0;
-        }
-        a_tail += exp(x);
-        b_tail += exp(x + ll);
-    }
-
-    // 6. variance about the mean; the body's terms (lh >= cutoff, and candidates at or below xcutoff)
-    double var = 0.0, a_body = 0.0, b_body = 0.0;
-    for (int i = tid; i < s; i += kElpdBlock) {
-        const uint32_t u = v[i];
-        const double ll = ll_of(u);
-        var += (ll - mean) * (ll - mean);
-        if (u >= ucut) {
-            const double x = -ll + ll_min;
-            a_body += exp(x);
-            b_body += exp(x + ll);
-        }
-    }
-    for (int t = tid; t < t0; t += kElpdBlock) {
-        const double ll = ll_of(keys[nc - 1 - t]);
-        const double x = -ll + ll_min;
-        a_body += exp(x);
-        b_body += exp(x + ll);
-    }
-    var = unit_block_reduce<kElpdWaves>(var, red, unit_sum{}) / s;
-    const double a_all = unit_block_reduce<kElpdWaves>(a_body + a_tail, red, unit_sum{});
-    const double b_all = unit_block_reduce<kElpdWaves>(b_body + b_tail, red, unit_sum{});
-    if (tid == 0) {
-        a.out[j] = log(b_all) - log(a_all);                   // logsumexp(x' - logsumexp(x') + ll)
-        a.out[a.n_kept + j] = k_hat;
-        a.out[2 * a.n_kept + j] = lppd;
-        a.out[3 * a.n_kept + j] = var;
-    }
+    a.out[j] = c.loo;
+    a.out[a.n_kept + j] = c.k_hat;
+    a.out[2 * a.n_kept + j] = c.lppd;
+    a.out[3 * a.n_kept + j] = c.var;
 }
 
 // NA rule of elpd.py:31 without a mask: keep[m] = 0 where every stored row is isclose(lh, 1); one wave per column
@@ -330,7 +114,7 @@ int sbe_elpd_abi_version(void) { return SBE_ELPD_ABI_VERSION; }
 const char* sbe_elpd_last_error(const sbe_elpd_store* st) { return unit_last_error(st); }
 
 int64_t sbe_elpd_lds_max_samples(void) {
-    static const int64_t v = lds_max_samples();
+    static const int64_t v = psis_lds_max_samples<ElpdKey>();
     return v;
 }
 
@@ -478,16 +262,16 @@ int sbe_elpd_compute(sbe_elpd_store* st, int64_t burn_rows, const uint8_t* na_va
         if (keep[m]) cols.push_back((int32_t)m);
     const int64_t nk = (int64_t)cols.size();
     if (nk == 0) return SBE_OK;
-    const bool staged = column_staged(s);
-    const int tn = tail_count(s), tp = pow2_at_least(std::max(tn, 1));
-    const size_t lds = (staged ? (size_t)s * sizeof(uint32_t) : 0) + tail_lds_bytes(s);
-    HIPCHK(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kStaticLds)));
+    const bool staged = psis_column_staged<ElpdKey>(s);
+    const int tn = psis_tail_count(s), tp = pow2_at_least(std::max(tn, 1));
+    const size_t lds = (staged ? (size_t)s * sizeof(uint32_t) : 0) + psis_tail_lds_bytes<ElpdKey>(s);
+    HIPCHK(st, hipFuncSetAttribute((const void*)k_elpd_column, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget - kPsisStaticLds)));
     HIPCHK(st, hipMemcpyAsync(st->d_cols, cols.data(), (size_t)nk * sizeof(int32_t), hipMemcpyHostToDevice, st->stream));
     HIPCHK(st, hipMemsetAsync(st->d_bad, 0, sizeof(int), st->stream));
     int rc = unit_timed(st, [&] {
         return unit_for_grid_chunks(nk, [&](int64_t j0, int64_t columns) {   // one workgroup per kept column
             const ElpdArgs args{st->d_lh, st->d_cols, st->cap, burn_rows, (int)s, tn, tp, staged ? 1 : 0, st->d_out, nk, j0, st->d_bad};
-            k_elpd_column<<<(unsigned)columns, kElpdBlock, lds, st->stream>>>(args);
+            k_elpd_column<<<(unsigned)columns, kPsisBlock, lds, st->stream>>>(args);
             HIPCHK(st, hipGetLastError());
             return SBE_OK;
         });
