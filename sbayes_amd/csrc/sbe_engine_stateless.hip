@@ -141,7 +141,9 @@ int sbe_normalize_weights(sbe_engine* e, const float* weights, int n_comp, const
     if (rc) return rc;
     const void *v_w = e->d_scratch, *v_hc;
     const size_t w_lds = (size_t)F * C * sizeof(float);
-    const bool in_lds = w_lds <= ((size_t)64 << 10);              // (beyond that the blocks read the device copy in place)
+    // (beyond the budget the blocks read the device copy in place; the kernel's static part counts: 64 KB of weights next to
+    //  it would ask for more than the 64 KB a block is granted without hipFuncAttributeMaxDynamicSharedMemorySize)
+    const bool in_lds = w_lds + kNwStaticLds <= ((size_t)64 << 10);
     if (N <= 256 && in_lds) rc = stage(e, weights, w_lds, e->d_scratch, &v_w);
     else rc = upload(e, e->d_scratch, weights, w_lds);
     if (rc) return rc;

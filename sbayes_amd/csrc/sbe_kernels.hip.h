@@ -476,6 +476,7 @@ static __global__ void k_scatter_weight_patterns(const uint8_t* __restrict__ bas
 // operands: the same bits), so nobody sorts patterns and the call is ONE launch.  Block = 8 rows; the [F][C] weights
 // and the block's has_components rows are read once into LDS (both may live in host-mapped staging memory).
 constexpr int kNwRows = 8;
+constexpr size_t kNwStaticLds = kNwRows * sizeof(uint32_t);    // `bits` below: counted in the launcher's LDS budget
 static __global__ void k_normalize_weight_rows(const float* __restrict__ weights /* [F][C] */,
                                         const uint8_t* __restrict__ has_components /* [N][C] */,
                                         float* __restrict__ out /* [N][F][C] */, int N, int F, int C, int stage_weights,
