@@ -37,7 +37,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, predict
+from . import _handle, _samples, predict
 from ._handle import _ptr, c_handle_p
 from .predict import NA
 
@@ -66,13 +66,6 @@ def sample_bytes(n_objects, n_features, n_states, n_components, n_clusters, n_ro
     """Device bytes one sample of an evaluate call takes while the call runs (sbe_contrib_sample_bytes)."""
     n, f, k = int(n_objects), int(n_features), int(n_clusters)
     return predict.sample_bytes(n, f, n_states, n_components, k, n_rows) + 8 * k * n * f + 8 * k * (n + f)
-
-
-def _write_rows(path, header, rows):
-    with open(path, "w") as f:
-        f.write("\t".join(header) + "\n")
-        for row in rows:
-            f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
 
 
 @dataclass
@@ -153,61 +146,27 @@ class ContributionResult:
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)
         paths = [directory / "clusters.tsv", directory / "membership.tsv"]
-        _write_rows(paths[0], *self.cluster_table())
-        _write_rows(paths[1], *self.membership_table(object_names))
+        _samples.write_tsv(paths[0], *self.cluster_table())
+        _samples.write_tsv(paths[1], *self.membership_table(object_names))
         for k in range(self.gain_feature.shape[1]):
             paths.append(directory / f"features_a{k}.tsv")
-            _write_rows(paths[-1], *self.feature_table(k, feature_names))
+            _samples.write_tsv(paths[-1], *self.feature_table(k, feature_names))
         return paths
 
 
-class ContributionHandle(_handle.UnitHandle):
+class ContributionHandle(_samples.SampleHandle):
     """Owner of one sbe_contrib handle: the data on one device.  evaluate() appends the rows of its samples; result() returns
     them.  last_kernel_ms(): the kernels of the last library call of evaluate()."""
     _prefix, _noun = "sbe_contrib", "a cluster contribution handle"
-
-    def __init__(self, device=None):
-        self.shape = None                                    # (N, F, S, C, K, R) once the data is set
-        self._clear()
-        self._create_on(load, device)
 
     def _clear(self):
         self._rows = {"affinity": [], "gain_feature": [], "member": []}
         self.n_samples, self.n_skipped, self.kernel_ms, self.n_calls = 0, 0, 0.0, 0
 
-    def set_data(self, codes, groups, n_groups, n_states, n_clusters):
-        """codes uint8 [N,F] (255 = NA); groups uint8 [C-1,N] (255 = none) with n_groups[c] groups each.  Forgets the rows."""
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        if codes.ndim != 2:
-            raise ValueError(f"codes must be [N, F], got shape {codes.shape}")
-        N, F = codes.shape
-        n_groups = [int(g) for g in n_groups]
-        C = len(n_groups) + 1
-        groups = np.ascontiguousarray(groups, dtype=np.uint8).reshape(C - 1, -1) if C > 1 else np.zeros((0, N), dtype=np.uint8)
-        if groups.shape != (C - 1, N):
-            raise ValueError(f"groups must be [{C - 1}, {N}], got shape {groups.shape}")
-        S, K = int(n_states), int(n_clusters)
-        R = predict._check_shape(N, F, S, C, K, n_groups)
-        counts = np.ascontiguousarray(n_groups, dtype=np.intc)
-        self.shape = None
-        self._check(self._lib.sbe_contrib_set_data(self._h, N, F, S, C, K, _ptr(codes), _ptr(groups) if C > 1 else None,
-                                                   _ptr(counts) if C > 1 else None))
-        self.shape = (N, F, S, C, K, R)
-        self._clear()
-
-    def _with_data(self):
-        if self.shape is None:
-            raise ValueError("no data yet (set_data)")
-        return self.shape
-
     def reset(self):
         """Forget the rows of the samples evaluated so far, keep the data."""
         self._with_data()
         self._clear()
-
-    def set_feature_tile(self, features):
-        """Features per workgroup tile (0: the default); no output depends on it."""
-        self._check(self._lib.sbe_contrib_set_feature_tile(self._h, int(features)))
 
     def max_samples(self) -> int:
         """The samples one library call holds."""
@@ -217,21 +176,10 @@ class ContributionHandle(_handle.UnitHandle):
         """Evaluate samples: clusters uint8 [T,K,N] of 0 / 1, weights float64 [T,F,C], tables float64 [T,R,F,S].  Blocks beyond
         max_samples() go in several library calls; each call validates its samples before it writes anything, so an
         EngineError leaves the rows of the calls before it appended."""
-        N, F, S, C, K, R = self._with_data()
-        clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-        T = clusters.shape[0]
-        if clusters.shape != (T, K, N) or weights.shape != (T, F, C) or tables.shape != (T, R, F, S):
-            raise ValueError(f"{T} samples take clusters {(T, K, N)}, weights {(T, F, C)} and tables {(T, R, F, S)}; got {clusters.shape}, "
-                             f"{weights.shape}, {tables.shape}")
-        step = self.max_samples()
-        if step < 1:
-            raise ValueError(f"one sample takes {sample_bytes(N, F, S, C, K, R)} bytes on the device, a call holds {MAX_STAGE_BYTES}")
-        clusters = np.ascontiguousarray(clusters, dtype=np.uint8)
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        _T, blocks = self._blocks(clusters, weights, tables)
+        N, F, _S, _C, K, _R = self.shape
         self.kernel_ms = 0.0
-        for t0 in range(0, T, step):
-            cl, w, tb = clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step]
+        for _t0, cl, w, tb in blocks:
             n = cl.shape[0]
             affinity, gain = np.empty((n, K, N)), np.empty((n, K, F))
             skipped = ct.c_int64(0)
@@ -257,43 +205,24 @@ def cluster_contribution(codes, groups, clusters, weights, tables, burnin=0.1, n
     """The per-cluster evidence of T logged samples after burn-in.  codes uint8 [N,F]; groups: uint8 [C-1,N] group indices (with
     n_groups) or a list of bool [G_c,N] assignments; clusters uint8 [T,K,N]; weights [T,F,C]; tables [T,R,F,S].  The labels are
     taken as logged (align them first), and a member's affinity is optimistic (its data shaped the cluster's effect draw)."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([predict.group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = predict._check_burnin(burnin, clusters.shape[0])
+    groups, n_groups, clusters, weights, tables, _u = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups)
     h = ContributionHandle(device)
     try:
         h.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1])
-        h.evaluate(clusters[burn:], weights[burn:], tables[burn:])
+        h.evaluate(clusters, weights, tables)
         return h.result()
     finally:
         h.close()
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.contribution",
-                                 description="Per-cluster evidence of an sBayes run's logged samples: the likelihood gain of every cluster per "
-                                             "feature, and every object's affinity to every cluster (labels as logged: align them first; a "
-                                             "member's affinity is optimistic)")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
+    ap = _samples.run_parser("python -m sbayes_amd.contribution",
+                             "Per-cluster evidence of an sBayes run's logged samples: the likelihood gain of every cluster per "
+                             "feature, and every object's affinity to every cluster (labels as logged: align them first; a "
+                             "member's affinity is optimistic)")
     ap.add_argument("--out", type=Path, default=None, help="directory for clusters.tsv, membership.tsv and features_a<k>.tsv")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    data = predict.read_data(args.features, args.feature_states, args.confounders)
-    weights, tables = predict.read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = predict.read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     res = cluster_contribution(data["codes"], data["groups"], clusters, weights, tables, burnin=args.burnin, n_groups=n_groups, device=args.device)
     print(f"{res.n_samples} samples, {res.gain_feature.shape[1]} clusters (labels as logged), {res.n_skipped} entries skipped")
     for k, mean, sd, size in res.cluster_table()[1]:

@@ -151,35 +151,18 @@ __global__ __launch_bounds__(kBlock) void k_contrib_sum_features(const double* d
 
 }  // namespace
 
-struct sbe_contrib : sbe_unit_handle {
-    bool has_data = false;
-    int64_t N = 0;
-    int F = 0, S = 0, C = 0, K = 0, R = 0;
-    int row_off[kMaxC] = {};
-    int forced_tile = 0;                // 0: the default
-    uint8_t* d_codes = nullptr;         // [N][F]
-    size_t codes_bytes = 0;
-    uint8_t* d_groups = nullptr;        // [C-1][N]
-    size_t groups_bytes = 0;
-    unsigned long long* d_words = nullptr;   // [0]: n_skipped of the call, [1]: the first offender's key
-    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
-    size_t clusters_bytes = 0;
-    double* d_weights = nullptr;        // [n][F][C]
-    size_t weights_bytes = 0;
-    double* d_tables = nullptr;         // [n][R][F][S]
-    size_t tables_bytes = 0;
-    uint16_t* d_kid = nullptr;          // [n][N]
-    size_t kid_bytes = 0;
+struct sbe_contrib : sbe_unit_handle, sample_store {
+    // d_words: [0]: n_skipped of the call, [1]: the first offender's key
     double* d_d = nullptr;              // [n][K][N][F]
     size_t d_bytes = 0;
     double* d_sums = nullptr;           // gain_feature [n][K][F], then affinity [n][K][N]
     size_t sums_bytes = 0;
-    std::vector<void*> buffers() const { return {d_codes, d_groups, d_words, d_clusters, d_weights, d_tables, d_kid, d_d, d_sums}; }
+    std::vector<void*> buffers() const { return buffers_with({d_d, d_sums}); }
 };
 
 namespace {
 
-constexpr char kNullHandle[] = "null handle";
+constexpr char kPrefix[] = "sbe_contrib";
 
 int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R) {
     return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + 8 * (int64_t)K * N * F + 8 * (int64_t)K * (N + F);
@@ -205,107 +188,43 @@ int64_t sbe_contrib_sample_bytes(int64_t n_objects, int64_t n_features, int n_st
                : 0;
 }
 
-int sbe_contrib_set_feature_tile(sbe_contrib* h, int features) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
-    h->forced_tile = features;
-    return SBE_OK;
-}
+int sbe_contrib_set_feature_tile(sbe_contrib* h, int features) { return set_feature_tile(h, features); }
 
 int sbe_contrib_set_data(sbe_contrib* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups) {
     CHECK_HANDLE(h, kNullHandle);
     int row_off[kMaxC], R;
     if (const int bad = check_data(h, N, F, S, C, K, codes, groups, n_groups, row_off, R)) return bad;
-    h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
-    if (!rc) rc = unit_ensure(h, h->d_groups, h->groups_bytes, std::max<size_t>(1, (size_t)(C - 1) * (size_t)N));
-    if (!rc) rc = unit_ensure(h, h->d_words, 2 * sizeof(unsigned long long));
-    if (!rc) rc = copy_pieces(h, h->d_codes, codes, (size_t)(N * F), hipMemcpyHostToDevice);
-    if (!rc && C > 1) rc = copy_pieces(h, h->d_groups, groups, (size_t)(C - 1) * (size_t)N, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->N = N;
-    h->F = (int)F;
-    h->S = S;
-    h->C = C;
-    h->K = K;
-    h->R = R;
-    std::copy(row_off, row_off + kMaxC, h->row_off);
-    h->has_data = true;
-    return SBE_OK;
+    return h->upload(h, N, F, S, C, K, R, row_off, codes, groups, no_hook, [&] { return wait_for_stream(h); });
 }
 
 int sbe_contrib_evaluate(sbe_contrib* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables, double* affinity,
                          double* gain_feature, int64_t* n_skipped_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_contrib_set_data comes first)");
+    if (!h->has_data) return no_data(h, kPrefix);
     if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
     if (n == 0) {
         if (n_skipped_out) *n_skipped_out = 0;
         return SBE_OK;
     }
-    if (!clusters || !weights || !tables)
-        return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
     const int64_t N = h->N, F = h->F, cells = N * F;
-    const int S = h->S, C = h->C, K = h->K, R = h->R;
-    const int64_t per_sample = sample_bytes(N, F, S, C, K, R);
-    if (n > SBE_CONTRIB_MAX_STAGE_BYTES / per_sample)
-        return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
-                    (long long)n, (long long)per_sample, (long long)SBE_CONTRIB_MAX_STAGE_BYTES, (long long)(SBE_CONTRIB_MAX_STAGE_BYTES / per_sample));
-    int Ft;
-    size_t lds;
-    if (const int bad = plan_tile(h, h->forced_tile, F, R, S, C, Ft, lds)) return bad;
-    HIPCHK(h, hipSetDevice(h->device));
+    const int K = h->K;
     const bool sums = affinity || gain_feature;
-    const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
     const size_t gain_count = (size_t)n * K * (size_t)F, aff_count = (size_t)n * K * (size_t)N;
-    int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_weights, h->weights_bytes, w_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_tables, h->tables_bytes, t_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_kid, h->kid_bytes, (size_t)n * N * sizeof(uint16_t));
-    if (!rc && sums) rc = unit_ensure(h, h->d_d, h->d_bytes, (size_t)n * K * (size_t)cells * sizeof(double));
-    if (!rc && sums) rc = unit_ensure(h, h->d_sums, h->sums_bytes, (gain_count + aff_count) * sizeof(double));
-    if (!rc) rc = copy_pieces(h, h->d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_weights, weights, w_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
+    SamplePlan plan;
+    int rc = h->stage(h, n, clusters, weights, tables, sample_bytes(N, F, h->S, h->C, K, h->R), SBE_CONTRIB_MAX_STAGE_BYTES, h->d_words + 1, [&] {
+        if (!sums) return SBE_OK;
+        const int own = unit_ensure(h, h->d_d, h->d_bytes, (size_t)n * K * (size_t)cells * sizeof(double));
+        return own ? own : unit_ensure(h, h->d_sums, h->sums_bytes, (gain_count + aff_count) * sizeof(double));
+    }, no_hook, plan);
     if (rc) return rc;
-    unsigned long long* d_err = h->d_words + 1;
-    if ((rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, h->d_clusters, h->d_weights, h->d_tables, h->d_kid, d_err))) return rc;
-    unsigned long long key = kNoError;
-    HIPCHK(h, hipMemcpyAsync(&key, d_err, sizeof key, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (key != kNoError) return data_error(h, key, (int)F, S, C);
 
     HIPCHK(h, hipMemsetAsync(h->d_words, 0, sizeof(unsigned long long), h->stream));
     CellArgs args{};
-    args.codes = h->d_codes;
-    args.groups = h->d_groups;
-    args.weights = h->d_weights;
-    args.tables = h->d_tables;
+    h->fill(args, n, plan);
     args.d = sums ? h->d_d : nullptr;
     args.n_skipped = h->d_words;
-    args.N = N;
-    args.F = (int)F;
-    args.S = S;
-    args.C = C;
-    args.R = R;
     args.K = K;
-    args.n = (int)n;
-    args.Ft = Ft;
-    args.Nt = kBlock / Ft;
-    args.f_tiles = div_up(F, Ft);
-    std::copy(h->row_off, h->row_off + kMaxC, args.row_off);
-    const CellKernel kernel = cell_kernel(C);
-    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    const int64_t blocks = (int64_t)args.f_tiles * ((N + args.Nt - 1) / args.Nt);
-    rc = unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
-        args.block0 = first;
-        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-        return SBE_OK;
-    });
-    if (rc) return rc;
+    if ((rc = launch_tiles(h, cell_kernel(h->C), args, plan.lds))) return rc;
     double* d_gain = h->d_sums;
     double* d_affinity = h->d_sums + gain_count;
     if (gain_feature) {

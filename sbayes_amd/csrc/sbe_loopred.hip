@@ -227,19 +227,12 @@ RowKernel acc_kernel(int S, int C) {
 
 }  // namespace
 
-struct sbe_loopred : sbe_unit_handle {
-    bool has_data = false, weighted = false;
-    int64_t N = 0, M = 0, cap = 0;
-    int F = 0, S = 0, C = 0, K = 0, R = 0;
-    int row_off[kMaxC] = {};
-    int forced_tile = 0;
+struct sbe_loopred : sbe_unit_handle, sample_store {
+    bool weighted = false;
+    int64_t M = 0, cap = 0;
     int64_t n_rows = 0;                 // T so far
     int64_t next_t = 0;                 // phase 3: the samples accumulated
     int cur = 0;                        // which of the two sums buffers holds the sums
-    uint8_t* d_codes = nullptr;         // [N][F]
-    size_t codes_bytes = 0;
-    uint8_t* d_groups = nullptr;        // [C-1][N]
-    size_t groups_bytes = 0;
     int32_t* d_cells = nullptr;         // [M]: the cell of a column
     size_t cells_bytes = 0;
     int32_t* d_col = nullptr;           // [N F]: the column of a cell, -1: NA
@@ -252,28 +245,17 @@ struct sbe_loopred : sbe_unit_handle {
     size_t w_bytes = 0;
     double* d_out = nullptr;            // [3][M]
     size_t out_bytes = 0;
-    unsigned long long* d_words = nullptr;   // [0]: the first offender's key, [1]: phase 2's and phase 3's first offender
-    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
-    size_t clusters_bytes = 0;
-    double* d_weights = nullptr;        // [n][F][C]
-    size_t weights_bytes = 0;
-    double* d_tables = nullptr;         // [n][R][F][S]
-    size_t tables_bytes = 0;
-    uint16_t* d_kid = nullptr;          // [n][N]
-    size_t kid_bytes = 0;
     float* d_lik = nullptr;             // staging [n][N F]
     size_t lik_bytes = 0;
-    std::vector<void*> buffers() const {
-        return {d_codes, d_groups, d_cells, d_col, d_p, d_lh, d_w, d_out, d_words, d_clusters, d_weights, d_tables, d_kid, d_lik};
-    }
+    // d_words: [0]: the first offender's key, [1]: phase 2's and phase 3's first offender
+    std::vector<void*> buffers() const { return buffers_with({d_cells, d_col, d_p, d_lh, d_w, d_out, d_lik}); }
     size_t p_doubles() const { return (size_t)N * F * S; }
     double* sums(int which) const { return d_p + (size_t)which * p_doubles(); }
 };
 
 namespace {
 
-constexpr char kNullHandle[] = "null handle";
-constexpr char kNoData[] = "no data yet (sbe_loopred_set_data comes first)";
+constexpr char kPrefix[] = "sbe_loopred";
 
 int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R) {
     return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + 4 * N * F;
@@ -290,63 +272,17 @@ int forget_rows(sbe_loopred* h) {
     return SBE_OK;
 }
 
-// The part add and accumulate share: the argument checks of n samples, the tile, the samples onto the device, ids and validation
-// (between them the handle's first event), the offender's key read.  On SBE_OK args holds what sbe_predict_row.hip.h reads.
+// The part add and accumulate share: the store's opening of a call over n samples with the staging rows of the likelihood; on
+// SBE_OK args holds what sbe_predict_row.hip.h reads.
 int stage_samples(sbe_loopred* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables, RowArgs& args, size_t& lds) {
-    if (!clusters || !weights || !tables)
-        return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
-    const int64_t N = h->N, F = h->F;
-    const int S = h->S, C = h->C, K = h->K, R = h->R;
-    const int64_t per_sample = sample_bytes(N, F, S, C, K, R);
-    if (n > SBE_LOOPRED_MAX_STAGE_BYTES / per_sample)
-        return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
-                    (long long)n, (long long)per_sample, (long long)SBE_LOOPRED_MAX_STAGE_BYTES, (long long)(SBE_LOOPRED_MAX_STAGE_BYTES / per_sample));
-    int Ft;
-    if (const int bad = plan_tile(h, h->forced_tile, F, R, S, C, Ft, lds)) return bad;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
-    int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_weights, h->weights_bytes, w_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_tables, h->tables_bytes, t_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_kid, h->kid_bytes, (size_t)n * N * sizeof(uint16_t));
-    if (!rc) rc = unit_ensure(h, h->d_lik, h->lik_bytes, (size_t)n * N * F * sizeof(float));
-    if (!rc) rc = copy_pieces(h, h->d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_weights, weights, w_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
+    SamplePlan plan;
+    const int rc = h->stage(h, n, clusters, weights, tables, sample_bytes(h->N, h->F, h->S, h->C, h->K, h->R), SBE_LOOPRED_MAX_STAGE_BYTES, h->d_words,
+                            [&] { return unit_ensure(h, h->d_lik, h->lik_bytes, (size_t)n * h->N * h->F * sizeof(float)); }, no_hook, plan);
     if (rc) return rc;
-    if ((rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, h->d_clusters, h->d_weights, h->d_tables, h->d_kid, h->d_words))) return rc;
-    unsigned long long key = kNoError;
-    HIPCHK(h, hipMemcpyAsync(&key, h->d_words, sizeof key, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (key != kNoError) return data_error(h, key, (int)F, S, C);
     args = RowArgs{};
-    args.codes = h->d_codes;
-    args.groups = h->d_groups;
-    args.kid = h->d_kid;
-    args.weights = h->d_weights;
-    args.tables = h->d_tables;
-    args.N = N;
-    args.F = (int)F;
-    args.S = S;
-    args.C = C;
-    args.R = R;
-    args.n = (int)n;
-    args.Ft = Ft;
-    args.Nt = kBlock / Ft;
-    args.f_tiles = div_up(F, Ft);
-    std::copy(h->row_off, h->row_off + kMaxC, args.row_off);
+    h->fill(args, n, plan);
+    lds = plan.lds;
     return SBE_OK;
-}
-
-int launch_tiles(sbe_loopred* h, RowKernel kernel, RowArgs& args, size_t lds) {
-    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    const int64_t blocks = (int64_t)args.f_tiles * ((args.N + args.Nt - 1) / args.Nt);
-    return unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
-        args.block0 = first;
-        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-        return SBE_OK;
-    });
 }
 
 }  // namespace
@@ -378,12 +314,7 @@ int64_t sbe_loopred_lds_max_samples(void) {
     return v;
 }
 
-int sbe_loopred_set_feature_tile(sbe_loopred* h, int features) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
-    h->forced_tile = features;
-    return SBE_OK;
-}
+int sbe_loopred_set_feature_tile(sbe_loopred* h, int features) { return set_feature_tile(h, features); }
 
 int sbe_loopred_set_data(sbe_loopred* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups,
                          int64_t capacity) {
@@ -402,47 +333,37 @@ int sbe_loopred_set_data(sbe_loopred* h, int64_t N, int64_t F, int S, int C, int
     if (store_bytes(M, capacity) > SBE_LOOPRED_MAX_STORE_BYTES)
         return fail(h, SBE_ERR_ARG, "the rows and weights of %lld observed cells x %lld samples take %lld bytes on the device, the limit is %lld",
                     (long long)M, (long long)capacity, (long long)store_bytes(M, capacity), (long long)SBE_LOOPRED_MAX_STORE_BYTES);
-    h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t store = std::max<size_t>(1, (size_t)M * (size_t)capacity);
-    int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
-    if (!rc) rc = unit_ensure(h, h->d_groups, h->groups_bytes, std::max<size_t>(1, (size_t)(C - 1) * (size_t)N));
-    if (!rc) rc = unit_ensure(h, h->d_cells, h->cells_bytes, std::max<size_t>(1, (size_t)M) * sizeof(int32_t));
-    if (!rc) rc = unit_ensure(h, h->d_col, h->col_bytes, (size_t)(N * F) * sizeof(int32_t));
-    if (!rc) rc = unit_ensure(h, h->d_p, h->p_bytes, 2 * (size_t)(N * F * S) * sizeof(double));
-    if (!rc) rc = unit_ensure(h, h->d_lh, h->lh_bytes, store * sizeof(float));
-    if (!rc) rc = unit_ensure(h, h->d_w, h->w_bytes, store * sizeof(double));
-    if (!rc) rc = unit_ensure(h, h->d_out, h->out_bytes, 3 * std::max<size_t>(1, (size_t)M) * sizeof(double));
-    if (!rc) rc = unit_ensure(h, h->d_words, 2 * sizeof(unsigned long long));
-    if (!rc) rc = copy_pieces(h, h->d_codes, codes, (size_t)(N * F), hipMemcpyHostToDevice);
-    if (!rc && C > 1) rc = copy_pieces(h, h->d_groups, groups, (size_t)(C - 1) * (size_t)N, hipMemcpyHostToDevice);
-    if (!rc && M > 0) rc = copy_pieces(h, h->d_cells, cells.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_col, col.data(), (size_t)(N * F) * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (rc) return rc;
-    h->N = N;
-    h->F = (int)F;
-    h->S = S;
-    h->C = C;
-    h->K = K;
-    h->R = R;
-    h->M = M;
-    h->cap = capacity;
-    std::copy(row_off, row_off + kMaxC, h->row_off);
-    if ((rc = forget_rows(h))) return rc;                 // (waits for the copies too: `cells` and `col` live until here)
-    h->has_data = true;
-    return SBE_OK;
+    return h->upload(
+        h, N, F, S, C, K, R, row_off, codes, groups,
+        [&] {
+            int rc = unit_ensure(h, h->d_cells, h->cells_bytes, std::max<size_t>(1, (size_t)M) * sizeof(int32_t));
+            if (!rc) rc = unit_ensure(h, h->d_col, h->col_bytes, (size_t)(N * F) * sizeof(int32_t));
+            if (!rc) rc = unit_ensure(h, h->d_p, h->p_bytes, 2 * (size_t)(N * F * S) * sizeof(double));
+            if (!rc) rc = unit_ensure(h, h->d_lh, h->lh_bytes, store * sizeof(float));
+            if (!rc) rc = unit_ensure(h, h->d_w, h->w_bytes, store * sizeof(double));
+            if (!rc) rc = unit_ensure(h, h->d_out, h->out_bytes, 3 * std::max<size_t>(1, (size_t)M) * sizeof(double));
+            if (!rc && M > 0) rc = copy_pieces(h, h->d_cells, cells.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice);
+            if (!rc) rc = copy_pieces(h, h->d_col, col.data(), (size_t)(N * F) * sizeof(int32_t), hipMemcpyHostToDevice);
+            return rc;
+        },
+        [&] {
+            h->M = M;
+            h->cap = capacity;
+            return forget_rows(h);                            // (waits for the copies too: `cells` and `col` live until here)
+        });
 }
 
 int sbe_loopred_reset(sbe_loopred* h) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     HIPCHK(h, hipSetDevice(h->device));
     return forget_rows(h);
 }
 
 int sbe_loopred_add(sbe_loopred* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
     if (n == 0) return SBE_OK;
     if (h->n_rows + n > h->cap)
@@ -471,7 +392,7 @@ int sbe_loopred_add(sbe_loopred* h, int64_t n, const uint8_t* clusters, const do
 
 int sbe_loopred_weights(sbe_loopred* h, double* loo_i, double* k_i, double* n_eff) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     if (!loo_i || !k_i || !n_eff) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !loo_i ? "loo_i" : !k_i ? "k_i" : "n_eff");
     const int64_t s = h->n_rows, M = h->M;
     if (s < SBE_ELPD_MIN_SAMPLES)
@@ -512,7 +433,7 @@ int sbe_loopred_weights(sbe_loopred* h, double* loo_i, double* k_i, double* n_ef
 
 int sbe_loopred_accumulate(sbe_loopred* h, int64_t t0, int64_t n, const uint8_t* clusters, const double* weights, const double* tables) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     if (!h->weighted) return fail(h, SBE_ERR_STATE, "no weights yet (sbe_loopred_weights comes before sbe_loopred_accumulate)");
     if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
     if (t0 != h->next_t || t0 + n > h->n_rows)
@@ -548,7 +469,7 @@ int sbe_loopred_accumulate(sbe_loopred* h, int64_t t0, int64_t n, const uint8_t*
 
 int sbe_loopred_read(sbe_loopred* h, double* p_loo, int64_t* n_samples_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     if (!n_samples_out) return fail(h, SBE_ERR_ARG, "null pointer argument: n_samples_out");
     HIPCHK(h, hipSetDevice(h->device));
     if (p_loo) {
@@ -561,7 +482,7 @@ int sbe_loopred_read(sbe_loopred* h, double* p_loo, int64_t* n_samples_out) {
 
 int sbe_loopred_get_store(sbe_loopred* h, float* lik, double* w) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "%s", kNoData);
+    if (!h->has_data) return no_data(h, kPrefix);
     if (w && !h->weighted) return fail(h, SBE_ERR_STATE, "no weights yet (sbe_loopred_weights comes first)");
     if (h->M == 0 || h->n_rows == 0) return SBE_OK;
     HIPCHK(h, hipSetDevice(h->device));

@@ -187,25 +187,8 @@ __global__ __launch_bounds__(kBlock) void k_ppc_sum_features(const double* d, in
 
 }  // namespace
 
-struct sbe_ppc : sbe_unit_handle {
-    bool has_data = false;
-    int64_t N = 0;
-    int F = 0, S = 0, C = 0, K = 0, R = 0;
-    int row_off[kMaxC] = {};
-    int forced_tile = 0;                // 0: the default
-    uint8_t* d_codes = nullptr;         // [N][F]
-    size_t codes_bytes = 0;
-    uint8_t* d_groups = nullptr;        // [C-1][N]
-    size_t groups_bytes = 0;
-    unsigned long long* d_words = nullptr;   // [0]: n_skipped of the call, [1]: the first offender's key
-    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
-    size_t clusters_bytes = 0;
-    double* d_weights = nullptr;        // [n][F][C]
-    size_t weights_bytes = 0;
-    double* d_tables = nullptr;         // [n][R][F][S]
-    size_t tables_bytes = 0;
-    uint16_t* d_kid = nullptr;          // [n][N]
-    size_t kid_bytes = 0;
+struct sbe_ppc : sbe_unit_handle, sample_store {
+    // d_words: [0]: n_skipped of the call, [1]: the first offender's key
     double* d_uniforms = nullptr;       // [n][N F]
     size_t uniforms_bytes = 0;
     uint8_t* d_y = nullptr;             // [n][N][F]
@@ -216,14 +199,12 @@ struct sbe_ppc : sbe_unit_handle {
     size_t sums_bytes = 0;
     int* d_counts = nullptr;            // [n][F][S]
     size_t counts_bytes = 0;
-    std::vector<void*> buffers() const {
-        return {d_codes, d_groups, d_words, d_clusters, d_weights, d_tables, d_kid, d_uniforms, d_y, d_d, d_sums, d_counts};
-    }
+    std::vector<void*> buffers() const { return buffers_with({d_uniforms, d_y, d_d, d_sums, d_counts}); }
 };
 
 namespace {
 
-constexpr char kNullHandle[] = "null handle";
+constexpr char kPrefix[] = "sbe_ppc";
 
 int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R, bool y_rep, bool uniforms) {
     return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + 16 * N * F + 16 * F + 16 * N + 4 * F * S + (y_rep ? N * F : 0) +
@@ -251,104 +232,62 @@ int64_t sbe_ppc_sample_bytes(int64_t n_objects, int64_t n_features, int n_states
                : 0;
 }
 
-int sbe_ppc_set_feature_tile(sbe_ppc* h, int features) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
-    h->forced_tile = features;
-    return SBE_OK;
-}
+int sbe_ppc_set_feature_tile(sbe_ppc* h, int features) { return set_feature_tile(h, features); }
 
 int sbe_ppc_set_data(sbe_ppc* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups) {
     CHECK_HANDLE(h, kNullHandle);
     int row_off[kMaxC], R;
     if (const int bad = check_data(h, N, F, S, C, K, codes, groups, n_groups, row_off, R)) return bad;
-    h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
-    if (!rc) rc = unit_ensure(h, h->d_groups, h->groups_bytes, std::max<size_t>(1, (size_t)(C - 1) * (size_t)N));
-    if (!rc) rc = unit_ensure(h, h->d_words, 2 * sizeof(unsigned long long));
-    if (!rc) rc = copy_pieces(h, h->d_codes, codes, (size_t)(N * F), hipMemcpyHostToDevice);
-    if (!rc && C > 1) rc = copy_pieces(h, h->d_groups, groups, (size_t)(C - 1) * (size_t)N, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->N = N;
-    h->F = (int)F;
-    h->S = S;
-    h->C = C;
-    h->K = K;
-    h->R = R;
-    std::copy(row_off, row_off + kMaxC, h->row_off);
-    h->has_data = true;
-    return SBE_OK;
+    return h->upload(h, N, F, S, C, K, R, row_off, codes, groups, no_hook, [&] { return wait_for_stream(h); });
 }
 
 int sbe_ppc_check(sbe_ppc* h, int64_t n, int64_t first_draw, uint64_t seed, const uint8_t* clusters, const double* weights, const double* tables,
                   const double* uniforms, uint8_t* y_rep, double* dev_feature, double* dev_object, int32_t* count_rep, int64_t* n_skipped_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_ppc_set_data comes first)");
+    if (!h->has_data) return no_data(h, kPrefix);
     if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
     if (first_draw < 0) return fail(h, SBE_ERR_ARG, "first_draw=%lld is negative", (long long)first_draw);
     if (n == 0) {
         if (n_skipped_out) *n_skipped_out = 0;
         return SBE_OK;
     }
-    if (!clusters || !weights || !tables)
-        return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
     const int64_t N = h->N, F = h->F, cells = N * F;
-    const int S = h->S, C = h->C, K = h->K, R = h->R;
-    const int64_t per_sample = sample_bytes(N, F, S, C, K, R, y_rep != nullptr, uniforms != nullptr);
-    if (n > SBE_PPC_MAX_STAGE_BYTES / per_sample)
-        return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
-                    (long long)n, (long long)per_sample, (long long)SBE_PPC_MAX_STAGE_BYTES, (long long)(SBE_PPC_MAX_STAGE_BYTES / per_sample));
-    int Ft;
-    size_t lds;
-    if (const int bad = plan_tile(h, h->forced_tile, F, R, S, C, Ft, lds)) return bad;
-    HIPCHK(h, hipSetDevice(h->device));
+    const int S = h->S;
     const bool sums = dev_feature || dev_object;
-    const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
     const size_t u_bytes = (size_t)n * cells * sizeof(double), c_bytes = (size_t)n * F * S * sizeof(int);
-    int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_weights, h->weights_bytes, w_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_tables, h->tables_bytes, t_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_kid, h->kid_bytes, (size_t)n * N * sizeof(uint16_t));
-    if (!rc && uniforms) rc = unit_ensure(h, h->d_uniforms, h->uniforms_bytes, u_bytes);
-    if (!rc && y_rep) rc = unit_ensure(h, h->d_y, h->y_bytes, (size_t)n * cells);
-    if (!rc && sums) rc = unit_ensure(h, h->d_d, h->d_bytes, 2 * u_bytes);
-    if (!rc && sums) rc = unit_ensure(h, h->d_sums, h->sums_bytes, (size_t)n * 2 * (size_t)(F + N) * sizeof(double));
-    if (!rc && count_rep) rc = unit_ensure(h, h->d_counts, h->counts_bytes, c_bytes);
-    if (!rc) rc = copy_pieces(h, h->d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_weights, weights, w_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
-    if (!rc && uniforms) rc = copy_pieces(h, h->d_uniforms, uniforms, u_bytes, hipMemcpyHostToDevice);
-    if (rc) return rc;
     unsigned long long* d_err = h->d_words + 1;
-    if ((rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, h->d_clusters, h->d_weights, h->d_tables, h->d_kid, d_err))) return rc;
-    if (uniforms) {
-        rc = unit_for_grid_chunks(div_up(n * cells, kBlock), [&](int64_t first, int64_t count) {
-            k_ppc_validate_uniforms<<<(unsigned)count, kBlock, 0, h->stream>>>(h->d_uniforms, n, cells, d_err, first);
-            HIPCHK(h, hipGetLastError());
-            return SBE_OK;
-        });
-        if (rc) return rc;
-    }
-    unsigned long long key = kNoError;
-    HIPCHK(h, hipMemcpyAsync(&key, d_err, sizeof key, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (key != kNoError) {
-        if ((int)((key >> 36) & 15) != kUniform) return data_error(h, key, (int)F, S, C);
-        const long long at = (long long)(key & ((1ull << 36) - 1));
-        return fail(h, SBE_ERR_DATA, "sample %lld: uniforms[%lld] (object %lld, feature %lld) is outside [0, 1) or not finite", (long long)(key >> 40), at,
-                    at / (long long)F, at % (long long)F);
+    SamplePlan plan;
+    int rc = h->stage(
+        h, n, clusters, weights, tables, sample_bytes(N, F, S, h->C, h->K, h->R, y_rep != nullptr, uniforms != nullptr), SBE_PPC_MAX_STAGE_BYTES, d_err,
+        [&] {
+            int own = uniforms ? unit_ensure(h, h->d_uniforms, h->uniforms_bytes, u_bytes) : SBE_OK;
+            if (!own && y_rep) own = unit_ensure(h, h->d_y, h->y_bytes, (size_t)n * cells);
+            if (!own && sums) own = unit_ensure(h, h->d_d, h->d_bytes, 2 * u_bytes);
+            if (!own && sums) own = unit_ensure(h, h->d_sums, h->sums_bytes, (size_t)n * 2 * (size_t)(F + N) * sizeof(double));
+            if (!own && count_rep) own = unit_ensure(h, h->d_counts, h->counts_bytes, c_bytes);
+            if (!own && uniforms) own = copy_pieces(h, h->d_uniforms, uniforms, u_bytes, hipMemcpyHostToDevice);
+            return own;
+        },
+        [&] {
+            if (!uniforms) return SBE_OK;
+            return unit_for_grid_chunks(div_up(n * cells, kBlock), [&](int64_t first, int64_t count) {
+                k_ppc_validate_uniforms<<<(unsigned)count, kBlock, 0, h->stream>>>(h->d_uniforms, n, cells, d_err, first);
+                HIPCHK(h, hipGetLastError());
+                return SBE_OK;
+            });
+        },
+        plan);
+    if (rc) return rc;
+    if (plan.key != kNoError) {                                // (kUniform: the other kinds are worded by the store)
+        const long long at = (long long)(plan.key & ((1ull << 36) - 1));
+        return fail(h, SBE_ERR_DATA, "sample %lld: uniforms[%lld] (object %lld, feature %lld) is outside [0, 1) or not finite", (long long)(plan.key >> 40),
+                    at, at / (long long)F, at % (long long)F);
     }
 
     HIPCHK(h, hipMemsetAsync(h->d_words, 0, sizeof(unsigned long long), h->stream));
     if (count_rep) HIPCHK(h, hipMemsetAsync(h->d_counts, 0, c_bytes, h->stream));
     DrawArgs args{};
-    args.codes = h->d_codes;
-    args.groups = h->d_groups;
-    args.kid = h->d_kid;
-    args.weights = h->d_weights;
-    args.tables = h->d_tables;
+    h->fill(args, n, plan);
     args.uniforms = uniforms ? h->d_uniforms : nullptr;
     args.y_rep = y_rep ? h->d_y : nullptr;
     args.d = sums ? h->d_d : nullptr;
@@ -356,26 +295,7 @@ int sbe_ppc_check(sbe_ppc* h, int64_t n, int64_t first_draw, uint64_t seed, cons
     args.n_skipped = h->d_words;
     args.seed = seed;
     args.first_draw = first_draw;
-    args.N = N;
-    args.F = (int)F;
-    args.S = S;
-    args.C = C;
-    args.R = R;
-    args.n = (int)n;
-    args.Ft = Ft;
-    args.Nt = kBlock / Ft;
-    args.f_tiles = div_up(F, Ft);
-    std::copy(h->row_off, h->row_off + kMaxC, args.row_off);
-    const DrawKernel kernel = draw_kernel(S, C);
-    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    const int64_t blocks = (int64_t)args.f_tiles * ((N + args.Nt - 1) / args.Nt);
-    rc = unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
-        args.block0 = first;
-        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-        return SBE_OK;
-    });
-    if (rc) return rc;
+    if ((rc = launch_tiles(h, draw_kernel(S, h->C), args, plan.lds))) return rc;
     double* d_feature = h->d_sums;
     double* d_object = h->d_sums + (size_t)n * 2 * (size_t)F;
     if (dev_feature) {

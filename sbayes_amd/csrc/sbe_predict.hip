@@ -127,31 +127,14 @@ AccKernel acc_kernel(int S, int C) {
 
 }  // namespace
 
-struct sbe_predict : sbe_unit_handle {
-    bool has_data = false;
-    int64_t N = 0;
-    int F = 0, S = 0, C = 0, K = 0, R = 0;
-    int row_off[kMaxC] = {};
-    int forced_tile = 0;                // 0: the default
+struct sbe_predict : sbe_unit_handle, sample_store {
     int64_t n_samples = 0;
-    uint8_t* d_codes = nullptr;         // [N][F]
-    size_t codes_bytes = 0;
-    uint8_t* d_groups = nullptr;        // [C-1][N]
-    size_t groups_bytes = 0;
     double* d_acc = nullptr;            // pred_sum [N][F][S], then resp_sum [N][F][C]
     size_t acc_bytes = 0;
-    unsigned long long* d_words = nullptr;   // [0]: n_zero, [1]: the first offender's key
-    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
-    size_t clusters_bytes = 0;
-    double* d_weights = nullptr;        // [n][F][C]
-    size_t weights_bytes = 0;
-    double* d_tables = nullptr;         // [n][R][F][S]
-    size_t tables_bytes = 0;
-    uint16_t* d_kid = nullptr;          // [n][N]
-    size_t kid_bytes = 0;
     float* d_lik = nullptr;             // [n][N F]
     size_t lik_bytes = 0;
-    std::vector<void*> buffers() const { return {d_codes, d_groups, d_acc, d_words, d_clusters, d_weights, d_tables, d_kid, d_lik}; }
+    // d_words: [0]: n_zero, [1]: the first offender's key
+    std::vector<void*> buffers() const { return buffers_with({d_acc, d_lik}); }
     double* pred() const { return d_acc; }
     double* resp() const { return d_acc + (size_t)N * F * S; }
     size_t acc_doubles() const { return (size_t)N * F * (S + C); }
@@ -159,7 +142,7 @@ struct sbe_predict : sbe_unit_handle {
 
 namespace {
 
-constexpr char kNullHandle[] = "null handle";
+constexpr char kPrefix[] = "sbe_predict";
 
 int64_t sample_bytes(int64_t N, int64_t F, int S, int C, int K, int R, bool lik) {
     return (int64_t)K * N + 8 * F * C + 8 * (int64_t)R * F * S + 2 * N + (lik ? 4 * N * F : 0);
@@ -193,108 +176,43 @@ int64_t sbe_predict_sample_bytes(int64_t n_objects, int64_t n_features, int n_st
                : 0;
 }
 
-int sbe_predict_set_feature_tile(sbe_predict* h, int features) {
-    CHECK_HANDLE(h, kNullHandle);
-    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
-    h->forced_tile = features;
-    return SBE_OK;
-}
+int sbe_predict_set_feature_tile(sbe_predict* h, int features) { return set_feature_tile(h, features); }
 
 int sbe_predict_set_data(sbe_predict* h, int64_t N, int64_t F, int S, int C, int K, const uint8_t* codes, const uint8_t* groups, const int* n_groups) {
     CHECK_HANDLE(h, kNullHandle);
     int row_off[kMaxC], R;
     if (const int bad = check_data(h, N, F, S, C, K, codes, groups, n_groups, row_off, R)) return bad;
-    h->has_data = false;                                  // (a failed allocation or copy leaves a handle without data)
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_codes, h->codes_bytes, (size_t)(N * F));
-    if (!rc) rc = unit_ensure(h, h->d_groups, h->groups_bytes, std::max<size_t>(1, (size_t)(C - 1) * (size_t)N));
-    if (!rc) rc = unit_ensure(h, h->d_acc, h->acc_bytes, (size_t)(N * F * (S + C)) * sizeof(double));
-    if (!rc) rc = unit_ensure(h, h->d_words, 2 * sizeof(unsigned long long));
-    if (!rc) rc = copy_pieces(h, h->d_codes, codes, (size_t)(N * F), hipMemcpyHostToDevice);
-    if (!rc && C > 1) rc = copy_pieces(h, h->d_groups, groups, (size_t)(C - 1) * (size_t)N, hipMemcpyHostToDevice);
-    if (rc) return rc;
-    h->N = N;
-    h->F = (int)F;
-    h->S = S;
-    h->C = C;
-    h->K = K;
-    h->R = R;
-    std::copy(row_off, row_off + kMaxC, h->row_off);
-    if ((rc = zero_accumulators(h))) return rc;          // (waits for the copies too)
-    h->has_data = true;
-    return SBE_OK;
+    return h->upload(h, N, F, S, C, K, R, row_off, codes, groups,
+                     [&] { return unit_ensure(h, h->d_acc, h->acc_bytes, (size_t)(N * F * (S + C)) * sizeof(double)); },
+                     [&] { return zero_accumulators(h); });               // (waits for the copies too)
 }
 
 int sbe_predict_reset(sbe_predict* h) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    if (!h->has_data) return no_data(h, kPrefix);
     HIPCHK(h, hipSetDevice(h->device));
     return zero_accumulators(h);
 }
 
 int sbe_predict_accumulate(sbe_predict* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables, float* lik_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    if (!h->has_data) return no_data(h, kPrefix);
     if (n < 0) return fail(h, SBE_ERR_ARG, "n=%lld is negative", (long long)n);
     if (n == 0) return SBE_OK;
-    if (!clusters || !weights || !tables)
-        return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
     const int64_t N = h->N, F = h->F;
-    const int S = h->S, C = h->C, K = h->K, R = h->R;
-    const int64_t per_sample = sample_bytes(N, F, S, C, K, R, lik_out != nullptr);
-    if (n > SBE_PREDICT_MAX_STAGE_BYTES / per_sample)
-        return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
-                    (long long)n, (long long)per_sample, (long long)SBE_PREDICT_MAX_STAGE_BYTES, (long long)(SBE_PREDICT_MAX_STAGE_BYTES / per_sample));
-    int Ft;
-    size_t lds;
-    if (const int bad = plan_tile(h, h->forced_tile, F, R, S, C, Ft, lds)) return bad;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
-    int rc = unit_ensure(h, h->d_clusters, h->clusters_bytes, cl_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_weights, h->weights_bytes, w_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_tables, h->tables_bytes, t_bytes);
-    if (!rc) rc = unit_ensure(h, h->d_kid, h->kid_bytes, (size_t)n * N * sizeof(uint16_t));
-    if (!rc && lik_out) rc = unit_ensure(h, h->d_lik, h->lik_bytes, (size_t)n * N * F * sizeof(float));
-    if (!rc) rc = copy_pieces(h, h->d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_weights, weights, w_bytes, hipMemcpyHostToDevice);
-    if (!rc) rc = copy_pieces(h, h->d_tables, tables, t_bytes, hipMemcpyHostToDevice);
+    SamplePlan plan;
+    int rc = h->stage(h, n, clusters, weights, tables, sample_bytes(N, F, h->S, h->C, h->K, h->R, lik_out != nullptr), SBE_PREDICT_MAX_STAGE_BYTES,
+                      h->d_words + 1, [&] { return lik_out ? unit_ensure(h, h->d_lik, h->lik_bytes, (size_t)n * N * F * sizeof(float)) : SBE_OK; },
+                      no_hook, plan);
     if (rc) return rc;
-    unsigned long long* d_err = h->d_words + 1;
-    if ((rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, h->d_clusters, h->d_weights, h->d_tables, h->d_kid, d_err))) return rc;
-    unsigned long long key = kNoError;
-    HIPCHK(h, hipMemcpyAsync(&key, d_err, sizeof key, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (key != kNoError) return data_error(h, key, (int)F, S, C);
 
     AccArgs args{};
-    args.codes = h->d_codes;
-    args.groups = h->d_groups;
-    args.kid = h->d_kid;
-    args.weights = h->d_weights;
-    args.tables = h->d_tables;
+    h->fill(args, n, plan);
     args.pred = h->pred();
     args.resp = h->resp();
     args.lik = lik_out ? h->d_lik : nullptr;
     args.n_zero = h->d_words;
-    args.N = N;
-    args.F = (int)F;
-    args.S = S;
-    args.C = C;
-    args.R = R;
-    args.n = (int)n;
-    args.Ft = Ft;
-    args.Nt = kBlock / Ft;
-    args.f_tiles = div_up(F, Ft);
-    std::copy(h->row_off, h->row_off + kMaxC, args.row_off);
-    const AccKernel kernel = acc_kernel(S, C);
-    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    const int64_t blocks = (int64_t)args.f_tiles * ((N + args.Nt - 1) / args.Nt);
-    rc = unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
-        args.block0 = first;
-        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
-        HIPCHK(h, hipGetLastError());
-        return SBE_OK;
-    });
+    rc = launch_tiles(h, acc_kernel(h->S, h->C), args, plan.lds);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     if (lik_out) rc = copy_pieces(h, lik_out, h->d_lik, (size_t)n * N * F * sizeof(float), hipMemcpyDeviceToHost);
@@ -306,7 +224,7 @@ int sbe_predict_accumulate(sbe_predict* h, int64_t n, const uint8_t* clusters, c
 
 int sbe_predict_read(sbe_predict* h, double* pred_sum, double* resp_sum, int64_t* n_samples_out, int64_t* n_zero_out) {
     CHECK_HANDLE(h, kNullHandle);
-    if (!h->has_data) return fail(h, SBE_ERR_STATE, "no data yet (sbe_predict_set_data comes first)");
+    if (!h->has_data) return no_data(h, kPrefix);
     if (!n_samples_out || !n_zero_out) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !n_samples_out ? "n_samples_out" : "n_zero_out");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = SBE_OK;

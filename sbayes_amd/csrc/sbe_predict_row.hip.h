@@ -1,12 +1,17 @@
 #pragma once
 // sbe_predict_row.hip.h -- the mixture row of a cell, m_t[n,f,.], written once for the units that put the logged samples back
-// on the data: the posterior predictive (sbe_predict.hip), the posterior predictive check (sbe_ppc.hip) and the per-cluster
-// evidence (sbe_contrib.hip).  All take the data
-// and a sample of include/sbe_predict.h word for word, so they share what reads them: the checks of the data's arguments, the
-// ids kernel, the validation kernel with the offender's key, the plan of the feature tile, the staging of a sample's slice
+// on the data: the posterior predictive (sbe_predict.hip), the posterior predictive check (sbe_ppc.hip), the per-cluster
+// evidence (sbe_contrib.hip) and the leave-one-out predictive (sbe_loopred.hip).  All take the data
+// and a sample of include/sbe_predict.h word for word, so they share what reads them.  Device side: the
+// ids kernel, the validation kernel with the offender's key, the staging of a sample's slice
 // into one of two LDS buffers and the w~ / m arithmetic of a cell.  A unit's kernel
 // calls, per workgroup, tile_cell and cell_group once and, per sample, stage_slice, cell_weights and cell_state
 // (sbe_contrib.hip: cell_weights_in_and_out, cell_state and cell_state_in, the object placed in every cluster and in none).
+// Host side: the checks of the data's arguments, the plan of the feature tile, the messages of the offender's key, and the
+// sample store, which a unit's handle derives from: the data and the samples of the call in flight on the device, the whole of
+// <prefix>_set_feature_tile, the device part of <prefix>_set_data (upload), the opening of a compute call up to the offender's
+// key (stage), the common fields of a kernel's argument struct (fill), the tile launch (launch_tiles) and the "no data yet"
+// message.  A unit keeps its own checks, buffers, sample_bytes and what follows the key; DESIGN.md section 7.1.
 // Everything lives in an unnamed namespace, as the unit layer does: every unit compiles its own copy.
 #include <hip/hip_runtime.h>
 
@@ -296,20 +301,6 @@ int plan_tile(H* h, int forced, int64_t F, int R, int S, int C, int& Ft, size_t&
     return SBE_OK;
 }
 
-// The first two kernels of a call over n samples held on the device: ids, validation (the unit adds its own before it reads
-// the key).  d_err is set to kNoError first.
-template <class H>
-int launch_ids_and_validation(H* h, int64_t n, int64_t N, int64_t F, int S, int C, int K, int R, const uint8_t* d_clusters, const double* d_weights,
-                              const double* d_tables, uint16_t* d_kid, unsigned long long* d_err) {
-    HIPCHK(h, hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    k_predict_ids<<<(unsigned)div_up(n * N, kBlock), kBlock, 0, h->stream>>>(d_clusters, n, N, K, d_kid, d_err);
-    HIPCHK(h, hipGetLastError());
-    k_predict_validate<<<(unsigned)div_up(n * F * (1 + R), kBlock), kBlock, 0, h->stream>>>(d_weights, d_tables, n, (int)F, S, C, R, d_err);
-    HIPCHK(h, hipGetLastError());
-    return SBE_OK;
-}
-
 // the message of a validation failure of one of the six kinds of include/sbe_predict.h
 template <class H>
 int data_error(H* h, unsigned long long key, int F, int S, int C) {
@@ -324,6 +315,178 @@ int data_error(H* h, unsigned long long key, int F, int S, int C) {
     case kTableRowEmpty: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld has no positive entry", t, at / F, at % F);
     default: return fail(h, SBE_ERR_DATA, "sample %lld: table row %lld, feature %lld sums further than %g from 1", t, at / F, at % F, SBE_PREDICT_SUM_TOL);
     }
+}
+
+// The first two kernels of a call over n samples held on the device: ids, validation (the unit adds its own before it reads
+// the key).  d_err is set to kNoError first.
+template <class H>
+int launch_ids_and_validation(H* h, int64_t n, int64_t N, int64_t F, int S, int C, int K, int R, const uint8_t* d_clusters, const double* d_weights,
+                              const double* d_tables, uint16_t* d_kid, unsigned long long* d_err) {
+    HIPCHK(h, hipMemsetAsync(d_err, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    k_predict_ids<<<(unsigned)div_up(n * N, kBlock), kBlock, 0, h->stream>>>(d_clusters, n, N, K, d_kid, d_err);
+    HIPCHK(h, hipGetLastError());
+    k_predict_validate<<<(unsigned)div_up(n * F * (1 + R), kBlock), kBlock, 0, h->stream>>>(d_weights, d_tables, n, (int)F, S, C, R, d_err);
+    HIPCHK(h, hipGetLastError());
+    return SBE_OK;
+}
+
+// ---- host side: the sample store -----------------------------------------------------------------------------------------------
+constexpr char kNullHandle[] = "null handle";
+
+// the state message of a call that needs data; prefix: "sbe_<unit>"
+template <class H>
+int no_data(H* h, const char* prefix) { return fail(h, SBE_ERR_STATE, "no data yet (%s_set_data comes first)", prefix); }
+
+inline int no_hook() { return SBE_OK; }
+
+template <class H>
+int wait_for_stream(H* h) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SBE_OK;
+}
+
+// what stage() leaves for a call's launches; key: kNoError, or an offender of kind kUniform, which is the unit's to word
+struct SamplePlan {
+    int Ft = 0;                         // features of a tile
+    size_t lds = 0;                     // of the two slices
+    unsigned long long key = kNoError;
+};
+
+// The data and the samples of the call in flight, as every unit of this header holds them.  A unit's handle derives from it
+// beside sbe_unit_handle and lists its pointers through buffers_with(its own).  The methods take the handle for its stream,
+// its events and its error message.
+struct sample_store {
+    bool has_data = false;
+    int64_t N = 0;
+    int F = 0, S = 0, C = 0, K = 0, R = 0;
+    int row_off[kMaxC] = {};
+    int forced_tile = 0;                // 0: the default
+    uint8_t* d_codes = nullptr;         // [N][F]
+    size_t codes_bytes = 0;
+    uint8_t* d_groups = nullptr;        // [C-1][N]
+    size_t groups_bytes = 0;
+    unsigned long long* d_words = nullptr;   // two words; the unit's handle says what each holds (one is stage()'s d_err)
+    uint8_t* d_clusters = nullptr;      // the samples of the call in flight: [n][K][N]
+    size_t clusters_bytes = 0;
+    double* d_weights = nullptr;        // [n][F][C]
+    size_t weights_bytes = 0;
+    double* d_tables = nullptr;         // [n][R][F][S]
+    size_t tables_bytes = 0;
+    uint16_t* d_kid = nullptr;          // [n][N]
+    size_t kid_bytes = 0;
+
+    std::vector<void*> buffers_with(std::initializer_list<void*> own) const {
+        std::vector<void*> all{d_codes, d_groups, d_words, d_clusters, d_weights, d_tables, d_kid};
+        all.insert(all.end(), own.begin(), own.end());
+        return all;
+    }
+
+    // The device part of <prefix>_set_data, after check_data and the unit's own checks: the data and the two words onto the
+    // device, own() (the unit's allocations and copies), the shape, last() (the unit's zeroing; it waits for the stream).  A
+    // failure leaves a handle without data.
+    template <class H, class Own, class Last>
+    int upload(H* h, int64_t n_objects, int64_t n_features, int n_states, int n_components, int n_clusters, int n_rows, const int (&offsets)[kMaxC],
+               const uint8_t* codes, const uint8_t* groups, Own own, Last last) {
+        has_data = false;
+        HIPCHK(h, hipSetDevice(h->device));
+        const size_t code_bytes = (size_t)(n_objects * n_features), group_bytes = (size_t)(n_components - 1) * (size_t)n_objects;
+        int rc = unit_ensure(h, d_codes, codes_bytes, code_bytes);
+        if (!rc) rc = unit_ensure(h, d_groups, groups_bytes, std::max<size_t>(1, group_bytes));
+        if (!rc) rc = unit_ensure(h, d_words, 2 * sizeof(unsigned long long));
+        if (!rc) rc = copy_pieces(h, d_codes, codes, code_bytes, hipMemcpyHostToDevice);
+        if (!rc && n_components > 1) rc = copy_pieces(h, d_groups, groups, group_bytes, hipMemcpyHostToDevice);
+        if (!rc) rc = own();
+        if (rc) return rc;
+        N = n_objects;
+        F = (int)n_features;
+        S = n_states;
+        C = n_components;
+        K = n_clusters;
+        R = n_rows;
+        std::copy(offsets, offsets + kMaxC, row_off);
+        if ((rc = last())) return rc;
+        has_data = true;
+        return SBE_OK;
+    }
+
+    // The opening of a compute call over n > 0 samples: the argument checks, the tile, the samples onto the device, extra() (the
+    // unit's allocations and copies), ids and validation (before them the handle's first event), validate() (the unit's own
+    // validation, reported through d_err as well), the offender's key read.  per_sample, max_stage: the unit's bytes per sample
+    // and its limit.  On SBE_OK the samples stand on the device and `plan` is set.
+    template <class H, class Extra, class Validate>
+    int stage(H* h, int64_t n, const uint8_t* clusters, const double* weights, const double* tables, int64_t per_sample, int64_t max_stage,
+              unsigned long long* d_err, Extra extra, Validate validate, SamplePlan& plan) {
+        if (!clusters || !weights || !tables)
+            return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !clusters ? "clusters" : !weights ? "weights" : "tables");
+        if (n > max_stage / per_sample)
+            return fail(h, SBE_ERR_ARG, "n=%lld samples of %lld bytes each exceed the %lld bytes one call holds on the device (at most %lld samples per call here)",
+                        (long long)n, (long long)per_sample, (long long)max_stage, (long long)(max_stage / per_sample));
+        if (const int bad = plan_tile(h, forced_tile, F, R, S, C, plan.Ft, plan.lds)) return bad;
+        HIPCHK(h, hipSetDevice(h->device));
+        const size_t cl_bytes = (size_t)n * K * N, w_bytes = (size_t)n * F * C * sizeof(double), t_bytes = (size_t)n * R * F * S * sizeof(double);
+        int rc = unit_ensure(h, d_clusters, clusters_bytes, cl_bytes);
+        if (!rc) rc = unit_ensure(h, d_weights, weights_bytes, w_bytes);
+        if (!rc) rc = unit_ensure(h, d_tables, tables_bytes, t_bytes);
+        if (!rc) rc = unit_ensure(h, d_kid, kid_bytes, (size_t)n * N * sizeof(uint16_t));
+        if (!rc) rc = copy_pieces(h, d_clusters, clusters, cl_bytes, hipMemcpyHostToDevice);
+        if (!rc) rc = copy_pieces(h, d_weights, weights, w_bytes, hipMemcpyHostToDevice);
+        if (!rc) rc = copy_pieces(h, d_tables, tables, t_bytes, hipMemcpyHostToDevice);
+        if (!rc) rc = extra();
+        if (!rc) rc = launch_ids_and_validation(h, n, N, F, S, C, K, R, d_clusters, d_weights, d_tables, d_kid, d_err);
+        if (!rc) rc = validate();
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(&plan.key, d_err, sizeof plan.key, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (plan.key != kNoError && (int)((plan.key >> 36) & 15) != kUniform) return data_error(h, plan.key, F, S, C);
+        return SBE_OK;
+    }
+
+    // the fields of a kernel's argument struct that the device part of this header reads (kid: where the struct has it)
+    template <class G>
+    void fill(G& g, int64_t n, const SamplePlan& plan) const {
+        g.codes = d_codes;
+        g.groups = d_groups;
+        set_kid(g, 0);
+        g.weights = d_weights;
+        g.tables = d_tables;
+        g.N = N;
+        g.F = F;
+        g.S = S;
+        g.C = C;
+        g.R = R;
+        g.n = (int)n;
+        g.Ft = plan.Ft;
+        g.Nt = kBlock / plan.Ft;
+        g.f_tiles = div_up(F, plan.Ft);
+        std::copy(row_off, row_off + kMaxC, g.row_off);
+    }
+    template <class G>
+    auto set_kid(G& g, int) const -> decltype((void)g.kid) { g.kid = d_kid; }
+    template <class G>
+    void set_kid(G&, long) const {}
+};
+
+// the whole of <prefix>_set_feature_tile
+template <class H>
+int set_feature_tile(H* h, int features) {
+    CHECK_HANDLE(h, kNullHandle);
+    if (features < 0 || features > kMaxTile) return fail(h, SBE_ERR_ARG, "features=%d out of range [0, %d]", features, kMaxTile);
+    h->forced_tile = features;
+    return SBE_OK;
+}
+
+// a kernel over the tiles of the data, in grid chunks; args: filled, its block0 is set per launch
+template <class H, class G>
+int launch_tiles(H* h, void (*kernel)(const G), G& args, size_t lds) {
+    HIPCHK(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+    const int64_t blocks = (int64_t)args.f_tiles * ((args.N + args.Nt - 1) / args.Nt);
+    return unit_for_grid_chunks(blocks, [&](int64_t first, int64_t count) {
+        args.block0 = first;
+        kernel<<<(unsigned)count, kBlock, lds, h->stream>>>(args);
+        HIPCHK(h, hipGetLastError());
+        return SBE_OK;
+    });
 }
 
 }  // namespace

@@ -41,7 +41,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, predict
+from . import _handle, _samples, predict
 from ._handle import _ptr, c_handle_p
 from .predict import NA, _check_burnin, _check_shape, group_index
 
@@ -205,11 +205,8 @@ class LooPredResult:
         out_dir = Path(out_dir)
         out_dir.mkdir(parents=True, exist_ok=True)
         paths = []
-        for name, (header, rows) in (("loo_predictive.tsv", self.table(feature_names, state_names)), ("loo_features.tsv", self.feature_table(feature_names))):
-            with open(out_dir / name, "w") as f:
-                f.write("\t".join(header) + "\n")
-                for row in rows:
-                    f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+        for name, table in (("loo_predictive.tsv", self.table(feature_names, state_names)), ("loo_features.tsv", self.feature_table(feature_names))):
+            _samples.write_tsv(out_dir / name, *table)
             paths.append(out_dir / name)
         return paths
 
@@ -227,16 +224,10 @@ def result_from(codes, p_loo, loo_i, k_i, n_eff, n_samples, kernel_ms=None) -> L
                          n_samples=int(n_samples), kernel_ms=kernel_ms)
 
 
-class LooPredHandle(_handle.UnitHandle):
+class LooPredHandle(_samples.SampleHandle):
     """Owner of one sbe_loopred handle: the data, the stored rows and weights and the sums on one device.  The phases in order:
     set_data(.., capacity), add(..) any number of times, weights(), accumulate(..) over the same samples again, result()."""
     _prefix, _noun = "sbe_loopred", "a leave-one-out predictive handle"
-
-    def __init__(self, device=None):
-        self.shape = None                                    # (N, F, S, C, K, R) once the data is set
-        self._codes = None
-        self._clear()
-        self._create_on(load, device)
 
     def _clear(self):
         self.n_rows, self.next_t, self._pointwise = 0, 0, None
@@ -244,34 +235,18 @@ class LooPredHandle(_handle.UnitHandle):
 
     def set_data(self, codes, groups, n_groups, n_states, n_clusters, capacity):
         """predict.PredictHandle.set_data's arguments and the number of samples the store takes."""
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        if codes.ndim != 2:
-            raise ValueError(f"codes must be [N, F], got shape {codes.shape}")
-        N, F = codes.shape
-        n_groups = [int(g) for g in n_groups]
-        C = len(n_groups) + 1
-        groups = np.ascontiguousarray(groups, dtype=np.uint8).reshape(C - 1, -1) if C > 1 else np.zeros((0, N), dtype=np.uint8)
-        if groups.shape != (C - 1, N):
-            raise ValueError(f"groups must be [{C - 1}, {N}], got shape {groups.shape}")
-        S, K, capacity = int(n_states), int(n_clusters), int(capacity)
-        R = _check_shape(N, F, S, C, K, n_groups)
-        if not 1 <= capacity <= MAX_SAMPLES:
-            raise ValueError(f"capacity={capacity}; the store takes 1 .. {MAX_SAMPLES} (2^20) samples")
-        M = int((codes != NA).sum())
-        if store_bytes(M, capacity) > MAX_STORE_BYTES:
-            raise ValueError(f"the rows and weights of {M} observed cells x {capacity} samples take {store_bytes(M, capacity)} bytes on the device, "
-                             f"the limit is {MAX_STORE_BYTES}")
-        counts = np.ascontiguousarray(n_groups, dtype=np.intc)
-        self.shape = None
-        self._check(self._lib.sbe_loopred_set_data(self._h, N, F, S, C, K, _ptr(codes), _ptr(groups) if C > 1 else None,
-                                                   _ptr(counts) if C > 1 else None, capacity))
-        self.shape, self._codes, self.n_observed, self.capacity = (N, F, S, C, K, R), codes, M, capacity
-        self._clear()
+        capacity = int(capacity)
 
-    def _with_data(self):
-        if self.shape is None:
-            raise ValueError("no data yet (set_data)")
-        return self.shape
+        def store(codes):
+            if not 1 <= capacity <= MAX_SAMPLES:
+                raise ValueError(f"capacity={capacity}; the store takes 1 .. {MAX_SAMPLES} (2^20) samples")
+            M = int((codes != NA).sum())
+            if store_bytes(M, capacity) > MAX_STORE_BYTES:
+                raise ValueError(f"the rows and weights of {M} observed cells x {capacity} samples take {store_bytes(M, capacity)} bytes on the device, "
+                                 f"the limit is {MAX_STORE_BYTES}")
+            return (capacity,)
+        self._set_data(codes, groups, n_groups, n_states, n_clusters, store)
+        self.n_observed, self.capacity = int((self._codes != NA).sum()), capacity
 
     def reset(self):
         """Forget the rows, the weights and the sums, keep the data."""
@@ -279,36 +254,17 @@ class LooPredHandle(_handle.UnitHandle):
         self._check(self._lib.sbe_loopred_reset(self._h))
         self._clear()
 
-    def set_feature_tile(self, features):
-        """Features per workgroup tile (0: the default); the results do not depend on it."""
-        self._check(self._lib.sbe_loopred_set_feature_tile(self._h, int(features)))
-
     def max_samples(self) -> int:
         """The samples one library call holds."""
         return MAX_STAGE_BYTES // sample_bytes(*self._with_data())
 
-    def _samples(self, clusters, weights, tables):
-        N, F, S, C, K, R = self._with_data()
-        clusters = np.ascontiguousarray(clusters, dtype=np.uint8)
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        tables = np.ascontiguousarray(tables, dtype=np.float64)
-        T = clusters.shape[0]
-        if clusters.shape != (T, K, N) or weights.shape != (T, F, C) or tables.shape != (T, R, F, S):
-            raise ValueError(f"{T} samples take clusters {(T, K, N)}, weights {(T, F, C)} and tables {(T, R, F, S)}; got {clusters.shape}, "
-                             f"{weights.shape}, {tables.shape}")
-        step = self.max_samples()
-        if step < 1:
-            raise ValueError(f"one sample takes {sample_bytes(N, F, S, C, K, R)} bytes on the device, a call holds {MAX_STAGE_BYTES}")
-        return clusters, weights, tables, T, step
-
     def add(self, clusters, weights, tables):
         """Phase 1: store the likelihood rows of the samples: clusters uint8 [T,K,N] of 0 / 1, weights float64 [T,F,C], tables
         float64 [T,R,F,S].  Blocks beyond max_samples() go in several library calls."""
-        clusters, weights, tables, T, step = self._samples(clusters, weights, tables)
+        T, blocks = self._blocks(clusters, weights, tables)
         if self.n_rows + T > self.capacity:
             raise ValueError(f"{self.n_rows} samples stored, {T} more exceed the capacity of {self.capacity}")
-        for t0 in range(0, T, step):
-            cl, w, tb = clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step]
+        for _t0, cl, w, tb in blocks:
             self._check(self._lib.sbe_loopred_add(self._h, cl.shape[0], _ptr(cl), _ptr(w), _ptr(tb)))
             self.n_rows += cl.shape[0]
             self.kernel_ms["add"] += self.last_kernel_ms()
@@ -332,11 +288,10 @@ class LooPredHandle(_handle.UnitHandle):
         if self._pointwise is None:
             self._with_data()
             raise ValueError("no weights yet (weights() comes before accumulate())")
-        clusters, weights, tables, T, step = self._samples(clusters, weights, tables)
+        T, blocks = self._blocks(clusters, weights, tables)
         if self.next_t + T > self.n_rows:
             raise ValueError(f"{self.next_t} of {self.n_rows} samples accumulated, {T} more are too many")
-        for t0 in range(0, T, step):
-            cl, w, tb = clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step]
+        for _t0, cl, w, tb in blocks:
             self._check(self._lib.sbe_loopred_accumulate(self._h, self.next_t, cl.shape[0], _ptr(cl), _ptr(w), _ptr(tb)))
             self.next_t += cl.shape[0]
             self.kernel_ms["accumulate"] += self.last_kernel_ms()
@@ -371,47 +326,28 @@ def loo_predictive(codes, groups, clusters, weights, tables, burnin=0.1, device=
     """The leave-one-out predictive of T logged samples after burn-in, in predict.posterior_predictive's argument forms: codes
     uint8 [N,F]; groups: uint8 [C-1,N] group indices (with n_groups) or a list of bool [G_c,N] assignments; clusters uint8 [T,K,N];
     weights [T,F,C]; tables [T,R,F,S].  The samples go to the device twice, in blocks of what one call holds."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = _check_burnin(burnin, clusters.shape[0])
-    T = clusters.shape[0] - burn
+    groups, n_groups, clusters, weights, tables, _u = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups)
+    T = clusters.shape[0]
     if not MIN_SAMPLES <= T <= MAX_SAMPLES:
         raise ValueError(f"{T} samples after burn-in; PSIS needs {MIN_SAMPLES} .. {MAX_SAMPLES} (2^20) per observation")
     h = LooPredHandle(device)
     try:
         h.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1], capacity=T)
-        h.add(clusters[burn:], weights[burn:], tables[burn:])
+        h.add(clusters, weights, tables)
         h.weights()
-        h.accumulate(clusters[burn:], weights[burn:], tables[burn:])
+        h.accumulate(clusters, weights, tables)
         return h.result()
     finally:
         h.close()
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.loopred",
-                                 description="Leave-one-out predictive of every observed cell of an sBayes run, given the logged effect draws: "
-                                             "held-out imputation accuracy, Brier score and calibration without refitting")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
+    ap = _samples.run_parser("python -m sbayes_amd.loopred",
+                             "Leave-one-out predictive of every observed cell of an sBayes run, given the logged effect draws: "
+                             "held-out imputation accuracy, Brier score and calibration without refitting")
     ap.add_argument("--out", type=Path, default=None, help="directory for loo_predictive.tsv and loo_features.tsv")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    data = predict.read_data(args.features, args.feature_states, args.confounders)
-    weights, tables = predict.read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = predict.read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     res = loo_predictive(data["codes"], data["groups"], clusters, weights, tables, burnin=args.burnin, device=args.device, n_groups=n_groups)
     print(f"{res.n_samples} samples, {int(res.observed.sum())} observed cells (given the logged effect draws): leave-one-out accuracy "
           f"{res.accuracy():.4f}, Brier {res.brier():.4f}, log score {res.log_score():.4f}")

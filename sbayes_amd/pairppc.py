@@ -40,7 +40,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, assoc, ppc, predict
+from . import _handle, _samples, assoc, ppc, predict         # noqa: F401 (ppc: the handle of the replicates, made by _samples)
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                              # SBE_PAIRPPC_ABI_VERSION of include/sbe_pairppc.h
@@ -151,11 +151,7 @@ class PairResult:
         return self.table(names)[1][:k]
 
     def write_table(self, path, names=None):
-        header, rows = self.table(names)
-        with open(path, "w") as f:
-            f.write("\t".join(header) + "\n")
-            for row in rows:
-                f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+        _samples.write_tsv(path, *self.table(names))
 
 
 class PairHandle(_handle.UnitHandle):
@@ -219,13 +215,7 @@ class PairHandle(_handle.UnitHandle):
         float64 [n, F, F].  Blocks beyond max_replicates() go in several library calls; each call validates its replicates before
         it changes anything, so an EngineError leaves the replicates of the calls before it added."""
         n_obj, f = self._with_data()
-        y = np.asarray(y_rep)
-        if y.dtype != np.uint8:
-            raise TypeError(f"replicates must be uint8 codes, got {y.dtype}")
-        if y.ndim == 2:
-            y = y[None]
-        if y.ndim != 3 or y.shape[1:] != (n_obj, f):
-            raise ValueError(f"replicates must be [n, {n_obj}, {f}], got shape {y.shape}")
+        y = _samples.check_replicates(y_rep, n_obj, f)
         step = self.max_replicates(stat_rep)
         if step < 1:
             raise ValueError(f"one replicate takes {replicate_bytes(n_obj, f, stat_rep)} bytes on the device, a call holds {MAX_STAGE_BYTES}")
@@ -261,68 +251,26 @@ def pairwise_check(codes, groups, clusters, weights, tables, n_states=None, burn
     (sbayes_amd/ppc.py), so the pairwise p-values belong to the same replicates as its per-feature ones (res.ppc holds that
     result, without y_rep).  n_states: states per feature (default: the tables' S for every feature -- a replicate may draw a state
     the data never shows).  The replicates pass through host memory, block by block."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([predict.group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = predict._check_burnin(burnin, clusters.shape[0])
-    if uniforms is not None:
-        uniforms = np.asarray(uniforms)
-        if uniforms.shape[0] != clusters.shape[0]:
-            raise ValueError(f"{uniforms.shape[0]} rows of uniforms for {clusters.shape[0]} samples")
-        uniforms = uniforms[burn:]
-    clusters, weights, tables = clusters[burn:], weights[burn:], tables[burn:]
+    groups, n_groups, clusters, weights, tables, uniforms = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups, uniforms)
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
     if n_states is None:
         n_states = np.full(codes.shape[1] if codes.ndim == 2 else 0, tables.shape[3], dtype=np.int32)
-    hp = ppc.PpcHandle(device)
-    try:
-        hp.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1])
-        h = PairHandle(hp.device)
-        try:
-            h.set_data(codes, n_states)
-            step = max(1, min(hp.max_samples(True, uniforms is not None), h.max_replicates()))
-            kernel_ms = 0.0
-            for t0 in range(0, clusters.shape[0], step):
-                hp.check(clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step], seed=seed,
-                         uniforms=uniforms[t0:t0 + step] if uniforms is not None else None, replicates=True)
-                for y in hp.drain_replicates():
-                    h.add(y)
-                    kernel_ms += h.kernel_ms
-            res = h.result()
-            res.kernel_ms, res.ppc = kernel_ms, hp.result()
-            return res
-        finally:
-            h.close()
-    finally:
-        hp.close()
+
+    def fill(h):
+        h.set_data(codes, n_states)
+        return h.max_replicates(), h.add
+    return _samples.check_with_replicates(PairHandle, fill, codes, groups, n_groups, clusters, weights, tables, seed, uniforms, device)
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.pairppc",
-                                 description="Pairwise dependence of an sBayes run's features checked against the fitted model: the chi-squared "
-                                             "statistic of every pair on the data among the same statistic on one replicated data set per logged "
-                                             "sample (conservative: given the logged effect draws; no correction for the many pairs)")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the replicates' uniforms")
+    ap = _samples.run_parser("python -m sbayes_amd.pairppc",
+                             "Pairwise dependence of an sBayes run's features checked against the fitted model: the chi-squared "
+                             "statistic of every pair on the data among the same statistic on one replicated data set per logged "
+                             "sample (conservative: given the logged effect draws; no correction for the many pairs)", seed=True)
     ap.add_argument("--out", type=Path, default=Path("pairs.tsv"), help="the table of the pairs (default: pairs.tsv)")
     ap.add_argument("-p", "--pThreshold", type=float, default=0.05, help="the predictive p below which a pair is counted as flagged")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    data = predict.read_data(args.features, args.feature_states, args.confounders)
-    weights, tables = predict.read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = predict.read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     n_states = np.array([max(1, len(s)) for s in data["state_names"]], dtype=np.int32)
     res = pairwise_check(data["codes"], data["groups"], clusters, weights, tables, n_states=n_states, burnin=args.burnin, seed=args.seed,
                          n_groups=n_groups, device=args.device)

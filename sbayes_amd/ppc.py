@@ -37,7 +37,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, predict
+from . import _handle, _samples, predict
 from ._handle import _ptr, c_handle_p
 from .predict import NA
 
@@ -145,11 +145,7 @@ class PpcResult:
         return sorted((r for r in rows if r[1] > 0), key=lambda r: r[4])[:k]
 
     def write_table(self, path, kind="feature", names=None):
-        header, rows = self.table(kind, names)
-        with open(path, "w") as f:
-            f.write("\t".join(header) + "\n")
-            for row in rows:
-                f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+        _samples.write_tsv(path, *self.table(kind, names))
 
 
 def count_observed(codes, n_states):
@@ -158,73 +154,31 @@ def count_observed(codes, n_states):
     return np.stack([(codes == s).sum(axis=0) for s in range(int(n_states))], axis=1).astype(np.int64)
 
 
-class PpcHandle(_handle.UnitHandle):
+class PpcHandle(_samples.SampleHandle):
     """Owner of one sbe_ppc handle: the data on one device.  check() appends the rows of its samples; result() returns them.
     last_kernel_ms(): the kernels of the last library call of check()."""
     _prefix, _noun = "sbe_ppc", "a posterior predictive check handle"
 
-    def __init__(self, device=None):
-        self.shape = None                                    # (N, F, S, C, K, R) once the data is set
-        self._codes = None
-        self._clear()
-        self._create_on(load, device)
-
     def _clear(self):
         self._rows = {"dev_feature": [], "dev_object": [], "count_rep": [], "y_rep": []}
         self.n_samples, self.n_skipped, self.kernel_ms = 0, 0, 0.0
-
-    def set_data(self, codes, groups, n_groups, n_states, n_clusters):
-        """codes uint8 [N,F] (255 = NA); groups uint8 [C-1,N] (255 = none) with n_groups[c] groups each.  Forgets the rows."""
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        if codes.ndim != 2:
-            raise ValueError(f"codes must be [N, F], got shape {codes.shape}")
-        N, F = codes.shape
-        n_groups = [int(g) for g in n_groups]
-        C = len(n_groups) + 1
-        groups = np.ascontiguousarray(groups, dtype=np.uint8).reshape(C - 1, -1) if C > 1 else np.zeros((0, N), dtype=np.uint8)
-        if groups.shape != (C - 1, N):
-            raise ValueError(f"groups must be [{C - 1}, {N}], got shape {groups.shape}")
-        S, K = int(n_states), int(n_clusters)
-        R = predict._check_shape(N, F, S, C, K, n_groups)
-        counts = np.ascontiguousarray(n_groups, dtype=np.intc)
-        self.shape = None
-        self._check(self._lib.sbe_ppc_set_data(self._h, N, F, S, C, K, _ptr(codes), _ptr(groups) if C > 1 else None,
-                                               _ptr(counts) if C > 1 else None))
-        self.shape, self._codes = (N, F, S, C, K, R), codes
-        self._clear()
-
-    def _with_data(self):
-        if self.shape is None:
-            raise ValueError("no data yet (set_data)")
-        return self.shape
 
     def reset(self):
         """Forget the rows of the samples checked so far (the next sample has draw index 0 again), keep the data."""
         self._with_data()
         self._clear()
 
-    def set_feature_tile(self, features):
-        """Features per workgroup tile (0: the default); no output depends on it."""
-        self._check(self._lib.sbe_ppc_set_feature_tile(self._h, int(features)))
-
     def max_samples(self, replicates=False, uniforms=False) -> int:
         """The samples one library call holds."""
-        N, F, S, C, K, R = self._with_data()
-        return MAX_STAGE_BYTES // sample_bytes(N, F, S, C, K, R, replicates, uniforms)
+        return MAX_STAGE_BYTES // sample_bytes(*self._with_data(), replicates, uniforms)
 
     def check(self, clusters, weights, tables, seed=0, uniforms=None, replicates=False):
         """Check samples: clusters uint8 [T,K,N] of 0 / 1, weights float64 [T,F,C], tables float64 [T,R,F,S]; uniforms: None
         (Philox under `seed`, the draw index continues from the samples checked so far) or float64 [T, N F] in [0, 1);
         replicates: keep y_rep.  Blocks beyond max_samples() go in several library calls; each call validates its samples
         before it writes anything, so an EngineError leaves the rows of the calls before it appended."""
-        N, F, S, C, K, R = self._with_data()
-        clusters = np.ascontiguousarray(clusters, dtype=np.uint8)
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        tables = np.ascontiguousarray(tables, dtype=np.float64)
-        T = clusters.shape[0]
-        if clusters.shape != (T, K, N) or weights.shape != (T, F, C) or tables.shape != (T, R, F, S):
-            raise ValueError(f"{T} samples take clusters {(T, K, N)}, weights {(T, F, C)} and tables {(T, R, F, S)}; got {clusters.shape}, "
-                             f"{weights.shape}, {tables.shape}")
+        T, blocks = self._blocks(clusters, weights, tables, replicates, uniforms is not None)
+        N, F, S = self.shape[:3]
         seed = int(seed)
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed={seed} must lie in [0, 2^64)")
@@ -239,15 +193,10 @@ class PpcHandle(_handle.UnitHandle):
             if bad.any():
                 t, i = np.argwhere(bad)[0]
                 raise ValueError(f"uniforms[{t}][{i}]={uniforms[t, i]} is outside [0, 1) or not finite")
-        step = self.max_samples(replicates, uniforms is not None)
-        if step < 1:
-            raise ValueError(f"one sample takes {sample_bytes(N, F, S, C, K, R, replicates, uniforms is not None)} bytes on the device, "
-                             f"a call holds {MAX_STAGE_BYTES}")
         self.kernel_ms = 0.0
-        for t0 in range(0, T, step):
-            cl, w, tb = clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step]
+        for t0, cl, w, tb in blocks:
             n = cl.shape[0]
-            u = uniforms[t0:t0 + step] if uniforms is not None else None
+            u = uniforms[t0:t0 + n] if uniforms is not None else None
             dev_f, dev_o = np.empty((n, 2, F)), np.empty((n, 2, N))
             count = np.empty((n, F, S), dtype=np.int32)
             y = np.empty((n, N, F), dtype=np.uint8) if replicates else None
@@ -285,49 +234,24 @@ def posterior_predictive_check(codes, groups, clusters, weights, tables, burnin=
     """The posterior predictive check of T logged samples after burn-in.  codes uint8 [N,F]; groups: uint8 [C-1,N] group indices
     (with n_groups) or a list of bool [G_c,N] assignments; clusters uint8 [T,K,N]; weights [T,F,C]; tables [T,R,F,S]; uniforms:
     None or float64 [T, N F], one row per sample before burn-in."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([predict.group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = predict._check_burnin(burnin, clusters.shape[0])
-    if uniforms is not None:
-        uniforms = np.asarray(uniforms)
-        if uniforms.shape[0] != clusters.shape[0]:
-            raise ValueError(f"{uniforms.shape[0]} rows of uniforms for {clusters.shape[0]} samples")
-        uniforms = uniforms[burn:]
+    groups, n_groups, clusters, weights, tables, uniforms = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups, uniforms)
     h = PpcHandle(device)
     try:
         h.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1])
-        h.check(clusters[burn:], weights[burn:], tables[burn:], seed=seed, uniforms=uniforms, replicates=replicates)
+        h.check(clusters, weights, tables, seed=seed, uniforms=uniforms, replicates=replicates)
         return h.result()
     finally:
         h.close()
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.ppc",
-                                 description="Posterior predictive check of an sBayes run's logged samples: a replicated data set per sample, and "
-                                             "p-values of the deviance per feature and per object (conservative: given the logged effect draws)")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the replicates' uniforms")
+    ap = _samples.run_parser("python -m sbayes_amd.ppc",
+                             "Posterior predictive check of an sBayes run's logged samples: a replicated data set per sample, and "
+                             "p-values of the deviance per feature and per object (conservative: given the logged effect draws)", seed=True)
     ap.add_argument("--out-features", type=Path, default=None, help="write the table per feature")
     ap.add_argument("--out-objects", type=Path, default=None, help="write the table per object")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    data = predict.read_data(args.features, args.feature_states, args.confounders)
-    weights, tables = predict.read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = predict.read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     res = posterior_predictive_check(data["codes"], data["groups"], clusters, weights, tables, burnin=args.burnin, seed=args.seed, n_groups=n_groups,
                                      device=args.device)
     print(f"{res.n_samples} samples, p_total {res.p_total:.4f} (conservative: given the logged effect draws), {res.n_skipped} cells skipped")

@@ -38,20 +38,12 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle
+from . import _handle, _samples
 from ._handle import _ptr, c_handle_p
+from ._samples import (MAX_ACC_BYTES, MAX_COMPONENTS, MAX_FEATURES, MAX_OBJECTS, MAX_ROWS, MAX_STAGE_BYTES, MAX_STATES, MAX_TILE, NA,  # noqa: F401
+                       SUM_TOL, _check_burnin, _check_shape, codes_of, group_index)                # (the limits and checks of the data)
 
 ABI_VERSION = 1                          # SBE_PREDICT_ABI_VERSION of include/sbe_predict.h
-MAX_STATES = 32                          # SBE_PREDICT_MAX_STATES
-MAX_COMPONENTS = 8                       # SBE_PREDICT_MAX_COMPONENTS
-MAX_ROWS = 256                           # SBE_PREDICT_MAX_ROWS
-MAX_OBJECTS = 1 << 20                    # SBE_PREDICT_MAX_OBJECTS
-MAX_FEATURES = 1 << 16                   # SBE_PREDICT_MAX_FEATURES
-MAX_ACC_BYTES = 1 << 32                  # SBE_PREDICT_MAX_ACC_BYTES
-MAX_STAGE_BYTES = 1 << 28                # SBE_PREDICT_MAX_STAGE_BYTES
-MAX_TILE = 256                           # SBE_PREDICT_MAX_TILE
-SUM_TOL = 1e-5                           # SBE_PREDICT_SUM_TOL
-NA = 255                                 # SBE_PREDICT_NA
 
 # name -> (restype, argtypes); mirrors include/sbe_predict.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
@@ -75,54 +67,6 @@ def sample_bytes(n_objects, n_features, n_states, n_components, n_clusters, n_ro
     """Device bytes one sample of an accumulate call takes while the call runs (sbe_predict_sample_bytes)."""
     n, f = int(n_objects), int(n_features)
     return int(n_clusters) * n + 8 * f * int(n_components) + 8 * int(n_rows) * f * int(n_states) + 2 * n + (4 * n * f if with_lik else 0)
-
-
-# ---- validation (host side, before any library call) -----------------------------------------------------------
-def _check_shape(N, F, S, C, K, n_groups):
-    """R of a shape within the limits."""
-    if not 1 <= N <= MAX_OBJECTS:
-        raise ValueError(f"{N} objects; the unit takes 1 .. {MAX_OBJECTS} (2^20)")
-    if not 1 <= F <= MAX_FEATURES:
-        raise ValueError(f"{F} features; the unit takes 1 .. {MAX_FEATURES} (2^16)")
-    if not 1 <= S <= MAX_STATES:
-        raise ValueError(f"{S} states; the unit takes 1 .. {MAX_STATES}")
-    if not 1 <= C <= MAX_COMPONENTS:
-        raise ValueError(f"{C} components; the unit takes 1 .. {MAX_COMPONENTS}")
-    if len(n_groups) != C - 1:
-        raise ValueError(f"{len(n_groups)} group counts for {C - 1} confounders")
-    if K < 1 or any(g < 1 for g in n_groups):
-        raise ValueError(f"{K} clusters and group counts {list(n_groups)}: every component needs at least one row")
-    R = K + sum(n_groups)
-    if R > MAX_ROWS:
-        raise ValueError(f"{K} clusters and the confounders' groups make {R} table rows, the limit is {MAX_ROWS}")
-    if N * F * (S + C) * 8 > MAX_ACC_BYTES:
-        raise ValueError(f"the accumulators of {N} objects x {F} features take {N * F * (S + C) * 8} bytes on the device, the limit is {MAX_ACC_BYTES}")
-    return R
-
-
-def _check_burnin(burnin, n):
-    burnin = float(burnin)
-    if not 0.0 <= burnin < 1.0:
-        raise ValueError(f"burnin={burnin} must lie in [0, 1)")
-    return int(burnin * n)
-
-
-def group_index(assignment):
-    """uint8 [N] group index (255 = none) of a bool [G, N] group assignment, the form the reference's Confounder holds."""
-    a = np.asarray(assignment, dtype=bool)
-    if a.ndim != 2 or a.shape[0] > NA:
-        raise ValueError(f"a group assignment is bool [G, N] with G <= {NA}, got shape {a.shape}")
-    if (a.sum(axis=0) > 1).any():
-        raise ValueError(f"object {int(np.flatnonzero(a.sum(axis=0) > 1)[0])} is in two groups of one confounder")
-    return np.where(a.any(axis=0), a.argmax(axis=0), NA).astype(np.uint8)
-
-
-def codes_of(features):
-    """uint8 [N, F] state index (255 = NA) of one-hot bool [N, F, S] features, the form the reference's Features holds."""
-    a = np.asarray(features, dtype=bool)
-    if a.ndim != 3 or a.shape[2] > MAX_STATES:
-        raise ValueError(f"one-hot features are bool [N, F, S] with S <= {MAX_STATES}, got shape {a.shape}")
-    return np.where(a.any(axis=2), a.argmax(axis=2), NA).astype(np.uint8)
 
 
 @dataclass
@@ -190,81 +134,33 @@ class PredictResult:
         return ["object", "feature", "observed", "predicted", "probability"] + [f"resp_{c}" for c in cn], rows
 
     def write_table(self, path, **kw):
-        header, rows = self.table(**kw)
-        with open(path, "w") as f:
-            f.write("\t".join(header) + "\n")
-            for row in rows:
-                f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+        _samples.write_tsv(path, *self.table(**kw))
 
 
-class PredictHandle(_handle.UnitHandle):
+class PredictHandle(_samples.SampleHandle):
     """Owner of one sbe_predict handle: the data and the accumulators on one device.  last_kernel_ms(): the kernels of the
     last library call of accumulate()."""
     _prefix, _noun = "sbe_predict", "a posterior predictive handle"
-
-    def __init__(self, device=None):
-        self.shape = None                                    # (N, F, S, C, K, R) once the data is set
-        self._codes = None
-        self._create_on(load, device)
-
-    def set_data(self, codes, groups, n_groups, n_states, n_clusters):
-        """codes uint8 [N,F] (255 = NA); groups uint8 [C-1,N] (255 = none) with n_groups[c] groups each.  Resets the sums."""
-        codes = np.ascontiguousarray(codes, dtype=np.uint8)
-        if codes.ndim != 2:
-            raise ValueError(f"codes must be [N, F], got shape {codes.shape}")
-        N, F = codes.shape
-        n_groups = [int(g) for g in n_groups]
-        C = len(n_groups) + 1
-        groups = np.ascontiguousarray(groups, dtype=np.uint8).reshape(C - 1, -1) if C > 1 else np.zeros((0, N), dtype=np.uint8)
-        if groups.shape != (C - 1, N):
-            raise ValueError(f"groups must be [{C - 1}, {N}], got shape {groups.shape}")
-        S, K = int(n_states), int(n_clusters)
-        R = _check_shape(N, F, S, C, K, n_groups)
-        counts = np.ascontiguousarray(n_groups, dtype=np.intc)
-        self.shape = None
-        self._check(self._lib.sbe_predict_set_data(self._h, N, F, S, C, K, _ptr(codes), _ptr(groups) if C > 1 else None,
-                                                   _ptr(counts) if C > 1 else None))
-        self.shape, self._codes = (N, F, S, C, K, R), codes
-
-    def _with_data(self):
-        if self.shape is None:
-            raise ValueError("no data yet (set_data)")
-        return self.shape
 
     def reset(self):
         """Zero the sums, keep the data."""
         self._with_data()
         self._check(self._lib.sbe_predict_reset(self._h))
 
-    def set_feature_tile(self, features):
-        """Features per workgroup tile (0: the default); the results do not depend on it."""
-        self._check(self._lib.sbe_predict_set_feature_tile(self._h, int(features)))
-
     def max_samples(self, lik=False) -> int:
         """The samples one library call holds."""
-        N, F, S, C, K, R = self._with_data()
-        return MAX_STAGE_BYTES // sample_bytes(N, F, S, C, K, R, lik)
+        return MAX_STAGE_BYTES // sample_bytes(*self._with_data(), lik)
 
     def accumulate(self, clusters, weights, tables, lik=False):
         """Add samples: clusters uint8 [T,K,N] of 0 / 1, weights float64 [T,F,C], tables float64 [T,R,F,S].  Returns the
         float32 [T, N F] likelihood rows with lik=True.  Blocks beyond max_samples() go in several library calls; each call
         validates its samples before it adds them, so an EngineError leaves the samples of the calls before it added."""
-        N, F, S, C, K, R = self._with_data()
-        clusters = np.ascontiguousarray(clusters, dtype=np.uint8)
-        weights = np.ascontiguousarray(weights, dtype=np.float64)
-        tables = np.ascontiguousarray(tables, dtype=np.float64)
-        T = clusters.shape[0]
-        if clusters.shape != (T, K, N) or weights.shape != (T, F, C) or tables.shape != (T, R, F, S):
-            raise ValueError(f"{T} samples take clusters {(T, K, N)}, weights {(T, F, C)} and tables {(T, R, F, S)}; got {clusters.shape}, "
-                             f"{weights.shape}, {tables.shape}")
-        step = self.max_samples(lik)
-        if step < 1:
-            raise ValueError(f"one sample takes {sample_bytes(N, F, S, C, K, R, lik)} bytes on the device, a call holds {MAX_STAGE_BYTES}")
+        T, blocks = self._blocks(clusters, weights, tables, lik)
+        N, F = self.shape[:2]
         rows = np.empty((T, N * F), dtype=np.float32) if lik else None
         self.kernel_ms = 0.0
-        for t0 in range(0, T, step):
-            cl, w, tb = clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step]
-            out = rows[t0:t0 + step] if lik else None
+        for t0, cl, w, tb in blocks:
+            out = rows[t0:t0 + cl.shape[0]] if lik else None
             self._check(self._lib.sbe_predict_accumulate(self._h, cl.shape[0], _ptr(cl), _ptr(w), _ptr(tb), _ptr(out) if lik else None))
             self.kernel_ms += self.last_kernel_ms()
         return rows
@@ -288,17 +184,11 @@ class PredictHandle(_handle.UnitHandle):
 def posterior_predictive(codes, groups, clusters, weights, tables, burnin=0.1, lik=False, device=None, n_groups=None) -> PredictResult:
     """The posterior predictive of T logged samples after burn-in.  codes uint8 [N,F]; groups: uint8 [C-1,N] group indices
     (with n_groups) or a list of bool [G_c,N] assignments; clusters uint8 [T,K,N]; weights [T,F,C]; tables [T,R,F,S]."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = _check_burnin(burnin, clusters.shape[0])
+    groups, n_groups, clusters, weights, tables, _u = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups)
     h = PredictHandle(device)
     try:
         h.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1])
-        rows = h.accumulate(clusters[burn:], weights[burn:], tables[burn:], lik=lik)
+        rows = h.accumulate(clusters, weights, tables, lik=lik)
         return h.result(rows)
     finally:
         h.close()
@@ -417,27 +307,14 @@ def read_data(features_csv, feature_states_csv, confounder_columns):
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.predict",
-                                 description="Posterior predictive of an sBayes run's logged samples: imputation of the missing cells, each "
-                                             "component's responsibility for the observed cells, and ELPD-LOO given the logged effect draws")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
+    ap = _samples.run_parser("python -m sbayes_amd.predict",
+                             "Posterior predictive of an sBayes run's logged samples: imputation of the missing cells, each "
+                             "component's responsibility for the observed cells, and ELPD-LOO given the logged effect draws")
     ap.add_argument("--out-imputed", type=Path, default=None, help="write the NA cells with their most probable state")
     ap.add_argument("--out-responsibility", type=Path, default=None, help="write every cell with the components' responsibilities")
     ap.add_argument("--elpd", action="store_true", help="PSIS-LOO over the likelihood rows (given the logged effect draws)")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    data = read_data(args.features, args.feature_states, args.confounders)
-    weights, tables = read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     res = posterior_predictive(data["codes"], data["groups"], clusters, weights, tables, burnin=args.burnin, lik=args.elpd, device=args.device,
                                n_groups=n_groups)
     filled, p = res.impute()

@@ -43,6 +43,7 @@ import numpy as np
 
 from . import _handle, diag
 from ._handle import _ptr, c_handle_p
+from ._samples import write_tsv
 from .diag import FLAG_CONSTANT, FLAG_NONFINITE, MAX_CHAINS, MAX_COLUMNS, MAX_DRAWS, MIN_DRAWS, PATHS  # noqa: F401
 
 ABI_VERSION = 1                          # SBE_PSENS_ABI_VERSION of include/sbe_psens.h
@@ -349,10 +350,7 @@ def powerscale_sensitivity(chains, components=None, delta=DEFAULT_DELTA, burnin=
 
 
 def write_table(path, res: PsensResult, threshold=DEFAULT_THRESHOLD):
-    with open(path, "w") as f:
-        f.write("\t".join(res.header()) + "\n")
-        for row in res.table(threshold):
-            f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+    write_tsv(path, res.header(), res.table(threshold))
 
 
 def _load_aligned_runs(stats_paths, cluster_paths, device):

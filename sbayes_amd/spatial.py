@@ -38,7 +38,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, assoc, ppc, predict
+from . import _handle, _samples, assoc, ppc, predict         # noqa: F401 (ppc: the handle of the replicates, made by _samples)
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                              # SBE_SPATIAL_ABI_VERSION of include/sbe_spatial.h
@@ -293,11 +293,7 @@ class SpatialResult:
         for path, make, names in ((features_path, self.table, feature_names), (objects_path, self.object_table, object_names)):
             if path is None:
                 continue
-            header, rows = make(names)
-            with open(path, "w") as f:
-                f.write("\t".join(header) + "\n")
-                for row in rows:
-                    f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+            _samples.write_tsv(path, *make(names))
 
 
 class SpatialHandle(_handle.UnitHandle):
@@ -357,13 +353,7 @@ class SpatialHandle(_handle.UnitHandle):
         calls; each call validates its replicates before it changes anything, so an EngineError leaves the replicates of the
         calls before it added."""
         n_obj, f, b = self._with_data()
-        y = np.asarray(y_rep)
-        if y.dtype != np.uint8:
-            raise TypeError(f"replicates must be uint8 codes, got {y.dtype}")
-        if y.ndim == 2:
-            y = y[None]
-        if y.ndim != 3 or y.shape[1:] != (n_obj, f):
-            raise ValueError(f"replicates must be [n, {n_obj}, {f}], got shape {y.shape}")
+        y = _samples.check_replicates(y_rep, n_obj, f)
         keep = REP_OUTPUTS if keep is True else tuple(keep)
         if set(keep) - set(REP_OUTPUTS):
             raise ValueError(f"keep={keep!r}: the per-replicate outputs are {REP_OUTPUTS}")
@@ -413,19 +403,7 @@ def spatial_check(codes, groups, clusters, weights, tables, band, n_bands=None, 
     without y_rep).  band: uint8 [N, N] with n_bands classes (None: one more than the largest class that occurs).  n_states:
     states per feature (default: the tables' S for every feature -- a replicate may draw a state the data never shows).  The
     replicates pass through host memory, block by block."""
-    clusters, weights, tables = np.asarray(clusters), np.asarray(weights), np.asarray(tables)
-    if tables.ndim != 4 or clusters.ndim != 3:
-        raise ValueError(f"clusters must be [T, K, N] and tables [T, R, F, S], got shapes {clusters.shape} and {tables.shape}")
-    if n_groups is None:
-        n_groups = [np.asarray(g).shape[0] for g in groups]
-        groups = np.stack([predict.group_index(g) for g in groups]) if len(n_groups) else np.zeros((0, clusters.shape[2]), dtype=np.uint8)
-    burn = predict._check_burnin(burnin, clusters.shape[0])
-    if uniforms is not None:
-        uniforms = np.asarray(uniforms)
-        if uniforms.shape[0] != clusters.shape[0]:
-            raise ValueError(f"{uniforms.shape[0]} rows of uniforms for {clusters.shape[0]} samples")
-        uniforms = uniforms[burn:]
-    clusters, weights, tables = clusters[burn:], weights[burn:], tables[burn:]
+    groups, n_groups, clusters, weights, tables, uniforms = _samples.after_burnin(groups, clusters, weights, tables, burnin, n_groups, uniforms)
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
     band = np.asarray(band)
     if n_bands is None:
@@ -434,27 +412,11 @@ def spatial_check(codes, groups, clusters, weights, tables, band, n_bands=None, 
     band, n_bands = _check_band(band, n_bands, codes.shape[0] if codes.ndim == 2 else 0)
     if n_states is None:
         n_states = np.full(codes.shape[1] if codes.ndim == 2 else 0, tables.shape[3], dtype=np.int32)
-    hp = ppc.PpcHandle(device)
-    try:
-        hp.set_data(codes, groups, n_groups, tables.shape[3], clusters.shape[1])
-        h = SpatialHandle(hp.device)
-        try:
-            h.set_data(codes, n_states, band, n_bands)
-            step = max(1, min(hp.max_samples(True, uniforms is not None), h.call_replicates()))
-            kernel_ms = 0.0
-            for t0 in range(0, clusters.shape[0], step):
-                hp.check(clusters[t0:t0 + step], weights[t0:t0 + step], tables[t0:t0 + step], seed=seed,
-                         uniforms=uniforms[t0:t0 + step] if uniforms is not None else None, replicates=True)
-                for y in hp.drain_replicates():
-                    h.add(y, keep=keep)
-                    kernel_ms += h.kernel_ms
-            res = h.result()
-            res.kernel_ms, res.ppc = kernel_ms, hp.result()
-            return res
-        finally:
-            h.close()
-    finally:
-        hp.close()
+
+    def fill(h):
+        h.set_data(codes, n_states, band, n_bands)
+        return h.call_replicates(), lambda y: h.add(y, keep=keep)
+    return _samples.check_with_replicates(SpatialHandle, fill, codes, groups, n_groups, clusters, weights, tables, seed, uniforms, device)
 
 
 # ---- files -----------------------------------------------------------------------------------------------------------------
@@ -490,27 +452,18 @@ def plane_distances(xy):
 
 
 def parser():
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.spatial",
-                                 description="Agreement of neighbouring objects of an sBayes run checked against the fitted model: the join counts "
-                                             "of the data per class of pairs among the same counts on one replicated data set per logged sample "
-                                             "(conservative: given the logged effect draws; no correction for the many comparisons)")
-    ap.add_argument("features", type=Path, help="the features.csv of the run")
-    ap.add_argument("feature_states", type=Path, help="the feature_states.csv of the run")
-    ap.add_argument("stats", type=Path, help="stats_K*_*.txt")
-    ap.add_argument("clusters", type=Path, help="clusters_K*_*.txt")
-    ap.add_argument("--confounders", nargs="*", default=[], help="the model's confounders, in its order")
+    ap = _samples.run_parser("python -m sbayes_amd.spatial",
+                             "Agreement of neighbouring objects of an sBayes run checked against the fitted model: the join counts "
+                             "of the data per class of pairs among the same counts on one replicated data set per logged sample "
+                             "(conservative: given the logged effect draws; no correction for the many comparisons)", seed=True)
     ap.add_argument("--costs", type=Path, default=None, help="a square CSV of costs between the objects, ids in the first column and the header; "
                                                              "without it plane distances are taken from the x, y columns of the features file")
     how = ap.add_mutually_exclusive_group()
     how.add_argument("--edges", type=float, nargs="+", default=None, help="increasing cost bounds: class b holds the pairs in (edge b-1, edge b]")
     how.add_argument("--bands", type=int, default=None, help="this many classes with quantile bounds over all pairs (the correlogram)")
     how.add_argument("--knn", type=int, default=None, help="one class over the symmetrised k-nearest-neighbour graph (default: --knn 6)")
-    ap.add_argument("--burnin", type=float, default=0.1, help="fraction of the samples discarded as burn-in")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the replicates' uniforms")
     ap.add_argument("--out-features", type=Path, default=Path("spatial_features.tsv"), help="the table per class and feature")
     ap.add_argument("--out-objects", type=Path, default=Path("spatial_objects.tsv"), help="the table per class and object")
-    ap.add_argument("--device", type=int, default=None)
     return ap
 
 
@@ -526,14 +479,9 @@ def bands_of_args(args, ids, xy):
 
 def main(argv=None):
     args = parser().parse_args(argv)
-    data = predict.read_data(args.features, args.feature_states, args.confounders)
+    data, clusters, weights, tables, n_groups = _samples.read_run(args)
     ids, xy = read_objects(args.features)
     band, n_bands = bands_of_args(args, ids, xy)
-    weights, tables = predict.read_parameters(args.stats, data["feature_names"], data["state_names"], data["confounders"])
-    clusters = predict.read_cluster_samples(args.clusters)
-    if clusters.shape[0] != weights.shape[0]:
-        raise SystemExit(f"{weights.shape[0]} stats rows, {clusters.shape[0]} cluster samples")
-    n_groups = [len(g) for g in data["confounders"].values()]
     n_states = np.array([max(1, len(s)) for s in data["state_names"]], dtype=np.int32)
     res = spatial_check(data["codes"], data["groups"], clusters, weights, tables, band, n_bands, n_states=n_states, burnin=args.burnin, seed=args.seed,
                         n_groups=n_groups, device=args.device)

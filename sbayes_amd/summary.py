@@ -35,6 +35,7 @@ import numpy as np
 
 from . import _handle, diag
 from ._handle import _ptr, c_handle_p
+from ._samples import write_tsv
 from .diag import (FLAG_CONSTANT, FLAG_NONFINITE, FLAG_TRUNCATED, MAX_CHAINS, MAX_COLUMNS, MAX_DRAWS, MIN_DRAWS, PATHS,  # noqa: F401
                    read_clusters, read_stats)
 
@@ -207,10 +208,7 @@ def summarize(chains, burnin=0.1, split=True, max_lag=0, probs=DEFAULT_PROBS, hd
 
 
 def write_table(path, res: SummaryResult):
-    with open(path, "w") as f:
-        f.write("\t".join(res.header()) + "\n")
-        for row in res.table():
-            f.write("\t".join(v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.10g}") for v in row) + "\n")
+    write_tsv(path, res.header(), res.table())
 
 
 def main(argv=None):
