@@ -1,5 +1,5 @@
-"""What the units that replay a run's logged samples share on the host side (predict, ppc, contribution, loopred, and pairppc
-and spatial, which consume ppc's replicates): the limits and checks of the data of include/sbe_predict.h, the handle that holds
+"""What the units that replay a run's logged samples share on the host side (predict, ppc, contribution, loopred, and pairppc,
+spatial and objpair, which consume ppc's replicates): the limits and checks of the data of include/sbe_predict.h, the handle that holds
 the data and sends blocks of samples, the opening of the one-call functions, the driver of a replicate consumer, the table
 writer and the command lines' common arguments.  The C side's counterpart is the sample store of csrc/sbe_predict_row.hip.h;
 DESIGN.md section 7 describes both."""

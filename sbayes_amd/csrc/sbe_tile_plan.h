@@ -1,5 +1,5 @@
 // sbe_tile_plan.h -- the numbers of the units that count co-occurrences as 32 x 32 tiles of a 0/1 matrix product on the
-// matrix pipe (sbe_assoc.hip, sbe_pairppc.hip, sbe_consensus.hip, sbe_partdist.hip, sbe_simerr.hip; DESIGN.md section 13 has the arguments): the geometry of
+// matrix pipe (sbe_assoc.hip, sbe_pairppc.hip, sbe_consensus.hip, sbe_partdist.hip, sbe_simerr.hip, sbe_objpair.hip; DESIGN.md section 13 has the arguments): the geometry of
 // a tile and of a round of the contraction, where a lane's accumulator registers lie in the tile, the enumeration of the
 // tile pairs I <= J, the launch budget and the rounding to whole rounds and tiles.  Plain C++17, no HIP and nothing of a
 // unit's handle; the kernels take the same functions through SBE_TILE_HD (sbe_unit_tiles.hip.h includes this file).

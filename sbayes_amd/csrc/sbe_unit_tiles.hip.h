@@ -1,5 +1,5 @@
 #pragma once
-// sbe_unit_tiles.hip.h -- what the units on the matrix pipe share beyond sbe_unit.hip.h (sbe_consensus.hip, sbe_partdist.hip, sbe_simerr.hip,
+// sbe_unit_tiles.hip.h -- what the units on the matrix pipe share beyond sbe_unit.hip.h (sbe_consensus.hip, sbe_partdist.hip, sbe_simerr.hip, sbe_objpair.hip,
 // and through sbe_assoc_pair.hip.h sbe_assoc.hip and sbe_pairppc.hip; no other file): the FP4 contraction step of a 32 x 32 tile of a 0/1 matrix product,
 // the walk over a lane's part of the finished tile, and the launches of a range of tiles within the budget.  The numbers
 // are sbe_tile_plan.h's; DESIGN.md section 13 says why the operands are FP4 and why their placement is free.  Everything
