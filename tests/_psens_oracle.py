@@ -25,7 +25,11 @@ PSIS is tests/_elpd_oracle.psis_column(-ratios), by construction (component_weig
 
 The formula is the published one (Kallioinen et al. 2023, the CJS distance of `priorsense` / `arviz.psens`) as far as it can
 be restated here; no arviz value was available, so the checker is pinned by closed forms, by a 50-digit evaluation of its own
-sums and by invariances (tests/test_psens_oracle_cpu.py)."""
+sums and by invariances (tests/test_psens_oracle_cpu.py).
+
+For the weights' range tests (tests/test_psens_range_cpu.py, tests/test_gpu_psens_range.py) the module also measures how far
+the PSIS checker's own k follows the last bit of its elementary functions (k_spread, tol_k) and evaluates the same steps in 50
+digits (psis_weights_mp)."""
 from __future__ import annotations
 
 import math
@@ -262,3 +266,140 @@ def sums_mp(s, q):
         pq, qp = spq + half * (qint - pint), sqp + half * (pint - qint)
         js = max(pq, mpmath.mpf(0)) + max(qp, mpmath.mpf(0))
         return js, pint + qint
+
+
+# ---- the weights over their range (tests/_psens_range_cases.py): the tail's anatomy, the checker's conditioning, 50 digits ---
+def tail_count(n):
+    """ceil(min(0.2 N, 3 sqrt N)), the tail psis_column asks for."""
+    return int(math.ceil(min(0.2 * n, 3 * math.sqrt(n))))
+
+
+def tail_anatomy(ratios):
+    """(tail count asked for, ratios strictly above the cutoff, whether the cutoff is floored at log DBL_MIN), by
+    psis_column's first steps."""
+    x = np.asarray(ratios, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        x = x - np.max(x)
+    tail_n = tail_count(len(x))
+    at_rank = float(np.sort(x)[len(x) - tail_n - 1])
+    floor = math.log(eorc.DBL_MIN)
+    return tail_n, int(np.sum(x > max(at_rank, floor))), at_rank < floor
+
+
+class _Jittered:
+    """Stands in for a module (numpy, math) inside tests/_elpd_oracle: exp, log1p, log and sqrt give their value moved by -1,
+    0 or +1 ulp at random, every other name is the module's.  Zeros and non-finite values stay; sqrt of a plain number (the
+    tail count's 3 sqrt S, an integer rule) stays."""
+    _moved = ("exp", "log1p", "log", "sqrt")
+
+    def __init__(self, module, rng):
+        self._module, self._rng = module, rng
+
+    def __getattr__(self, name):
+        f = getattr(self._module, name)
+        if name not in self._moved:
+            return f
+
+        def moved(v, *args, **kwargs):
+            out = f(v, *args, **kwargs)
+            if name == "sqrt" and np.ndim(v) == 0:
+                return out
+            a = np.asarray(out, dtype=np.float64)
+            step = self._rng.integers(-1, 2, size=a.shape)
+            with np.errstate(over="ignore"):
+                b = np.where(step > 0, np.nextafter(a, np.inf), np.where(step < 0, np.nextafter(a, -np.inf), a))
+            b = np.where(np.isfinite(a) & (a != 0.0), b, a)
+            return b if np.ndim(out) else float(b)
+        return moved
+
+
+class _jitter:
+    """Context manager: tests/_elpd_oracle sees _Jittered numpy and math inside it and its own modules again after it."""
+
+    def __init__(self, seed):
+        self._rng = np.random.default_rng(seed)
+
+    def __enter__(self):
+        self._saved = (eorc.np, eorc.math)
+        eorc.np, eorc.math = _Jittered(self._saved[0], self._rng), _Jittered(self._saved[1], self._rng)
+
+    def __exit__(self, *exc):
+        eorc.np, eorc.math = self._saved
+        return False
+
+
+def k_spread(ratios, repeats=16, seed=2024):
+    """(largest |k' - k|, largest |lw' - lw|) over `repeats` seeded runs of the float64 checker in which every value of exp,
+    log1p, log and sqrt formed inside psis_column / gpdfit / gpinv is moved by -1, 0 or +1 ulp at random: how far the
+    checker's own k and log weights follow the last bit of its elementary functions.  inf where a run changes whether k
+    (or a log weight) is finite or NaN; entries that are -inf or NaN in every run add nothing."""
+    ratios = np.asarray(ratios, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        if ratios.max() - ratios.min() == 0.0:
+            return 0.0, 0.0
+    lw, k = eorc.psis_column(-ratios)
+    dk = dlw = 0.0
+    for r in range(repeats):
+        with _jitter([seed, r]):
+            lw2, k2 = eorc.psis_column(-ratios)
+        if np.isfinite(k) and np.isfinite(k2):
+            dk = max(dk, abs(float(k2) - float(k)))
+        elif not (k == k2 or (np.isnan(k) and np.isnan(k2))):
+            dk = math.inf
+        same = (lw == lw2) | (np.isnan(lw) & np.isnan(lw2))
+        with np.errstate(invalid="ignore"):
+            moved = np.abs(lw2 - lw)[~same]
+        if moved.size:
+            dlw = max(dlw, math.inf if np.isnan(moved).any() else float(moved.max()))
+    return dk, dlw
+
+
+K_TOL, K_MARGIN = 1e-10, 8.0
+
+
+def tol_k(ratios, repeats=16, seed=2024):
+    """What |k_device - k_checker| may be for one vector of log ratios: the project's 1e-10 for well-conditioned fits plus 8
+    times the checker's own spread under a +-1 ulp probe (the device's exp and log1p are good to a few
+    ulp, not to one; its sums run in another order; sixteen samples miss the worst case).  From the checker alone."""
+    return K_TOL + K_MARGIN * k_spread(ratios, repeats, seed)[0]
+
+
+def psis_weights_mp(ratios):
+    """(log weights float64 [N], k) of one vector of log ratios by the steps of psis_column / gpdfit / gpinv in 50 digits, the
+    ratios taken as the exact doubles.  For short inputs (N <= 1000)."""
+    import mpmath
+    ratios = [float(r) for r in np.asarray(ratios, dtype=np.float64)]
+    s = len(ratios)
+    tail_n = tail_count(s)
+    with mpmath.workdps(50):
+        mpf = mpmath.mpf
+        top = max(ratios)
+        x = [mpf(r) - mpf(top) for r in ratios]
+        xcutoff = max(sorted(x)[s - tail_n - 1], mpmath.log(mpf(float(eorc.DBL_MIN))))
+        expxcutoff = mpmath.exp(xcutoff)
+        tail = sorted((i for i in range(s) if x[i] > xcutoff), key=lambda i: (x[i], i))
+        n = len(tail)
+        k = mpmath.inf
+        if n > 4:
+            ary = [mpmath.exp(x[i]) - expxcutoff for i in tail]
+            m_est = 30 + int(n ** 0.5)
+            quart, last = ary[int(n / 4 + 0.5) - 1], ary[-1]
+            b_ary = [(1 - mpmath.sqrt(mpf(m_est) / (mpf(j) - mpf(0.5)))) / (3 * quart) + 1 / last for j in range(1, m_est + 1)]
+            k_ary = [mpmath.fsum(mpmath.log1p(-b * a) for a in ary) / n for b in b_ary]
+            len_scale = [n * (mpmath.log(-(b / kk)) - kk - 1) for b, kk in zip(b_ary, k_ary)]
+            weights = [1 / mpmath.fsum(mpmath.exp(lj - li) for lj in len_scale) for li in len_scale]
+            kept = [(b, w) for b, w in zip(b_ary, weights) if w >= 10 * mpf(float(eorc.DBL_EPS))]
+            wsum = mpmath.fsum(w for _b, w in kept)
+            b_post = mpmath.fsum(b * (w / wsum) for b, w in kept)
+            k_post = mpmath.fsum(mpmath.log1p(-b_post * a) for a in ary) / n
+            sigma = -k_post / b_post
+            k = (n * k_post + 5) / (n + 10)
+            if sigma <= 0:
+                return np.full(s, np.nan), float(k)
+            for place, i in enumerate(tail):
+                lp = mpmath.log1p(-(mpf(place) + mpf(0.5)) / n)
+                gq = -lp if abs(k) < mpf(float(eorc.DBL_EPS)) else mpmath.expm1(-k * lp) / k
+                x[i] = min(mpmath.log(gq * sigma + expxcutoff), mpf(0))
+        peak = max(x)
+        lse = mpmath.log(mpmath.fsum(mpmath.exp(v - peak) for v in x)) + peak
+        return np.array([float(v - lse) for v in x]), float(k)

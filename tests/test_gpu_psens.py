@@ -223,6 +223,7 @@ def test_the_psis_weights_against_the_elpd_checker(n, g):
     assert np.all(w > 0.0)
     assert np.allclose(np.log(w), lws, rtol=1e-10, atol=1e-10)
     assert np.array_equal(np.isinf(k), np.isinf(ks)) and np.allclose(k[np.isfinite(ks)], ks[np.isfinite(ks)], rtol=1e-10, atol=1e-10)
+    assert np.array_equal(np.isnan(k), np.isnan(ks))
     assert np.allclose(ess, want_ess, rtol=1e-9, atol=0.0)
     if n == 4:
         assert np.isinf(k).all()                                             # a tail of one: raw weights
