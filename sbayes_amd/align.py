@@ -33,7 +33,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _handle, diag
+from . import _clusters, _handle, diag
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_ALIGN_ABI_VERSION of include/sbe_align.h
@@ -68,16 +68,7 @@ def max_objects(n_clusters) -> int:
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------
-def _check_shape(n_runs, n_clusters, n_objects, capacity):
-    if not 1 <= n_runs <= MAX_RUNS:
-        raise ValueError(f"{n_runs} runs; the alignment takes 1 .. {MAX_RUNS}")
-    if not 1 <= n_clusters <= MAX_CLUSTERS:
-        raise ValueError(f"{n_clusters} clusters; the alignment takes 1 .. {MAX_CLUSTERS}")
-    if not 1 <= n_objects <= max_objects(n_clusters):
-        raise ValueError(f"{n_objects} objects; with {n_clusters} clusters the alignment takes 1 .. {max_objects(n_clusters)} "
-                         "(the running sums live in LDS)")
-    if not 1 <= capacity <= MAX_ROWS:
-        raise ValueError(f"capacity={capacity} out of range [1, {MAX_ROWS}] (2^20 samples per run)")
+LIMITS = _clusters.StoreLimits("the alignment", MAX_CLUSTERS, max_objects, MAX_ROWS, "(the running sums live in LDS)", max_runs=MAX_RUNS)
 
 
 def _check_seed(seed):
@@ -87,101 +78,34 @@ def _check_seed(seed):
     return seed
 
 
-def _check_samples(clusters, shape=None):
-    """uint8 [n, K, N] of 0 / 1, C order.  `shape`: the store's (K, N), where one sample [K, N] is accepted too."""
-    a = np.asarray(clusters)
-    if a.dtype.kind not in "biu":
-        raise TypeError(f"cluster samples must be boolean or integer 0 / 1, got {a.dtype}")
-    if a.ndim == 2 and shape is not None:
-        a = a[None]
-    if a.ndim != 3:
-        raise ValueError(f"cluster samples must be [n_samples, n_clusters, n_objects], got shape {a.shape}")
-    if shape is not None and a.shape[1:] != tuple(shape):
-        raise ValueError(f"samples are {a.shape[1]} clusters x {a.shape[2]} objects, the store holds {shape[0]} x {shape[1]}")
-    if a.dtype.kind != "b" and a.size and (a.min() < 0 or a.max() > 1):
-        raise ValueError("cluster samples must hold 0 and 1 only")
-    return np.ascontiguousarray(a, dtype=np.uint8)
-
-
 def _check_runs(runs):
-    runs = list(runs)
-    if not 1 <= len(runs) <= MAX_RUNS:
-        raise ValueError(f"{len(runs)} runs; the alignment takes 1 .. {MAX_RUNS}")
-    blocks = [_check_samples(r) for r in runs]
-    if len({b.shape[1:] for b in blocks}) != 1:
-        raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
-    k, n = blocks[0].shape[1:]
-    _check_shape(*_store_shape(blocks, k, n))
+    blocks, k, n = _clusters.check_runs(LIMITS, runs)
+    LIMITS.check_shape(*_clusters.store_shape(blocks, k, n))
     return blocks, k, n
 
 
-def _burn_rows(lengths, burnin):
-    burnin = float(burnin)
-    if not 0.0 <= burnin < 1.0:
-        raise ValueError(f"burnin={burnin} must lie in [0, 1)")
-    return [int(burnin * int(s)) for s in lengths]                          # Results.drop_burnin
-
-
-class SampleStoreHandle(_handle.RowStoreHandle):
-    """Owner of a handle with the store of several runs of cluster samples on one device (AlignHandle, ConsensusHandle).  A
-    subclass gives its module's load() and shape check."""
-    _lane = "run"
-    _load = staticmethod(load)
-    _check_shape = staticmethod(_check_shape)
-
-    def __init__(self, device=None):
-        self._unshape()
-        self._create_on(self._load, device)
-
-    def _lane_count(self):
-        return self.n_runs
-
-    def _unshape(self):
-        self.n_runs = self.n_clusters = self.n_objects = self.capacity = 0
-        self._stored = []
-
-    def reset(self, n_runs, n_clusters, n_objects, capacity):
-        """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits."""
-        n_runs, n_clusters, n_objects, capacity = int(n_runs), int(n_clusters), int(n_objects), int(capacity)
-        self._check_shape(n_runs, n_clusters, n_objects, capacity)
-        self._unshape()
-        self._check(self._fn("reset")(self._h, n_runs, n_clusters, n_objects, capacity))
-        self.n_runs, self.n_clusters, self.n_objects, self.capacity = n_runs, n_clusters, n_objects, capacity
-        self._stored = [0] * n_runs
-
-    def _checked_block(self, run, clusters):
-        """(run, samples uint8 [n, K, N]) of an append, refused here where the run would overflow."""
-        run = self._check_lane(run)
-        block = _check_samples(clusters, (self.n_clusters, self.n_objects))
-        if self._stored[run] + block.shape[0] > self.capacity:
-            raise ValueError(f"store overflow: run {run} holds {self._stored[run]} samples, {block.shape[0]} more exceed the capacity "
-                             f"of {self.capacity}")
-        return run, block
+class AlignHandle(_clusters.SampleStoreHandle):
+    """Owner of one sbe_align handle: the bit store of several runs of cluster samples on one device.
+    last_kernel_ms(): the within-run kernel of the last within() call."""
+    _prefix, _noun, _limits = "sbe_align", "an alignment handle", LIMITS
 
     def append(self, run, clusters):
-        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run."""
+        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run.  (The store has no operand image: a failed
+        append leaves its shape.)"""
         run, block = self._checked_block(run, clusters)
         self._check(self._append_rows(run, block))
         self._stored[run] += block.shape[0]
 
-
-class AlignHandle(SampleStoreHandle):
-    """Owner of one sbe_align handle: the bit store of several runs of cluster samples on one device.
-    last_kernel_ms(): the within-run kernel of the last within() call."""
-    _prefix, _noun = "sbe_align", "an alignment handle"
-
     def within(self, seed=0):
         """One permutation per stored sample of every run: a list of int8 [S_r, K] arrays."""
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
+        self._shaped()
         seed = _check_seed(seed)
         perms = np.zeros((self.n_runs, self.capacity, self.n_clusters), dtype=np.int8)
         self._check(self._lib.sbe_align_within(self._h, seed, _ptr(perms)))
         return [perms[r, :self.rows(r)].copy() for r in range(self.n_runs)]
 
     def _burn(self, burn_rows):
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
+        self._shaped()
         burn = np.zeros(self.n_runs, dtype=np.int64) if burn_rows is None else np.ascontiguousarray(burn_rows, dtype=np.int64)
         if burn.shape != (self.n_runs,):
             raise ValueError(f"burn_rows must hold one value per run ({self.n_runs}), got shape {burn.shape}")
@@ -231,13 +155,8 @@ class AlignResult:
         return int(self.agreement[r][np.arange(k), self.run_perms[r]].sum())
 
 
-def _store_shape(blocks, k, n):
-    """The shape of a store that holds these runs: the capacity is the longest run's, and at least one sample."""
-    return len(blocks), k, n, max(max(b.shape[0] for b in blocks), 1)
-
-
 def _within(blocks, k, n, seed, device):
-    h = AlignHandle.filled(device, _store_shape(blocks, k, n), blocks)
+    h = AlignHandle.filled(device, _clusters.store_shape(blocks, k, n), blocks)
     try:
         return h.within(seed)
     finally:
@@ -266,8 +185,8 @@ def align_runs(runs, pivot=0, within=None, burnin=0.0, device=None) -> AlignResu
     if not 0 <= pivot < len(blocks):
         raise ValueError(f"pivot {pivot} out of range [0, {len(blocks)})")
     seed = None if within is None else _check_seed(within)
-    burn = _burn_rows([b.shape[0] for b in blocks], burnin)
-    h = AlignHandle.filled(device, _store_shape(blocks, k, n), blocks)
+    burn = _clusters.burn_rows([b.shape[0] for b in blocks], burnin)
+    h = AlignHandle.filled(device, _clusters.store_shape(blocks, k, n), blocks)
     try:
         if seed is None:
             perms = [np.tile(np.arange(k, dtype=np.int8), (b.shape[0], 1)) for b in blocks]
@@ -346,7 +265,7 @@ def read_clusters(path):
 
 def write_clusters(path, clusters):
     """Write samples [S, K, N] in the ClustersLogger format."""
-    c = _check_samples(clusters)
+    c = _clusters.check_samples(clusters)
     table = np.array([ord("0"), ord("1")], dtype=np.uint8)[c]
     with open(path, "w") as f:
         for sample in table:

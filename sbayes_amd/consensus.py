@@ -26,13 +26,11 @@ There is no CPU fallback: without the library or a GPU the functions raise.  Han
 from __future__ import annotations
 
 import ctypes as ct
-import re
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 
-from . import _handle, align
+from . import _clusters, _handle, align
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_CONSENSUS_ABI_VERSION of include/sbe_consensus.h
@@ -69,19 +67,8 @@ def image_bytes(n_runs, n_clusters, n_objects, capacity) -> int:
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------
-def _check_shape(n_runs, n_clusters, n_objects, capacity):
-    if not 1 <= n_runs <= MAX_RUNS:
-        raise ValueError(f"{n_runs} runs; the consensus store takes 1 .. {MAX_RUNS}")
-    if not 1 <= n_clusters <= MAX_CLUSTERS:
-        raise ValueError(f"{n_clusters} clusters; the consensus store takes 1 .. {MAX_CLUSTERS}")
-    if not 1 <= n_objects <= MAX_OBJECTS:
-        raise ValueError(f"{n_objects} objects; the consensus store takes 1 .. {MAX_OBJECTS} (an int32 matrix [N, N] of at most 1 GiB)")
-    if not 1 <= capacity <= MAX_ROWS:
-        raise ValueError(f"capacity={capacity} out of range [1, {MAX_ROWS}] (2^20 samples per run)")
-    need = image_bytes(n_runs, n_clusters, n_objects, capacity)
-    if need > MAX_IMAGE_BYTES:
-        raise ValueError(f"a store of {n_runs} runs x {capacity} samples x {n_clusters} clusters x {n_objects} objects takes {need} bytes "
-                         f"on the device, the limit is {MAX_IMAGE_BYTES}")
+LIMITS = _clusters.StoreLimits("the consensus store", MAX_CLUSTERS, MAX_OBJECTS, MAX_ROWS, "(an int32 matrix [N, N] of at most 1 GiB)",
+                               max_runs=MAX_RUNS, image_bytes=image_bytes, max_image_bytes=MAX_IMAGE_BYTES)
 
 
 def _check_elements(n_samples, n_clusters):
@@ -92,63 +79,28 @@ def _check_elements(n_samples, n_clusters):
                          f"{MAX_ELEMENTS} (2^24: the counts are exact in the f32 accumulator up to there)")
 
 
-def _check_slot(slot):
-    if isinstance(slot, bool) or slot not in (0, 1):
-        raise ValueError(f"slot={slot!r} is neither 0 nor 1")
-    return int(slot)
-
-
 def _check_runs(runs, burnin):
     """The runs after burn-in (uint8 [S_r, K, N], C order), K, N."""
-    runs = list(runs)
-    if not 1 <= len(runs) <= MAX_RUNS:
-        raise ValueError(f"{len(runs)} runs; the consensus store takes 1 .. {MAX_RUNS}")
-    blocks = [align._check_samples(r) for r in runs]
-    if len({b.shape[1:] for b in blocks}) != 1:
-        raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
-    k, n = blocks[0].shape[1:]
-    _check_shape(*align._store_shape(blocks, k, n))
-    burn = align._burn_rows([b.shape[0] for b in blocks], burnin)
-    return [b[at:] for b, at in zip(blocks, burn)], k, n
+    blocks, k, n = _clusters.check_runs(LIMITS, runs)
+    LIMITS.check_shape(*_clusters.store_shape(blocks, k, n))
+    return _clusters.after_burnin(blocks, burnin), k, n
 
 
-class ConsensusHandle(align.SampleStoreHandle):
+class ConsensusHandle(_clusters.SampleStoreHandle):
     """Owner of one sbe_consensus handle: the store of several runs of cluster samples on one device and two similarity
-    matrices (slots 0 and 1).  last_kernel_ms(): the kernels of the last similarity(), scores() or compare()."""
-    _prefix, _noun = "sbe_consensus", "a consensus handle"
-    _load = staticmethod(load)
-    _check_shape = staticmethod(_check_shape)
+    matrices (slots 0 and 1; both are out of date after an append).  last_kernel_ms(): the kernels of the last similarity(),
+    scores() or compare()."""
+    _prefix, _noun, _limits = "sbe_consensus", "a consensus handle", LIMITS
 
-    def _unshape(self):
-        super()._unshape()
+    def _out_of_date(self):
         self.slot_samples = [0, 0]                  # T of the matrix in each slot (0: empty or out of date)
-
-    def append(self, run, clusters):
-        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run.  Both slots are out of date afterwards."""
-        run, block = self._checked_block(run, clusters)
-        if block.shape[0]:
-            self.slot_samples = [0, 0]
-        rc = self._append_rows(run, block)
-        if rc == 2:                                 # SBE_ERR_HIP: the library has unshaped the store, and so does this object
-            message = self._last_error()
-            self._unshape()
-            raise _handle.EngineError(rc, message)
-        self._check(rc)
-        self._stored[run] += block.shape[0]
-
-    def set_launch_tiles(self, tile_pairs):
-        """Tile pairs per launch of the similarity kernel (0: the default); the results do not depend on it."""
-        self._check(self._lib.sbe_consensus_set_launch_tiles(self._h, int(tile_pairs)))
 
     def similarity(self, runs=None, slot=0, copy=True):
         """The similarity counts over `runs` (indices; None: every run) into `slot`; int32 [N, N], or None with copy=False
         (the matrix stays on the device for scores() and compare())."""
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
-        slot = _check_slot(slot)
-        mask = np.zeros(self.n_runs, dtype=np.uint8)
-        for run in (range(self.n_runs) if runs is None else runs):
-            mask[self._check_lane(run)] = 1
+        self._shaped()
+        slot = _clusters.check_index("slot", slot)
+        mask = self._mask(runs)
         total = sum(s for s, m in zip(self._stored, mask) if m)
         _check_elements(total, self.n_clusters)
         counts = np.empty((self.n_objects, self.n_objects), dtype=np.int32) if copy else None
@@ -159,15 +111,14 @@ class ConsensusHandle(align.SampleStoreHandle):
 
     def scores(self, run, slot=0):
         """int64 [rows(run)]: the score of every stored sample of `run` against the matrix in `slot`."""
-        run, slot = self._check_lane(run), _check_slot(slot)
+        run, slot = self._check_lane(run), _clusters.check_index("slot", slot)
         scores = np.empty(self._stored[run], dtype=np.int64)
         self._check(self._lib.sbe_consensus_scores(self._h, slot, run, _ptr(scores)))
         return scores
 
     def compare(self):
         """(row_max, row_sum) int64 [N] of |C_0 T_1 - C_1 T_0|, slot 0 against slot 1."""
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
+        self._shaped()
         row_max = np.empty(self.n_objects, dtype=np.int64)
         row_sum = np.empty(self.n_objects, dtype=np.int64)
         self._check(self._lib.sbe_consensus_compare(self._h, _ptr(row_max), _ptr(row_sum)))
@@ -207,11 +158,15 @@ class RunComparison:
     n_samples: tuple
 
 
+def _filled(blocks, k, n, device):
+    return ConsensusHandle.filled(device, _clusters.store_shape(blocks, k, n), blocks)
+
+
 def similarity(runs, burnin=0.0, device=None) -> Similarity:
     """The similarity of the objects over all samples of `runs` (a list of 0/1 [S_r, K, N] arrays) after burn-in."""
     blocks, k, n = _check_runs(runs, burnin)
     _check_elements(sum(b.shape[0] for b in blocks), k)
-    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
+    h = _filled(blocks, k, n, device)
     try:
         counts = h.similarity()
         return Similarity(counts, h.slot_samples[0], h.last_kernel_ms())
@@ -219,36 +174,31 @@ def similarity(runs, burnin=0.0, device=None) -> Similarity:
         h.close()
 
 
-def argmin_score(scores):
-    """(run, sample) of the smallest (score, run, sample) over per-run score arrays."""
-    best = None
-    for r, s in enumerate(scores):
-        if len(s):
-            at = int(np.argmin(s))                                          # (the first minimum)
-            if best is None or int(s[at]) < best[0]:
-                best = (int(s[at]), r, at)
-    if best is None:
-        raise ValueError("no sample to choose from")
-    return best[1], best[2]
+argmin_score = _clusters.argmin_rows      # (run, sample) of the smallest (score, run, sample) over per-run score arrays
+
+
+def _estimate(h, blocks, copy=False, clock=lambda: 0.0):
+    """point_estimate on a filled handle, and the pooled counts (None without copy).  clock: the handle's last_kernel_ms
+    where the caller wants the kernels' time."""
+    counts = h.similarity(copy=copy)
+    kernel_ms = clock()
+    scores = []
+    for r in range(len(blocks)):
+        scores.append(h.scores(r))
+        kernel_ms += clock()
+    run, sample = argmin_score(scores)
+    return PointEstimate(run, sample, blocks[run][sample].copy(), scores, h.slot_samples[0], kernel_ms), counts
 
 
 def point_estimate(runs, burnin=0.0, device=None) -> PointEstimate:
     """The consensus clustering: the sample of `runs` (after burn-in) with the smallest score against the pooled matrix."""
     blocks, k, n = _check_runs(runs, burnin)
     _check_elements(sum(b.shape[0] for b in blocks), k)
-    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
+    h = _filled(blocks, k, n, device)
     try:
-        h.similarity(copy=False)
-        kernel_ms = h.last_kernel_ms()
-        scores = []
-        for r in range(len(blocks)):
-            scores.append(h.scores(r))
-            kernel_ms += h.last_kernel_ms()
-        total = h.slot_samples[0]
+        return _estimate(h, blocks, clock=h.last_kernel_ms)[0]
     finally:
         h.close()
-    run, sample = argmin_score(scores)
-    return PointEstimate(run, sample, blocks[run][sample].copy(), scores, total, kernel_ms)
 
 
 def difference(row_max, row_sum, n_a, n_b):
@@ -257,25 +207,30 @@ def difference(row_max, row_sum, n_a, n_b):
     return int(max(int(v) for v in row_max)) / (n_a * n_b), sum(int(v) for v in row_sum) / (n_a * n_b * n * n)
 
 
+def _compare(h, lengths) -> RunComparison:
+    """compare_runs on a filled handle: every run's own matrix (slot 0) against every later run's (slot 1)."""
+    r_n = len(lengths)
+    max_abs, mean_abs = np.zeros((r_n, r_n)), np.zeros((r_n, r_n))
+    for a in range(r_n - 1):
+        h.similarity([a], slot=0, copy=False)
+        for b in range(a + 1, r_n):
+            h.similarity([b], slot=1, copy=False)
+            row_max, row_sum = h.compare()
+            max_abs[a, b], mean_abs[a, b] = difference(row_max, row_sum, lengths[a], lengths[b])
+            max_abs[b, a], mean_abs[b, a] = max_abs[a, b], mean_abs[a, b]
+    return RunComparison(max_abs, mean_abs, tuple(lengths))
+
+
 def compare_runs(runs, burnin=0.0, device=None) -> RunComparison:
     """Every run's own similarity probabilities against every other run's, with no label matching."""
     blocks, k, n = _check_runs(runs, burnin)
     for b in blocks:
         _check_elements(b.shape[0], k)
-    r_n = len(blocks)
-    max_abs, mean_abs = np.zeros((r_n, r_n)), np.zeros((r_n, r_n))
-    h = ConsensusHandle.filled(device, align._store_shape(blocks, k, n), blocks)
+    h = _filled(blocks, k, n, device)
     try:
-        for a in range(r_n - 1):
-            h.similarity([a], slot=0, copy=False)
-            for b in range(a + 1, r_n):
-                h.similarity([b], slot=1, copy=False)
-                row_max, row_sum = h.compare()
-                max_abs[a, b], mean_abs[a, b] = difference(row_max, row_sum, blocks[a].shape[0], blocks[b].shape[0])
-                max_abs[b, a], mean_abs[b, a] = max_abs[a, b], mean_abs[a, b]
+        return _compare(h, [b.shape[0] for b in blocks])
     finally:
         h.close()
-    return RunComparison(max_abs, mean_abs, tuple(b.shape[0] for b in blocks))
 
 
 # ---- files -------------------------------------------------------------------------------------------------------
@@ -292,50 +247,28 @@ def read_similarity(path):
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.consensus",
-                                 description="Posterior similarity of the objects, agreement of the runs and the consensus clustering "
-                                             "of several sBayes runs")
-    ap.add_argument("files", nargs="+", type=Path, help="clusters files of the runs (clusters_K<k>_<run>.txt), all of one K")
-    ap.add_argument("--burnin", type=float, default=0.0)
-    ap.add_argument("--out", type=Path, default=None, help="folder of the outputs (default: that of the first file)")
-    ap.add_argument("--device", type=int, default=None)
+    ap = _clusters.runs_parser("python -m sbayes_amd.consensus", "Posterior similarity of the objects, agreement of the runs and the consensus "
+                                                                 "clustering of several sBayes runs")
     args = ap.parse_args(argv)
-    runs = [align.read_clusters(p) for p in args.files]
-    if len({c.shape[1:] for c in runs}) != 1:
-        raise SystemExit(f"the files differ in clusters or objects: {[c.shape[1:] for c in runs]}")
-    k, n = runs[0].shape[1:]
-    m = re.match(r"clusters_(K\d+)_", args.files[0].name)
-    tag = m.group(1) if m else f"K{k}"
-    out = args.files[0].parent if args.out is None else args.out
-    out.mkdir(parents=True, exist_ok=True)
+    runs, tag, _names, out = _clusters.read_runs(args)
     blocks, k, n = _check_runs(runs, args.burnin)
     lengths = [b.shape[0] for b in blocks]
     _check_elements(sum(lengths), k)
-    r_n = len(blocks)
-    max_abs, mean_abs = np.zeros((r_n, r_n)), np.zeros((r_n, r_n))
-    h = ConsensusHandle.filled(args.device, align._store_shape(blocks, k, n), blocks)      # one store serves the three questions
+    h = _filled(blocks, k, n, args.device)                  # one store serves the three questions
     try:
-        counts = h.similarity()                             # the pooled matrix, slot 0
-        total = h.slot_samples[0]
-        scores = [h.scores(r) for r in range(r_n)]
-        for a in range(r_n - 1):                            # every run's own matrix against every later run's
-            h.similarity([a], slot=0, copy=False)
-            for b in range(a + 1, r_n):
-                h.similarity([b], slot=1, copy=False)
-                row_max, row_sum = h.compare()
-                max_abs[a, b], mean_abs[b, a] = difference(row_max, row_sum, lengths[a], lengths[b])
+        est, counts = _estimate(h, blocks, copy=True)       # the pooled matrix, slot 0
+        cmp = _compare(h, lengths)
     finally:
         h.close()
-    run, sample = argmin_score(scores)
-    print(f"{r_n} runs, {k} clusters, {n} objects; {total} samples after burn-in")
-    print(f"consensus: sample {sample} (after burn-in) of {args.files[run].name}, score {int(scores[run][sample])}")
-    align.write_clusters(out / f"consensus_{tag}.txt", blocks[run][sample][None])
-    write_similarity(out / f"similarity_{tag}.txt", counts / float(total))
+    r_n = len(blocks)
+    print(f"{r_n} runs, {k} clusters, {n} objects; {est.n_samples} samples after burn-in")
+    print(f"consensus: sample {est.sample} (after burn-in) of {args.files[est.run].name}, score {int(est.scores[est.run][est.sample])}")
+    align.write_clusters(out / f"consensus_{tag}.txt", est.clusters[None])
+    write_similarity(out / f"similarity_{tag}.txt", counts / float(est.n_samples))
     if r_n > 1:
         print("max |P_a - P_b| (above the diagonal) and mean |P_a - P_b| (below it) of the runs' similarity probabilities:")
         for a in range(r_n):
-            cells = ["-" if a == b else "%.6f" % (max_abs[a, b] if a < b else mean_abs[a, b]) for b in range(r_n)]
+            cells = ["-" if a == b else "%.6f" % (cmp.max_abs[a, b] if a < b else cmp.mean_abs[a, b]) for b in range(r_n)]
             print(f"{args.files[a].name}\t" + "\t".join(cells))
     return 0
 

@@ -153,17 +153,13 @@ struct Slot {
     int32_t* d_counts = nullptr;        // [N][N]
     size_t bytes = 0;
     int64_t T = 0;
-    uint64_t version = 0;               // of the store when it was computed (0: empty)
 };
 
 }  // namespace
 
-struct sbe_consensus : sbe_unit_handle, unit_bit_store, unit_tile_launches {   // (ev: around the kernels of the last similarity, scores or compare)
-    int64_t seg_bytes = 0, stride = 0;
-    uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
+// (ev: around the kernels of the last similarity, scores or compare; the image's two results are the slots)
+struct sbe_consensus : sbe_unit_handle, unit_bit_store, unit_tile_launches, unit_segment_image {
     Slot slot[2];
-    uint8_t* d_img = nullptr;           // [32 W][n_runs][seg_bytes]
-    size_t img_bytes = 0;
     unsigned long long* d_score = nullptr;   // [cap]
     size_t score_bytes = 0;
     long long* d_cmp = nullptr;         // [2][N]
@@ -174,7 +170,7 @@ struct sbe_consensus : sbe_unit_handle, unit_bit_store, unit_tile_launches {   /
 namespace {
 
 constexpr char kNullHandle[] = "null handle";
-constexpr char kLane[] = "run", kReset[] = "sbe_consensus_reset";
+constexpr char kLane[] = "run", kReset[] = "sbe_consensus_reset", kSlot[] = "slot", kSimilarity[] = "sbe_consensus_similarity";
 
 constexpr unit_store_limits kLimits{kMaxRuns, SBE_CONSENSUS_MAX_CLUSTERS, SBE_CONSENSUS_MAX_OBJECTS, SBE_CONSENSUS_MAX_ROWS,
                                     SBE_CONSENSUS_MAX_IMAGE_BYTES, "(an int32 matrix [N][N] of at most 1 GiB)"};
@@ -184,18 +180,6 @@ int64_t segment_bytes(int K, int64_t cap) { return rounds_of(cap * K) * kRoundBy
 int64_t store_bytes(int n_runs, int K, int64_t N, int64_t cap) {
     const int64_t W = (N + 31) / 32;
     return 32 * W * n_runs * segment_bytes(K, cap) + (int64_t)n_runs * cap * K * W * (int64_t)sizeof(uint32_t);
-}
-
-int check_slot_index(sbe_consensus* h, int slot) {
-    return slot == 0 || slot == 1 ? SBE_OK : fail(h, SBE_ERR_ARG, "slot=%d is neither 0 nor 1", slot);
-}
-
-// a slot a later call reads: computed, and on the store as it is now
-int check_slot_current(sbe_consensus* h, int slot) {
-    if (h->slot[slot].version == 0) return fail(h, SBE_ERR_STATE, "slot %d is empty (sbe_consensus_similarity comes first)", slot);
-    if (h->slot[slot].version != h->version)
-        return fail(h, SBE_ERR_STATE, "slot %d was computed before the store last changed (sbe_consensus_similarity again)", slot);
-    return SBE_OK;
 }
 
 }  // namespace
@@ -223,22 +207,13 @@ int sbe_consensus_reset(sbe_consensus* h, int n_runs, int n_clusters, int64_t n_
     if (const int rc = h->check_shape(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows)) return rc;
     if (const int rc = h->check_device_bytes(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows, store_bytes(n_runs, n_clusters, n_objects, capacity_rows)))
         return rc;
-    const int64_t W = (n_objects + 31) / 32, seg = segment_bytes(n_clusters, capacity_rows);
-    const size_t img = (size_t)(32 * W * n_runs * seg);
-    h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
-    h->slot[0].version = h->slot[1].version = 0;
-    ++h->version;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_img, h->img_bytes, img);
-    if (!rc) rc = h->alloc_bits(h, n_runs, n_clusters, n_objects, capacity_rows);
-    if (!rc) rc = unit_ensure(h, h->d_score, h->score_bytes, (size_t)capacity_rows * sizeof(unsigned long long));
-    if (!rc) rc = unit_ensure(h, h->d_cmp, h->cmp_bytes, (size_t)2 * (size_t)n_objects * sizeof(long long));
-    if (rc) return rc;
-    // the image is zero wherever no element was appended: the padding of every segment and the objects behind N
-    HIPCHK(h, hipMemsetAsync(h->d_img, 0, img, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->seg_bytes = seg;
-    h->stride = n_runs * seg;
+    const auto ensure_rest = [&] {
+        int rc = h->alloc_bits(h, n_runs, n_clusters, n_objects, capacity_rows);
+        if (!rc) rc = unit_ensure(h, h->d_score, h->score_bytes, (size_t)capacity_rows * sizeof(unsigned long long));
+        if (!rc) rc = unit_ensure(h, h->d_cmp, h->cmp_bytes, (size_t)2 * (size_t)n_objects * sizeof(long long));
+        return rc;
+    };
+    if (const int rc = h->reset_image(h, n_runs, n_objects, segment_bytes(n_clusters, capacity_rows), ensure_rest)) return rc;
     h->set_shape(n_runs, n_clusters, n_objects, capacity_rows);
     return SBE_OK;
 }
@@ -264,17 +239,14 @@ int sbe_consensus_append_rows(sbe_consensus* h, int run, const uint8_t* rows, in
         HIPCHK(h, hipGetLastError());
         return SBE_OK;
     });
-    // a piece may be in the image already while the run's row count is not: the next append would OR new elements onto
-    // it.  The store is unshaped instead (sbe_consensus_reset comes next), as after a failed allocation
-    if (rc) h->runs.rows.clear();
-    return rc;
+    return h->append_done(h, rc);
 }
 
 int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot, int32_t* counts_out) {
     CHECK_HANDLE(h, kNullHandle);
     if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
     if (!run_mask) return fail(h, SBE_ERR_ARG, "null pointer argument: run_mask");
-    if (const int rc = check_slot_index(h, slot)) return rc;
+    if (const int rc = h->check_result_index(h, kSlot, slot)) return rc;
     SimArgs args{};
     int64_t T = 0, steps = 0;
     for (int r = 0; r < h->runs.count(); ++r) {
@@ -293,38 +265,29 @@ int sbe_consensus_similarity(sbe_consensus* h, const uint8_t* run_mask, int slot
     Slot& s = h->slot[slot];
     const size_t nn = (size_t)h->N * (size_t)h->N;
     HIPCHK(h, hipSetDevice(h->device));
-    s.version = 0;                                        // (until the new matrix is in place)
+    h->result_version[slot] = 0;                          // (until the new matrix is in place)
     int rc = unit_ensure(h, s.d_counts, s.bytes, nn * sizeof(int32_t));
     if (rc) return rc;
-    const int64_t tiles = tiles_of(h->N), tile_pairs = tiles * (tiles + 1) / 2;
     args.img = h->d_img;
     args.stride = h->stride;
     args.counts = s.d_counts;
     args.N = (int)h->N;
-    rc = unit_timed(h, [&] {
-        return unit_for_tile_launches(tile_pairs, tiles_per_launch(steps, h->launch_tiles), [&](int64_t t0, int64_t t_end) {      // one wave per tile pair
-            args.t0 = t0;
-            args.t_end = t_end;
-            k_consensus_similarity<<<(unsigned)(t_end - t0), 64, 0, h->stream>>>(args);
-            HIPCHK(h, hipGetLastError());
-            return SBE_OK;
-        });
-    });
+    rc = unit_launch_tile_pairs(h, steps, args, k_consensus_similarity);
     if (!rc && counts_out) rc = unit_copy_back(h, (const int32_t*)s.d_counts, nn, {counts_out});
     if (!rc) rc = unit_sync_timed(h);
     if (rc) return rc;
     s.T = T;
-    s.version = h->version;
+    h->result_version[slot] = h->version;
     return SBE_OK;
 }
 
 int sbe_consensus_scores(sbe_consensus* h, int slot, int run, int64_t* score_out) {
     CHECK_HANDLE(h, kNullHandle);
     if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
-    if (const int rc = check_slot_index(h, slot)) return rc;
+    if (const int rc = h->check_result_index(h, kSlot, slot)) return rc;
     if (run < 0 || run >= h->runs.count()) return fail(h, SBE_ERR_ARG, "run %d out of range [0,%d)", run, h->runs.count());
     if (!score_out) return fail(h, SBE_ERR_ARG, "null pointer argument: score_out");
-    if (const int rc = check_slot_current(h, slot)) return rc;
+    if (const int rc = h->check_result_current(h, kSlot, kSimilarity, slot)) return rc;
     const int64_t rows = h->runs.rows[(size_t)run];
     HIPCHK(h, hipSetDevice(h->device));
     const Slot& s = h->slot[slot];
@@ -351,7 +314,7 @@ int sbe_consensus_compare(sbe_consensus* h, int64_t* row_max, int64_t* row_sum) 
     if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
     if (!row_max || !row_sum) return fail(h, SBE_ERR_ARG, "null pointer argument: %s", !row_max ? "row_max" : "row_sum");
     for (int slot = 0; slot < 2; ++slot)
-        if (const int rc = check_slot_current(h, slot)) return rc;
+        if (const int rc = h->check_result_current(h, kSlot, kSimilarity, slot)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = unit_timed(h, [&] {
         k_consensus_compare<<<(unsigned)h->N, kBlock, 0, h->stream>>>(h->slot[0].d_counts, (long long)h->slot[0].T, h->slot[1].d_counts,

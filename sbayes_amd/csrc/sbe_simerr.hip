@@ -198,18 +198,15 @@ struct Side {
     long long* d_s2 = nullptr;          // [N][N]
     size_t s2_bytes = 0;
     int64_t n_batches = 0;
-    uint64_t version = 0;               // of the store when it was computed (0: empty)
 };
 
 }  // namespace
 
-// (the bit store's lanes, shape, staging buffer and host checks; its bit rows are not kept: d_bits stays null)
-struct sbe_simerr : sbe_unit_handle, unit_bit_store, unit_tile_launches {   // (ev: around the kernels of the last moments or compare)
-    int64_t batch_rows = 0, batch_steps = 0, seg_bytes = 0, stride = 0;
-    uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
+// (the bit store's lanes, shape, staging buffer and host checks; its bit rows are not kept: d_bits stays null.  ev: around
+// the kernels of the last moments or compare; the image's two results are the sides)
+struct sbe_simerr : sbe_unit_handle, unit_bit_store, unit_tile_launches, unit_segment_image {
+    int64_t batch_rows = 0, batch_steps = 0;
     Side side[2];
-    uint8_t* d_img = nullptr;           // [32 W][n_runs][seg_bytes]
-    size_t img_bytes = 0;
     double* d_z2 = nullptr;             // [N][N], once a compare has asked for it
     size_t z2_bytes = 0;
     double* d_row_max = nullptr;        // [N]
@@ -224,7 +221,7 @@ struct sbe_simerr : sbe_unit_handle, unit_bit_store, unit_tile_launches {   // (
 namespace {
 
 constexpr char kNullHandle[] = "null handle";
-constexpr char kLane[] = "run", kReset[] = "sbe_simerr_reset";
+constexpr char kLane[] = "run", kReset[] = "sbe_simerr_reset", kSide[] = "side", kMoments[] = "sbe_simerr_moments";
 
 constexpr unit_store_limits kLimits{kMaxRuns, SBE_SIMERR_MAX_CLUSTERS, SBE_SIMERR_MAX_OBJECTS, SBE_SIMERR_MAX_ROWS, SBE_SIMERR_MAX_IMAGE_BYTES,
                                     "(a side holds 12 N^2 bytes: at most 768 MiB)"};
@@ -236,18 +233,6 @@ int64_t segment_bytes(int K, int64_t cap, int64_t b) { return (cap + b - 1) / b 
 int64_t store_bytes(int n_runs, int K, int64_t N, int64_t cap, int64_t b) { return whole_tiles(N) * n_runs * segment_bytes(K, cap, b); }
 
 bool batch_ok(int64_t cap, int64_t b) { return b >= 1 && b <= cap; }
-
-int check_side_index(sbe_simerr* h, int side) {
-    return side == 0 || side == 1 ? SBE_OK : fail(h, SBE_ERR_ARG, "side=%d is neither 0 nor 1", side);
-}
-
-// a side a compare reads: computed, and on the store as it is now
-int check_side_current(sbe_simerr* h, int side) {
-    if (h->side[side].version == 0) return fail(h, SBE_ERR_STATE, "side %d is empty (sbe_simerr_moments comes first)", side);
-    if (h->side[side].version != h->version)
-        return fail(h, SBE_ERR_STATE, "side %d was computed before the store last changed (sbe_simerr_moments again)", side);
-    return SBE_OK;
-}
 
 }  // namespace
 
@@ -278,21 +263,14 @@ int sbe_simerr_reset(sbe_simerr* h, int n_runs, int n_clusters, int64_t n_object
         return fail(h, SBE_ERR_ARG, "batch_rows=%lld out of range [1, %lld] (the capacity of a run)", (long long)batch_rows, (long long)capacity_rows);
     const int64_t img = store_bytes(n_runs, n_clusters, n_objects, capacity_rows, batch_rows);
     if (const int rc = h->check_device_bytes(h, kLimits, n_runs, n_clusters, n_objects, capacity_rows, img)) return rc;
-    h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
-    h->side[0].version = h->side[1].version = 0;
-    ++h->version;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc = unit_ensure(h, h->d_img, h->img_bytes, (size_t)img);
-    if (!rc) rc = unit_ensure(h, h->d_row_max, h->row_max_bytes, (size_t)n_objects * sizeof(double));
-    if (!rc) rc = unit_ensure(h, h->d_row_int, h->row_int_bytes, (size_t)n_objects * (1 + kMaxThresholds) * sizeof(int32_t));
-    if (rc) return rc;
-    // the image is zero wherever no element was appended: the padding of every batch and the objects behind N
-    HIPCHK(h, hipMemsetAsync(h->d_img, 0, (size_t)img, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // (the image is zero in the padding of every batch too)
+    const auto ensure_rows = [&] {
+        const int rc = unit_ensure(h, h->d_row_max, h->row_max_bytes, (size_t)n_objects * sizeof(double));
+        return rc ? rc : unit_ensure(h, h->d_row_int, h->row_int_bytes, (size_t)n_objects * (1 + kMaxThresholds) * sizeof(int32_t));
+    };
+    if (const int rc = h->reset_image(h, n_runs, n_objects, segment_bytes(n_clusters, capacity_rows, batch_rows), ensure_rows)) return rc;
     h->batch_rows = batch_rows;
     h->batch_steps = steps_of_batch(n_clusters, batch_rows);
-    h->seg_bytes = segment_bytes(n_clusters, capacity_rows, batch_rows);
-    h->stride = n_runs * h->seg_bytes;
     h->set_shape(n_runs, n_clusters, n_objects, capacity_rows);
     return SBE_OK;
 }
@@ -322,18 +300,15 @@ int sbe_simerr_append_rows(sbe_simerr* h, int run, const uint8_t* rows, int64_t 
             return SBE_OK;
         });
     });
-    // a piece may be in the image already while the run's row count is not: the next append would OR new elements onto
-    // it.  The store is unshaped instead (sbe_simerr_reset comes next), as after a failed allocation
-    if (rc) h->runs.rows.clear();
-    else h->runs.rows[(size_t)run] = have + n_rows;
-    return rc;
+    if (!rc) h->runs.rows[(size_t)run] = have + n_rows;
+    return h->append_done(h, rc);
 }
 
 int sbe_simerr_moments(sbe_simerr* h, const uint8_t* run_mask, int side, int32_t* s1_out, int64_t* s2_out, int64_t* n_batches_out) {
     CHECK_HANDLE(h, kNullHandle);
     if (const int rc = h->runs.check_shaped(h, kReset)) return rc;
     if (!run_mask) return fail(h, SBE_ERR_ARG, "null pointer argument: run_mask");
-    if (const int rc = check_side_index(h, side)) return rc;
+    if (const int rc = h->check_result_index(h, kSide, side)) return rc;
     MomentArgs args{};
     int64_t nB = 0, rows_selected = 0;
     for (int r = 0; r < h->runs.count(); ++r) {
@@ -356,33 +331,24 @@ int sbe_simerr_moments(sbe_simerr* h, const uint8_t* run_mask, int side, int32_t
     Side& s = h->side[side];
     const size_t nn = (size_t)h->N * (size_t)h->N;
     HIPCHK(h, hipSetDevice(h->device));
-    s.version = 0;                                        // (until the new moments are in place)
+    h->result_version[side] = 0;                          // (until the new moments are in place)
     int rc = unit_ensure(h, s.d_s1, s.s1_bytes, nn * sizeof(int32_t));
     if (!rc) rc = unit_ensure(h, s.d_s2, s.s2_bytes, nn * sizeof(long long));
     if (rc) return rc;
-    const int64_t tiles = tiles_of(h->N), tile_pairs = tiles * (tiles + 1) / 2;
     args.img = h->d_img;
     args.stride = h->stride;
     args.s1 = s.d_s1;
     args.s2 = s.d_s2;
     args.N = (int)h->N;
     args.batch_steps = (int)h->batch_steps;
-    rc = unit_timed(h, [&] {
-        return unit_for_tile_launches(tile_pairs, tiles_per_launch(nB * h->batch_steps, h->launch_tiles), [&](int64_t t0, int64_t t_end) {   // one wave per tile pair
-            args.t0 = t0;
-            args.t_end = t_end;
-            k_simerr_moments<<<(unsigned)(t_end - t0), 64, 0, h->stream>>>(args);
-            HIPCHK(h, hipGetLastError());
-            return SBE_OK;
-        });
-    });
+    rc = unit_launch_tile_pairs(h, nB * h->batch_steps, args, k_simerr_moments);
     if (!rc && s1_out) rc = unit_copy_back(h, (const int32_t*)s.d_s1, nn, {s1_out});
     if (!rc && s2_out) rc = unit_copy_back(h, (const int64_t*)s.d_s2, nn, {s2_out});
     if (!rc) rc = unit_sync_timed(h);
     if (rc) return rc;
     if (n_batches_out) *n_batches_out = nB;
     s.n_batches = nB;
-    s.version = h->version;
+    h->result_version[side] = h->version;
     return SBE_OK;
 }
 
@@ -401,7 +367,7 @@ int sbe_simerr_compare(sbe_simerr* h, const double* thresholds, int n_thresholds
         args.thr[m] = thresholds[m];
     }
     for (int side = 0; side < 2; ++side)
-        if (const int rc = check_side_current(h, side)) return rc;
+        if (const int rc = h->check_result_current(h, kSide, kMoments, side)) return rc;
     const size_t N = (size_t)h->N, nn = N * N;
     HIPCHK(h, hipSetDevice(h->device));
     if (z2_out)

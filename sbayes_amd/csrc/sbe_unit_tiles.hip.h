@@ -1,7 +1,8 @@
 #pragma once
 // sbe_unit_tiles.hip.h -- what the units on the matrix pipe share beyond sbe_unit.hip.h (sbe_consensus.hip, sbe_partdist.hip, sbe_simerr.hip, sbe_objpair.hip,
 // and through sbe_assoc_pair.hip.h sbe_assoc.hip and sbe_pairppc.hip; no other file): the FP4 contraction step of a 32 x 32 tile of a 0/1 matrix product,
-// the walk over a lane's part of the finished tile, and the launches of a range of tiles within the budget.  The numbers
+// the walk over a lane's part of the finished tile, the launches of a range of tiles within the budget, and the host part of
+// the segmented operand image that sbe_consensus.hip and sbe_simerr.hip keep (unit_segment_image).  The numbers
 // are sbe_tile_plan.h's; DESIGN.md section 13 says why the operands are FP4 and why their placement is free.  Everything
 // lives in an unnamed namespace, as in the sibling headers.
 #include "sbe_unit.hip.h"
@@ -76,5 +77,73 @@ int unit_for_tile_launches(int64_t total, int64_t per_launch, Fn fn) {
         if (const int rc = fn(t0, std::min(total, t0 + per_launch))) return rc;
     return SBE_OK;
 }
+
+// ... with a kernel that computes one tile pair I <= J of an N x N result per wave (Args has t0 and t_end: the pairs of a
+// launch), between the handle's two events; steps: the contraction steps of a pair
+template <class H, class Args>
+int unit_launch_tile_pairs(H* h, int64_t steps, Args& args, void (*kernel)(const Args)) {
+    const int64_t tiles = tiles_of(h->N), tile_pairs = tiles * (tiles + 1) / 2;
+    return unit_timed(h, [&] {
+        return unit_for_tile_launches(tile_pairs, tiles_per_launch(steps, h->launch_tiles), [&](int64_t t0, int64_t t_end) {
+            args.t0 = t0;
+            args.t_end = t_end;
+            kernel<<<(unsigned)(t_end - t0), 64, 0, h->stream>>>(args);
+            HIPCHK(h, hipGetLastError());
+            return SBE_OK;
+        });
+    });
+}
+
+// What the handles of sbe_consensus.hip and sbe_simerr.hip derive from beside the bit store: the operand image of the runs,
+// [whole tiles of objects][n_runs segments][seg_bytes] and zero wherever no element was appended, the version of the store
+// and the versions of the two results (slots, sides) that the unit computes from it.  `word` names a result in the messages,
+// `producer` the entry point that computes one.
+struct unit_segment_image {
+    int64_t seg_bytes = 0, stride = 0;  // of a run's segment, of one object's image
+    uint64_t version = 0;               // of the store: every reset and every appended piece makes a new one
+    uint64_t result_version[2] = {};    // of the store when the result was computed (0: empty)
+    uint8_t* d_img = nullptr;           // [whole_tiles(N)][n_runs][seg_bytes]
+    size_t img_bytes = 0;
+
+    // The middle of <prefix>_reset, behind the shape checks: the store loses its shape and the results their versions, the
+    // image and -- ensure_rest() -- the unit's other buffers are allocated, the image is zeroed.  set_shape follows
+    template <class H, class Rest>
+    int reset_image(H* h, int n_runs, int64_t n_objects, int64_t seg, Rest ensure_rest) {
+        const size_t img = (size_t)(whole_tiles(n_objects) * n_runs * seg);
+        h->runs.rows.clear();                                 // (a failed allocation leaves an unshaped store)
+        result_version[0] = result_version[1] = 0;
+        ++version;
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc = unit_ensure(h, d_img, img_bytes, img);
+        if (!rc) rc = ensure_rest();
+        if (rc) return rc;
+        // the image is zero wherever no element was appended: the padding of every segment and the objects behind N
+        HIPCHK(h, hipMemsetAsync(d_img, 0, img, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        seg_bytes = seg;
+        stride = n_runs * seg;
+        return SBE_OK;
+    }
+    // The code <prefix>_append_rows returns.  After a failure a piece may be in the image already while the run's row count
+    // is not: the next append would OR new elements onto it.  The store is unshaped instead (<prefix>_reset comes next), as
+    // after a failed allocation
+    template <class H>
+    static int append_done(H* h, int rc) {
+        if (rc) h->runs.rows.clear();
+        return rc;
+    }
+    template <class H>
+    static int check_result_index(H* h, const char* word, int i) {
+        return i == 0 || i == 1 ? SBE_OK : fail(h, SBE_ERR_ARG, "%s=%d is neither 0 nor 1", word, i);
+    }
+    // a result a later call reads: computed, and on the store as it is now
+    template <class H>
+    int check_result_current(H* h, const char* word, const char* producer, int i) const {
+        if (result_version[i] == 0) return fail(h, SBE_ERR_STATE, "%s %d is empty (%s comes first)", word, i, producer);
+        if (result_version[i] != version)
+            return fail(h, SBE_ERR_STATE, "%s %d was computed before the store last changed (%s again)", word, i, producer);
+        return SBE_OK;
+    }
+};
 
 }  // namespace

@@ -33,13 +33,11 @@ from __future__ import annotations
 
 import ctypes as ct
 import math
-import re
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 
-from . import _handle, align
+from . import _clusters, _handle, align
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_PARTDIST_ABI_VERSION of include/sbe_partdist.h
@@ -52,7 +50,7 @@ MAX_IMAGE_BYTES = 1 << 34                # SBE_PARTDIST_MAX_IMAGE_BYTES
 MAX_BLOCK = 1 << 28                      # SBE_PARTDIST_MAX_BLOCK
 MAX_SUM_ROWS = 1 << 16                   # SBE_PARTDIST_MAX_SUM_ROWS
 MAX_PAIRS = 1 << 24                      # SBE_PARTDIST_MAX_PAIRS
-LOSSES = ("vi", "binder")
+LOSSES = _clusters.LOSSES
 
 # name -> (restype, argtypes); mirrors include/sbe_partdist.h one to one (the engine's own table, _lib.PROTOTYPES, is not extended)
 PROTOTYPES = {
@@ -95,56 +93,24 @@ def xlogx(n_objects):
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------
-def _check_shape(n_runs, n_clusters, n_objects, capacity):
-    if not 1 <= n_runs <= MAX_RUNS:
-        raise ValueError(f"{n_runs} runs; the partition store takes 1 .. {MAX_RUNS}")
-    if not 1 <= n_clusters <= MAX_CLUSTERS:
-        raise ValueError(f"{n_clusters} clusters; the partition store takes 1 .. {MAX_CLUSTERS}")
-    if not 1 <= n_objects <= MAX_OBJECTS:
-        raise ValueError(f"{n_objects} objects; the partition store takes 1 .. {MAX_OBJECTS} (2 N^2 fits an int32)")
-    if not 1 <= capacity <= MAX_ROWS:
-        raise ValueError(f"capacity={capacity} out of range [1, {MAX_ROWS}] (2^20 samples per run)")
-    need = image_bytes(n_runs, n_clusters, n_objects, capacity)
-    if need > MAX_IMAGE_BYTES:
-        raise ValueError(f"a store of {n_runs} runs x {capacity} samples x {n_clusters} clusters x {n_objects} objects takes {need} bytes "
-                         f"on the device, the limit is {MAX_IMAGE_BYTES}")
+LIMITS = _clusters.StoreLimits("the partition store", MAX_CLUSTERS, MAX_OBJECTS, MAX_ROWS, "(2 N^2 fits an int32)", max_runs=MAX_RUNS,
+                               image_bytes=image_bytes, max_image_bytes=MAX_IMAGE_BYTES)
 
 
-def _check_disjoint(block):
-    """The areas of every sample of a checked block [n, K, N] are disjoint: the measures are partition measures."""
-    if block.size:
-        held = block.sum(axis=1, dtype=np.uint8)
-        if held.max() > 1:
-            s, i = (int(v) for v in np.argwhere(held > 1)[0])
-            raise ValueError(f"sample {s}: object {i} is in {int(held[s, i])} areas (the areas of a sample must be disjoint)")
-
-
-def _check_loss(loss):
-    if loss not in LOSSES:
-        raise ValueError(f"loss={loss!r} is neither 'vi' nor 'binder'")
-    return loss
-
-
-def _check_runs(runs, burnin, extra_runs=0):
-    """The runs after burn-in (uint8 [S_r, K, N], C order, disjoint areas), K, N."""
-    runs = list(runs)
-    if not 1 <= len(runs) <= MAX_RUNS - extra_runs:
-        raise ValueError(f"{len(runs)} runs; the partition store takes 1 .. {MAX_RUNS - extra_runs}")
-    blocks = [align._check_samples(r) for r in runs]
-    if len({b.shape[1:] for b in blocks}) != 1:
-        raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
-    k, n = blocks[0].shape[1:]
-    _check_shape(*align._store_shape(blocks, k, n))
-    burn = align._burn_rows([b.shape[0] for b in blocks], burnin)
-    blocks = [b[at:] for b, at in zip(blocks, burn)]
+def check_runs(runs, burnin, extra_runs=0):
+    """The runs after burn-in (uint8 [S_r, K, N], C order, disjoint areas), K, N.  extra_runs: runs of the store that the
+    caller keeps for itself."""
+    blocks, k, n = _clusters.check_runs(LIMITS, runs, extra_runs)
+    LIMITS.check_shape(*_clusters.store_shape(blocks, k, n))
+    blocks = _clusters.after_burnin(blocks, burnin)
     if sum(b.shape[0] for b in blocks) < 1:
         raise ValueError("the runs hold no samples")
     for b in blocks:
-        _check_disjoint(b)
+        _clusters.check_disjoint(b)
     return blocks, k, n
 
 
-def _check_sum_rows(total):
+def check_sum_rows(total):
     if total < 1:
         raise ValueError("the selected runs hold no samples")
     if total > MAX_SUM_ROWS:
@@ -159,42 +125,16 @@ class Block:
     sumsq: np.ndarray
 
 
-class PartitionHandle(align.SampleStoreHandle):
+class PartitionHandle(_clusters.SampleStoreHandle):
     """Owner of one sbe_partdist handle: the store of several runs of cluster samples with disjoint areas on one device.
     last_kernel_ms(): the kernels of the last block(), sums() or tables()."""
-    _prefix, _noun = "sbe_partdist", "a partition handle"
-    _load = staticmethod(load)
-    _check_shape = staticmethod(_check_shape)
+    _prefix, _noun, _limits = "sbe_partdist", "a partition handle", LIMITS
 
-    def reset(self, n_runs, n_clusters, n_objects, capacity):
-        """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits."""
-        n_runs, n_clusters, n_objects, capacity = int(n_runs), int(n_clusters), int(n_objects), int(capacity)
-        self._check_shape(n_runs, n_clusters, n_objects, capacity)
-        self._unshape()
-        table = xlogx(n_objects)
-        self._check(self._lib.sbe_partdist_reset(self._h, n_runs, n_clusters, n_objects, capacity, _ptr(table)))
-        self.n_runs, self.n_clusters, self.n_objects, self.capacity = n_runs, n_clusters, n_objects, capacity
-        self._stored = [0] * n_runs
+    def _behind_shape(self, shape, extra):
+        return (xlogx(shape[2]),)
 
-    def append(self, run, clusters):
-        """Append samples ([n, K, N] of 0 / 1 with disjoint areas, or one sample [K, N]) to a run."""
-        run, block = self._checked_block(run, clusters)
-        _check_disjoint(block)
-        rc = self._append_rows(run, block)
-        if rc == 2:                                 # SBE_ERR_HIP: the library has unshaped the store, and so does this object
-            message = self._last_error()
-            self._unshape()
-            raise _handle.EngineError(rc, message)
-        self._check(rc)
-        self._stored[run] += block.shape[0]
-
-    def set_launch_tiles(self, tile_pairs):
-        """Tiles per launch of the tile kernel (0: the default); the results do not depend on it."""
-        self._check(self._lib.sbe_partdist_set_launch_tiles(self._h, int(tile_pairs)))
-
-    def _shaped(self):
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
+    def _check_block(self, block):
+        _clusters.check_disjoint(block)
 
     def _check_range(self, side, run, first, count):
         run = self._check_lane(run)
@@ -229,19 +169,13 @@ class PartitionHandle(align.SampleStoreHandle):
                                                  _ptr(out_v) if vi else None, _ptr(out_s) if sumsq else None))
         return Block(out_b, out_v, out_s)
 
-    def _mask(self, runs):
-        mask = np.zeros(self.n_runs, dtype=np.uint8)
-        for run in (range(self.n_runs) if runs is None else runs):
-            mask[self._check_lane(run)] = 1
-        return mask
-
     def sums(self, runs=None):
         """(binder_sum int64, vi_sum float64), each [T_sel, R_sel]: for every sample of the selected runs (indices; None: every
         run), in (run, sample) order, the sum of its distances to the samples of each selected run."""
         self._shaped()
         mask = self._mask(runs)
         total = sum(s for s, m in zip(self._stored, mask) if m)
-        _check_sum_rows(total)
+        check_sum_rows(total)
         binder_sum = np.empty((total, int(mask.sum())), dtype=np.int64)
         vi_sum = np.empty((total, int(mask.sum())), dtype=np.float64)
         self._check(self._lib.sbe_partdist_sums(self._h, _ptr(mask), _ptr(binder_sum), _ptr(vi_sum)))
@@ -304,20 +238,10 @@ def adjusted_rand(sumsq, sizes_a, sizes_b, n_objects):
     return out
 
 
-def argmin_loss(losses):
-    """(run, sample) of the smallest (loss, run, sample) over per-run loss arrays."""
-    best = None
-    for r, s in enumerate(losses):
-        if len(s):
-            at = int(np.argmin(s))                                          # (the first minimum)
-            if best is None or s[at] < best[0]:
-                best = (s[at], r, at)
-    if best is None:
-        raise ValueError("no sample to choose from")
-    return best[1], best[2]
+argmin_loss = _clusters.argmin_rows       # (run, sample) of the smallest (loss, run, sample) over per-run loss arrays
 
 
-def _split(rows, lengths):
+def split_runs(rows, lengths):
     at = np.cumsum([0] + list(lengths))
     return [rows[at[r]:at[r + 1]] for r in range(len(lengths))]
 
@@ -330,7 +254,7 @@ def _total_loss(binder_sum, vi_sum, lengths, loss):
         total = np.zeros(vi_sum.shape[0])
         for col in range(vi_sum.shape[1]):
             total = total + vi_sum[:, col]
-    return _split(total, lengths)
+    return split_runs(total, lengths)
 
 
 def mean_run_distances(binder_sum, vi_sum, lengths):
@@ -338,7 +262,7 @@ def mean_run_distances(binder_sum, vi_sum, lengths):
     on the diagonal the zero self-pairs are left out (nan for a run of one sample, or of none).  Python integers for binder."""
     r_n = len(lengths)
     binder, vi = np.full((r_n, r_n), np.nan), np.full((r_n, r_n), np.nan)
-    rows_b, rows_v = _split(binder_sum, lengths), _split(vi_sum, lengths)
+    rows_b, rows_v = split_runs(binder_sum, lengths), split_runs(vi_sum, lengths)
     for a in range(r_n):
         for b in range(r_n):
             pairs = lengths[a] * (lengths[a] - 1) if a == b else lengths[a] * lengths[b]
@@ -408,7 +332,7 @@ class CredibleBall:
 
 
 def _filled(blocks, k, n, device, extra=None):
-    shape = list(align._store_shape(blocks, k, n))
+    shape = list(_clusters.store_shape(blocks, k, n))
     if extra is not None:
         shape[0] += 1
     h = PartitionHandle.filled(device, shape, blocks)
@@ -424,7 +348,7 @@ def _filled(blocks, k, n, device, extra=None):
 def distances(runs, burnin=0.0, device=None) -> Distances:
     """Binder's distance, the variation of information and the adjusted Rand index of every pair of samples of `runs` (a
     list of 0/1 [S_r, K, N] arrays with disjoint areas) after burn-in."""
-    blocks, k, n = _check_runs(runs, burnin)
+    blocks, k, n = check_runs(runs, burnin)
     lengths = [b.shape[0] for b in blocks]
     total = sum(lengths)
     if total * total > MAX_BLOCK:
@@ -450,7 +374,7 @@ def distances(runs, burnin=0.0, device=None) -> Distances:
 
 
 def _sums_of(blocks, k, n, device):
-    _check_sum_rows(sum(b.shape[0] for b in blocks))
+    check_sum_rows(sum(b.shape[0] for b in blocks))
     h = _filled(blocks, k, n, device)
     try:
         binder_sum, vi_sum = h.sums()
@@ -462,8 +386,8 @@ def _sums_of(blocks, k, n, device):
 def medoid(runs, loss="vi", burnin=0.0, device=None) -> Medoid:
     """The point estimate under `loss`: the sample of `runs` (after burn-in) with the smallest (summed distance to all
     samples, run, sample).  For loss="binder" it is consensus.point_estimate's sample."""
-    loss = _check_loss(loss)
-    blocks, k, n = _check_runs(runs, burnin)
+    loss = _clusters.check_loss(loss)
+    blocks, k, n = check_runs(runs, burnin)
     lengths = [b.shape[0] for b in blocks]
     binder_sum, vi_sum, kernel_ms = _sums_of(blocks, k, n, device)
     totals = _total_loss(binder_sum, vi_sum, lengths, loss)
@@ -473,35 +397,49 @@ def medoid(runs, loss="vi", burnin=0.0, device=None) -> Medoid:
 
 def run_distances(runs, burnin=0.0, device=None) -> RunDistances:
     """Mean distances between the samples of every two runs: within-run on the diagonal, between-run off it."""
-    blocks, k, n = _check_runs(runs, burnin)
+    blocks, k, n = check_runs(runs, burnin)
     lengths = [b.shape[0] for b in blocks]
     binder_sum, vi_sum, kernel_ms = _sums_of(blocks, k, n, device)
     binder, vi = mean_run_distances(binder_sum, vi_sum, lengths)
     return RunDistances(binder, vi, tuple(lengths), kernel_ms)
 
 
-def _check_mass(mass):
+def check_mass(mass):
     mass = float(mass)
     if not 0.0 < mass <= 1.0:
         raise ValueError(f"mass={mass} must lie in (0, 1]")
     return mass
 
 
+def _distances_to(h, lengths, at, loss, clock=lambda: 0.0):
+    """(one float64 array per run of `lengths`: every sample's distance to the stored sample at = (run, sample); the kernels'
+    time) on a filled handle.  clock: the handle's last_kernel_ms where the caller wants that time."""
+    dist, kernel_ms = [], 0.0
+    for r in range(len(lengths)):
+        if lengths[r]:
+            got = h.block(r, col_run=at[0], col_first=at[1], n_cols=1, binder=loss == "binder", vi=loss == "vi", sumsq=False)
+            kernel_ms += clock()
+            dist.append((got.vi if loss == "vi" else got.binder)[:, 0].astype(np.float64))
+        else:
+            dist.append(np.zeros(0))
+    return dist, kernel_ms
+
+
 def credible_ball(runs, estimate=None, mass=0.95, loss="vi", burnin=0.0, device=None) -> CredibleBall:
     """The credible ball around `estimate` (0/1 [K, N]; None: the medoid under `loss`): every sample's distance to it, the
     smallest distance that holds `mass` of the samples, and which samples lie within."""
-    loss, mass = _check_loss(loss), _check_mass(mass)
+    loss, mass = _clusters.check_loss(loss), check_mass(mass)
     given = estimate is not None
-    blocks, k, n = _check_runs(runs, burnin, extra_runs=int(given))
+    blocks, k, n = check_runs(runs, burnin, extra_runs=int(given))
     lengths = [b.shape[0] for b in blocks]
     extra = None
     if given:
-        extra = align._check_samples(estimate, (k, n))
+        extra = _clusters.check_samples(estimate, (k, n))
         if extra.shape[0] != 1:
             raise ValueError(f"the estimate must be one sample [{k}, {n}], got {extra.shape[0]}")
-        _check_disjoint(extra)
+        _clusters.check_disjoint(extra)
     else:
-        _check_sum_rows(sum(lengths))
+        check_sum_rows(sum(lengths))
     h = _filled(blocks, k, n, device, extra)
     kernel_ms = 0.0
     try:
@@ -510,16 +448,9 @@ def credible_ball(runs, estimate=None, mass=0.95, loss="vi", burnin=0.0, device=
         else:
             binder_sum, vi_sum = h.sums(range(len(blocks)))
             kernel_ms += h.last_kernel_ms()
-            run, sample = argmin_loss(_total_loss(binder_sum, vi_sum, lengths, loss))
-            at = (run, sample)
-        dist = []
-        for r in range(len(blocks)):
-            if lengths[r]:
-                got = h.block(r, col_run=at[0], col_first=at[1], n_cols=1, binder=loss == "binder", vi=loss == "vi", sumsq=False)
-                kernel_ms += h.last_kernel_ms()
-                dist.append((got.vi if loss == "vi" else got.binder)[:, 0].astype(np.float64))
-            else:
-                dist.append(np.zeros(0))
+            at = run, sample = argmin_loss(_total_loss(binder_sum, vi_sum, lengths, loss))
+        dist, block_ms = _distances_to(h, lengths, at, loss, h.last_kernel_ms)
+        kernel_ms += block_ms
     finally:
         h.close()
     radius = ball_radius(dist, mass)
@@ -537,43 +468,21 @@ def write_trace(path, distances, loss):
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.partdist",
-                                 description="Pairwise distances between the cluster samples of several sBayes runs: the medoid under "
-                                             "the variation of information or Binder's loss, run-against-run distances and the credible ball")
-    ap.add_argument("files", nargs="+", type=Path, help="clusters files of the runs (clusters_K<k>_<run>.txt), all of one K")
-    ap.add_argument("--burnin", type=float, default=0.0)
+    ap = _clusters.runs_parser("python -m sbayes_amd.partdist", "Pairwise distances between the cluster samples of several sBayes runs: the "
+                               "medoid under the variation of information or Binder's loss, run-against-run distances and the credible ball")
     ap.add_argument("--loss", choices=LOSSES, default="vi")
     ap.add_argument("--mass", type=float, default=0.95)
-    ap.add_argument("--out", type=Path, default=None, help="folder of the outputs (default: that of the first file)")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    runs = [align.read_clusters(p) for p in args.files]
-    if len({c.shape[1:] for c in runs}) != 1:
-        raise SystemExit(f"the files differ in clusters or objects: {[c.shape[1:] for c in runs]}")
-    m = re.match(r"clusters_(K\d+)_(.*)\.txt$", args.files[0].name)
-    tag = m.group(1) if m else f"K{runs[0].shape[1]}"
-    names = []
-    for r, p in enumerate(args.files):
-        m = re.match(r"clusters_K\d+_(.*)\.txt$", p.name)
-        names.append(m.group(1) if m else str(r))
-    out = args.files[0].parent if args.out is None else args.out
-    out.mkdir(parents=True, exist_ok=True)
-    mass = _check_mass(args.mass)
-    blocks, k, n = _check_runs(runs, args.burnin)
+    runs, tag, names, out = _clusters.read_runs(args)
+    mass = check_mass(args.mass)
+    blocks, k, n = check_runs(runs, args.burnin)
     lengths = [b.shape[0] for b in blocks]
-    _check_sum_rows(sum(lengths))
+    check_sum_rows(sum(lengths))
     h = _filled(blocks, k, n, args.device)                   # one store serves the three questions
     try:
         binder_sum, vi_sum = h.sums()
         run, sample = argmin_loss(_total_loss(binder_sum, vi_sum, lengths, args.loss))
-        dist = []
-        for r in range(len(blocks)):
-            if lengths[r]:
-                got = h.block(r, col_run=run, col_first=sample, n_cols=1, binder=args.loss == "binder", vi=args.loss == "vi", sumsq=False)
-                dist.append((got.vi if args.loss == "vi" else got.binder)[:, 0].astype(np.float64))
-            else:
-                dist.append(np.zeros(0))
+        dist, _ms = _distances_to(h, lengths, (run, sample), args.loss)
     finally:
         h.close()
     mean_binder, mean_vi = mean_run_distances(binder_sum, vi_sum, lengths)

@@ -30,13 +30,11 @@ There is no CPU fallback: without the library or a GPU the functions raise.  Han
 from __future__ import annotations
 
 import ctypes as ct
-import re
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 
-from . import _handle, align, partdist
+from . import _clusters, _handle, align, partdist
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_PARTSEARCH_ABI_VERSION of include/sbe_partsearch.h
@@ -89,13 +87,7 @@ def rows_of(labels, n_clusters):
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------
-def _check_shape(n_clusters, n_objects, capacity):
-    if not 1 <= n_clusters <= MAX_CLUSTERS:
-        raise ValueError(f"{n_clusters} clusters; the partition search takes 1 .. {MAX_CLUSTERS}")
-    if not 1 <= n_objects <= MAX_OBJECTS:
-        raise ValueError(f"{n_objects} objects; the partition search takes 1 .. {MAX_OBJECTS}")
-    if not 1 <= capacity <= MAX_ROWS:
-        raise ValueError(f"capacity={capacity} out of range [1, {MAX_ROWS}] (2^16 samples)")
+LIMITS = _clusters.StoreLimits("the partition search", MAX_CLUSTERS, MAX_OBJECTS, MAX_ROWS, rows_why="(2^16 samples)")
 
 
 def _check_sweeps(max_sweeps):
@@ -192,7 +184,7 @@ class SearchHandle(_handle.UnitHandle):
     def reset(self, n_clusters, n_objects, capacity):
         """Shape the store: up to `capacity` samples of n_clusters x n_objects bits, empty."""
         n_clusters, n_objects, capacity = int(n_clusters), int(n_objects), int(capacity)
-        _check_shape(n_clusters, n_objects, capacity)
+        LIMITS.check_shape(n_clusters, n_objects, capacity)
         self._unshape()
         table = partdist.xlogx(n_objects)
         self._check(self._lib.sbe_partsearch_reset(self._h, n_clusters, n_objects, capacity, _ptr(table)))
@@ -207,16 +199,11 @@ class SearchHandle(_handle.UnitHandle):
     def append(self, clusters):
         """Append samples ([n, K, N] of 0 / 1 with disjoint areas, or one sample [K, N])."""
         self._shaped(rows=False)
-        block = align._check_samples(clusters, (self.n_clusters, self.n_objects))
+        block = _clusters.check_samples(clusters, (self.n_clusters, self.n_objects))
         if self._stored + block.shape[0] > self.capacity:
             raise ValueError(f"store overflow: the store holds {self._stored} samples, {block.shape[0]} more exceed the capacity of {self.capacity}")
-        partdist._check_disjoint(block)
-        rc = self._lib.sbe_partsearch_append_rows(self._h, _ptr(block), block.shape[0])
-        if rc == 2:                                 # SBE_ERR_HIP: the library has unshaped the store, and so does this object
-            message = self._last_error()
-            self._unshape()
-            raise _handle.EngineError(rc, message)
-        self._check(rc)
+        _clusters.check_disjoint(block)
+        _clusters.finish_append(self, self._lib.sbe_partsearch_append_rows(self._h, _ptr(block), block.shape[0]))
         self._stored += block.shape[0]
 
     def rows(self) -> int:
@@ -231,7 +218,7 @@ class SearchHandle(_handle.UnitHandle):
     def search(self, loss, init, order, max_sweeps=64, trace=False) -> Starts:
         """One search per row of init (label rows [n, N]) with the sweep orders order [n, N], against the stored samples."""
         self._shaped()
-        code = LOSSES.index(partdist._check_loss(loss))
+        code = LOSSES.index(_clusters.check_loss(loss))
         max_sweeps = _check_sweeps(max_sweeps)
         init = _check_labels("init", init, self.n_clusters, self.n_objects)
         n = init.shape[0]
@@ -353,12 +340,12 @@ def rename_blocks(labels, label_rows, n_clusters, loss):
 def search(runs, loss="vi", starts=16, seed=0, max_sweeps=64, burnin=0.0, device=None) -> SearchResult:
     """The partition with the smallest expected `loss` that greedy single-object sweeps reach from `starts` starts: the best
     of them, or the medoid itself if none is strictly better."""
-    loss = partdist._check_loss(loss)
+    loss = _clusters.check_loss(loss)
     starts, max_sweeps, seed = _check_starts(starts), _check_sweeps(max_sweeps), int(seed)
-    blocks, k, n = partdist._check_runs(runs, burnin)
+    blocks, k, n = partdist.check_runs(runs, burnin)
     lengths = [b.shape[0] for b in blocks]
     total = sum(lengths)
-    partdist._check_sum_rows(total)
+    partdist.check_sum_rows(total)
     med = partdist.medoid(blocks, loss=loss, device=device)
     label_rows = np.concatenate([labels_of(b) for b in blocks])
     medoid_at = sum(lengths[:med.run]) + med.sample
@@ -385,8 +372,8 @@ def search(runs, loss="vi", starts=16, seed=0, max_sweeps=64, burnin=0.0, device
 
 
 def _check_estimates(estimates, k, n):
-    rows = align._check_samples(estimates, (k, n))
-    partdist._check_disjoint(rows)
+    rows = _clusters.check_samples(estimates, (k, n))
+    _clusters.check_disjoint(rows)
     return labels_of(rows)
 
 
@@ -395,8 +382,8 @@ def evaluate(runs, estimates, burnin=0.0, device=None) -> Evaluation:
     if isinstance(runs, SearchHandle):
         runs._shaped()
         return runs.evaluate(_check_estimates(estimates, runs.n_clusters, runs.n_objects))
-    blocks, k, n = partdist._check_runs(runs, burnin)
-    partdist._check_sum_rows(sum(b.shape[0] for b in blocks))
+    blocks, k, n = partdist.check_runs(runs, burnin)
+    partdist.check_sum_rows(sum(b.shape[0] for b in blocks))
     labels = _check_estimates(estimates, k, n)
     h = SearchHandle.filled(device, k, n, blocks)
     try:
@@ -408,40 +395,28 @@ def evaluate(runs, estimates, burnin=0.0, device=None) -> Evaluation:
 def credible_ball(runs, estimate, mass=0.95, loss="vi", burnin=0.0, device=None) -> partdist.CredibleBall:
     """The credible ball around `estimate` (0/1 [K, N], a search's clusters): evaluate's distances per run, the smallest
     distance that holds `mass` of the samples, and which samples lie within."""
-    loss, mass = partdist._check_loss(loss), partdist._check_mass(mass)
-    blocks, k, n = partdist._check_runs(runs, burnin)
-    partdist._check_sum_rows(sum(b.shape[0] for b in blocks))
-    center = align._check_samples(estimate, (k, n))
+    loss, mass = _clusters.check_loss(loss), partdist.check_mass(mass)
+    blocks, k, n = partdist.check_runs(runs, burnin)
+    partdist.check_sum_rows(sum(b.shape[0] for b in blocks))
+    center = _clusters.check_samples(estimate, (k, n))
     if center.shape[0] != 1:
         raise ValueError(f"the estimate must be one sample [{k}, {n}], got {center.shape[0]}")
     ev = evaluate(blocks, center, device=device)
-    dist = partdist._split(ev.distances(loss)[0], [b.shape[0] for b in blocks])
+    dist = partdist.split_runs(ev.distances(loss)[0], [b.shape[0] for b in blocks])
     radius = partdist.ball_radius(dist, mass)
     return partdist.CredibleBall(dist, radius, [d <= radius for d in dist], center[0], loss, mass, kernel_ms=ev.kernel_ms)
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.partsearch",
-                                 description="The partition of least expected loss over the cluster samples of several sBayes runs: greedy "
-                                             "sweeps from many starts, the medoid for comparison and the credible ball around the estimate")
-    ap.add_argument("files", nargs="+", type=Path, help="clusters files of the runs (clusters_K<k>_<run>.txt), all of one K")
-    ap.add_argument("--burnin", type=float, default=0.0)
+    ap = _clusters.runs_parser("python -m sbayes_amd.partsearch", "The partition of least expected loss over the cluster samples of several sBayes "
+                               "runs: greedy sweeps from many starts, the medoid for comparison and the credible ball around the estimate")
     ap.add_argument("--loss", choices=LOSSES, default="vi")
     ap.add_argument("--starts", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-sweeps", type=int, default=64)
     ap.add_argument("--mass", type=float, default=0.95)
-    ap.add_argument("--out", type=Path, default=None, help="folder of the outputs (default: that of the first file)")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    runs = [align.read_clusters(p) for p in args.files]
-    if len({c.shape[1:] for c in runs}) != 1:
-        raise SystemExit(f"the files differ in clusters or objects: {[c.shape[1:] for c in runs]}")
-    m = re.match(r"clusters_(K\d+)_(.*)\.txt$", args.files[0].name)
-    tag = m.group(1) if m else f"K{runs[0].shape[1]}"
-    out = args.files[0].parent if args.out is None else args.out
-    out.mkdir(parents=True, exist_ok=True)
+    runs, tag, _names, out = _clusters.read_runs(args)
     res = search(runs, loss=args.loss, starts=args.starts, seed=args.seed, max_sweeps=args.max_sweeps, burnin=args.burnin, device=args.device)
     ball = credible_ball(runs, res.clusters, mass=args.mass, loss=args.loss, burnin=args.burnin, device=args.device)
     align.write_clusters(out / f"estimate_{tag}.txt", res.clusters[None])

@@ -35,13 +35,11 @@ from __future__ import annotations
 
 import ctypes as ct
 import math
-import re
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 
-from . import _handle, align, consensus
+from . import _clusters, _handle, consensus
 from ._handle import _ptr, c_handle_p
 
 ABI_VERSION = 1                          # SBE_SIMERR_ABI_VERSION of include/sbe_simerr.h
@@ -79,21 +77,15 @@ def image_bytes(n_runs, n_clusters, n_objects, capacity, batch_rows) -> int:
 
 
 # ---- validation (host side, before any library call) -----------------------------------------------------------
+LIMITS = _clusters.StoreLimits("the similarity-error store", MAX_CLUSTERS, MAX_OBJECTS, MAX_ROWS, "(a side holds 12 N^2 bytes: at most 768 MiB)",
+                               max_runs=MAX_RUNS, image_bytes=image_bytes, max_image_bytes=MAX_IMAGE_BYTES)
+
+
 def _check_shape(n_runs, n_clusters, n_objects, capacity, batch_rows):
-    if not 1 <= n_runs <= MAX_RUNS:
-        raise ValueError(f"{n_runs} runs; the similarity-error store takes 1 .. {MAX_RUNS}")
-    if not 1 <= n_clusters <= MAX_CLUSTERS:
-        raise ValueError(f"{n_clusters} clusters; the similarity-error store takes 1 .. {MAX_CLUSTERS}")
-    if not 1 <= n_objects <= MAX_OBJECTS:
-        raise ValueError(f"{n_objects} objects; the similarity-error store takes 1 .. {MAX_OBJECTS} (a side holds 12 N^2 bytes: at most 768 MiB)")
-    if not 1 <= capacity <= MAX_ROWS:
-        raise ValueError(f"capacity={capacity} out of range [1, {MAX_ROWS}] (2^20 samples per run)")
+    LIMITS.check_ranges(n_runs, n_clusters, n_objects, capacity)
     if not 1 <= batch_rows <= capacity:
         raise ValueError(f"batch_rows={batch_rows} out of range [1, {capacity}] (the capacity of a run)")
-    need = image_bytes(n_runs, n_clusters, n_objects, capacity, batch_rows)
-    if need > MAX_IMAGE_BYTES:
-        raise ValueError(f"a store of {n_runs} runs x {capacity} samples x {n_clusters} clusters x {n_objects} objects in batches of {batch_rows} "
-                         f"takes {need} bytes on the device, the limit is {MAX_IMAGE_BYTES}")
+    LIMITS.check_image(n_runs, n_clusters, n_objects, capacity, batch_rows, how=f" in batches of {batch_rows}")
 
 
 def _check_side_batches(n_batches, batch_rows, n_samples, n_clusters):
@@ -105,12 +97,6 @@ def _check_side_batches(n_batches, batch_rows, n_samples, n_clusters):
     if used * n_clusters > MAX_ELEMENTS:
         raise ValueError(f"the side holds {used} samples x {n_clusters} clusters = {used * n_clusters} elements, the limit is "
                          f"{MAX_ELEMENTS} (2^24: the counts are exact in the f32 accumulator up to there)")
-
-
-def _check_side(side):
-    if isinstance(side, bool) or side not in (0, 1):
-        raise ValueError(f"side={side!r} is neither 0 nor 1")
-    return int(side)
 
 
 def _check_thresholds(thresholds):
@@ -128,23 +114,16 @@ def default_batch_rows(lengths) -> int:
 
 
 def _check_runs(runs, burnin, batch_rows):
-    """The runs after burn-in and without their leading S_r mod b samples (uint8 [nB_r b, K, N], C order), K, N, b."""
-    runs = list(runs)
-    if not 1 <= len(runs) <= MAX_RUNS:
-        raise ValueError(f"{len(runs)} runs; the similarity-error store takes 1 .. {MAX_RUNS}")
-    blocks = [align._check_samples(r) for r in runs]
-    if len({b.shape[1:] for b in blocks}) != 1:
-        raise ValueError(f"the runs differ in clusters or objects: {[b.shape[1:] for b in blocks]}")
-    k, n = blocks[0].shape[1:]
-    burn = align._burn_rows([b.shape[0] for b in blocks], burnin)
-    blocks = [b[at:] for b, at in zip(blocks, burn)]
-    lengths = [b.shape[0] for b in blocks]
+    """The runs after burn-in and without their leading S_r mod b samples (uint8 [nB_r b, K, N], C order), K, N, b.  (The store
+    is shaped to what the burn-in leaves, so its shape is checked behind it.)"""
+    blocks, k, n = _clusters.check_runs(LIMITS, runs)
+    blocks = _clusters.after_burnin(blocks, burnin)
     if batch_rows is None:
-        batch_rows = default_batch_rows(lengths)
+        batch_rows = default_batch_rows([b.shape[0] for b in blocks])
     elif isinstance(batch_rows, bool) or int(batch_rows) != batch_rows:
         raise ValueError(f"batch_rows={batch_rows!r} is not a whole number")
     batch_rows = int(batch_rows)
-    _check_shape(*align._store_shape(blocks, k, n), batch_rows)
+    _check_shape(*_clusters.store_shape(blocks, k, n), batch_rows)
     return [b[b.shape[0] % batch_rows:] for b in blocks], k, n, batch_rows
 
 
@@ -172,54 +151,32 @@ class Comparison:
     row_count: np.ndarray
 
 
-class SimErrHandle(align.SampleStoreHandle):
+class SimErrHandle(_clusters.SampleStoreHandle):
     """Owner of one sbe_simerr handle: the store of several runs of cluster samples in batches on one device and the
-    moments of two sides (0 and 1).  last_kernel_ms(): the kernels of the last moments() or compare()."""
-    _prefix, _noun = "sbe_simerr", "a similarity-error handle"
-    _load = staticmethod(load)
+    moments of two sides (0 and 1; both are out of date after an append).  last_kernel_ms(): the kernels of the last moments()
+    or compare()."""
+    _prefix, _noun, _limits = "sbe_simerr", "a similarity-error handle", LIMITS
     _check_shape = staticmethod(_check_shape)
 
     def _unshape(self):
         super()._unshape()
         self.batch_rows = 0
+
+    def _out_of_date(self):
         self.side_batches = [0, 0]                  # nB of each side (0: empty or out of date)
 
     def reset(self, n_runs, n_clusters, n_objects, capacity, batch_rows):
         """Shape the store: n_runs empty runs of up to `capacity` samples of n_clusters x n_objects bits, in batches of
         `batch_rows` samples."""
-        n_runs, n_clusters, n_objects, capacity, batch_rows = int(n_runs), int(n_clusters), int(n_objects), int(capacity), int(batch_rows)
-        self._check_shape(n_runs, n_clusters, n_objects, capacity, batch_rows)
-        self._unshape()
-        self._check(self._fn("reset")(self._h, n_runs, n_clusters, n_objects, capacity, batch_rows))
-        self.n_runs, self.n_clusters, self.n_objects, self.capacity, self.batch_rows = n_runs, n_clusters, n_objects, capacity, batch_rows
-        self._stored = [0] * n_runs
-
-    def append(self, run, clusters):
-        """Append samples ([n, K, N] of 0 / 1, or one sample [K, N]) to a run.  Both sides are out of date afterwards."""
-        run, block = self._checked_block(run, clusters)
-        if block.shape[0]:
-            self.side_batches = [0, 0]
-        rc = self._append_rows(run, block)
-        if rc == 2:                                 # SBE_ERR_HIP: the library has unshaped the store, and so does this object
-            message = self._last_error()
-            self._unshape()
-            raise _handle.EngineError(rc, message)
-        self._check(rc)
-        self._stored[run] += block.shape[0]
-
-    def set_launch_tiles(self, tile_pairs):
-        """Tile pairs per launch of the moments kernel (0: the default); the results do not depend on it."""
-        self._check(self._lib.sbe_simerr_set_launch_tiles(self._h, int(tile_pairs)))
+        super().reset(n_runs, n_clusters, n_objects, capacity, batch_rows)
+        self.batch_rows = int(batch_rows)
 
     def moments(self, runs=None, side=0, copy=True) -> Moments:
         """The moments over the complete batches of `runs` (indices; None: every run) into `side`; with copy=False S1 and S2
         stay on the device for compare() and only n_batches is returned."""
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
-        side = _check_side(side)
-        mask = np.zeros(self.n_runs, dtype=np.uint8)
-        for run in (range(self.n_runs) if runs is None else runs):
-            mask[self._check_lane(run)] = 1
+        self._shaped()
+        side = _clusters.check_index("side", side)
+        mask = self._mask(runs)
         stored = [s for s, m in zip(self._stored, mask) if m]
         _check_side_batches(sum(s // self.batch_rows for s in stored), self.batch_rows, sum(stored), self.n_clusters)
         s1 = np.empty((self.n_objects, self.n_objects), dtype=np.int32) if copy else None
@@ -234,8 +191,7 @@ class SimErrHandle(align.SampleStoreHandle):
     def compare(self, thresholds=THRESHOLDS, z2=False) -> Comparison:
         """Side 0 against side 1: z^2 of every pair of objects (returned only with z2=True), its row maxima, their columns and
         the columns strictly above each threshold."""
-        if not self.n_runs:
-            raise ValueError("the store has no shape yet (reset)")
+        self._shaped()
         thr = _check_thresholds(thresholds)
         n = self.n_objects
         full = np.empty((n, n), dtype=np.float64) if z2 else None
@@ -318,7 +274,7 @@ def similarity_error(runs, burnin=0.0, batch_rows=None, device=None) -> Similari
     batch means.  batch_rows None: floor(sqrt(S)) of the shortest run after burn-in."""
     blocks, k, n, batch_rows = _check_runs(runs, burnin, batch_rows)
     _check_side_batches(sum(b.shape[0] // batch_rows for b in blocks), batch_rows, sum(b.shape[0] for b in blocks), k)
-    h = SimErrHandle.filled(device, (*align._store_shape(blocks, k, n), batch_rows), blocks)
+    h = SimErrHandle.filled(device, (*_clusters.store_shape(blocks, k, n), batch_rows), blocks)
     try:
         m = h.moments()
         return SimilarityError(m.s1, m.variance, m.n_batches, batch_rows, h.last_kernel_ms())
@@ -365,7 +321,7 @@ def run_agreement(runs, burnin=0.0, batch_rows=None, thresholds=THRESHOLDS, devi
     _check_thresholds(thresholds)
     for b in blocks:
         _check_side_batches(b.shape[0] // batch_rows, batch_rows, b.shape[0], k)
-    h = SimErrHandle.filled(device, (*align._store_shape(blocks, k, n), batch_rows), blocks)
+    h = SimErrHandle.filled(device, (*_clusters.store_shape(blocks, k, n), batch_rows), blocks)
     try:
         return _agreement(h, len(blocks), thresholds)
     finally:
@@ -387,28 +343,16 @@ def write_agreement(path, names, agreement):
 
 
 def main(argv=None):
-    import argparse
-    ap = argparse.ArgumentParser(prog="python -m sbayes_amd.simerr",
-                                 description="Monte-Carlo standard error of the posterior similarity of the objects (batch means) and the "
-                                             "agreement of several sBayes runs in units of it")
-    ap.add_argument("files", nargs="+", type=Path, help="clusters files of the runs (clusters_K<k>_<run>.txt), all of one K")
-    ap.add_argument("--burnin", type=float, default=0.0)
+    ap = _clusters.runs_parser("python -m sbayes_amd.simerr", "Monte-Carlo standard error of the posterior similarity of the objects (batch "
+                                                              "means) and the agreement of several sBayes runs in units of it")
     ap.add_argument("--batch", type=int, default=None, help="samples per batch (default: floor(sqrt(S)) of the shortest run after burn-in)")
-    ap.add_argument("--out", type=Path, default=None, help="folder of the outputs (default: that of the first file)")
-    ap.add_argument("--device", type=int, default=None)
     args = ap.parse_args(argv)
-    runs = [align.read_clusters(p) for p in args.files]
-    if len({c.shape[1:] for c in runs}) != 1:
-        raise SystemExit(f"the files differ in clusters or objects: {[c.shape[1:] for c in runs]}")
-    m = re.match(r"clusters_(K\d+)_", args.files[0].name)
-    tag = m.group(1) if m else f"K{runs[0].shape[1]}"
-    out = args.files[0].parent if args.out is None else args.out
-    out.mkdir(parents=True, exist_ok=True)
+    runs, tag, _names, out = _clusters.read_runs(args)
     blocks, k, n, batch_rows = _check_runs(runs, args.burnin, args.batch)
     for b in blocks:
         _check_side_batches(b.shape[0] // batch_rows, batch_rows, b.shape[0], k)
     _check_side_batches(sum(b.shape[0] // batch_rows for b in blocks), batch_rows, sum(b.shape[0] for b in blocks), k)
-    h = SimErrHandle.filled(args.device, (*align._store_shape(blocks, k, n), batch_rows), blocks)      # one store serves both questions
+    h = SimErrHandle.filled(args.device, (*_clusters.store_shape(blocks, k, n), batch_rows), blocks)      # one store serves both questions
     try:
         pooled = h.moments()
         agreement = _agreement(h, len(blocks), THRESHOLDS)

@@ -7,7 +7,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from sbayes_amd import align, consensus
+from sbayes_amd import _clusters, align, consensus
 from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
@@ -38,7 +38,7 @@ def test_limits_agree_with_the_header():
     for shape in [(0, 1, 1, 1), (65, 1, 1, 1), (1, 0, 1, 1), (1, 9, 1, 1), (1, 1, 0, 1), (1, 1, 16385, 1), (1, 1, 1, 0), (1, 1, 1, (1 << 20) + 1)]:
         assert lib.sbe_consensus_image_bytes(*shape) == 0, shape
         with pytest.raises(ValueError):
-            consensus._check_shape(*shape)
+            consensus.LIMITS.check_shape(*shape)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
@@ -86,7 +86,7 @@ def test_bad_input_is_refused_before_the_device(no_device, runs, kw, err, match)
 
 
 def test_shapes_beyond_the_limits_are_refused_before_the_device(no_device, monkeypatch):
-    monkeypatch.setattr(align, "_check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
+    monkeypatch.setattr(_clusters, "check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
     with pytest.raises(ValueError, match="capacity=1048577 out of range"):
         consensus.similarity([_wide((1 << 20) + 1, 1, 1)])
     # T K = 2^24 + K: three runs of 2^20, 2^20 and 1 samples of K = 8

@@ -6,7 +6,7 @@ import math
 import numpy as np
 import pytest
 
-from sbayes_amd import align, consensus, diag, partdist
+from sbayes_amd import _clusters, align, consensus, diag, partdist
 from sbayes_amd._handle import EngineError
 from tests import _consensus_oracle as consensus_orc
 from tests import _partdist_cases as cases
@@ -137,7 +137,7 @@ def test_the_binder_sums_are_the_consensus_scores_plus_the_sum_of_the_counts_on_
     runs = cases.three_runs()
     fill(handle, runs)
     binder_sum, _ = handle.sums()
-    ch = consensus.ConsensusHandle.filled(None, align._store_shape(runs, 4, 100), runs)
+    ch = consensus.ConsensusHandle.filled(None, _clusters.store_shape(runs, 4, 100), runs)
     try:
         counts = ch.similarity()
         scores = np.concatenate([ch.scores(r) for r in range(3)])

@@ -7,7 +7,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from sbayes_amd import align, partdist
+from sbayes_amd import _clusters, partdist
 from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
@@ -41,7 +41,7 @@ def test_limits_agree_with_the_header():
     for shape in [(0, 1, 1, 1), (65, 1, 1, 1), (1, 0, 1, 1), (1, 9, 1, 1), (1, 1, 0, 1), (1, 1, 16385, 1), (1, 1, 1, 0), (1, 1, 1, (1 << 20) + 1)]:
         assert lib.sbe_partdist_image_bytes(*shape) == 0, shape
         with pytest.raises(ValueError):
-            partdist._check_shape(*shape)
+            partdist.LIMITS.check_shape(*shape)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
@@ -113,8 +113,8 @@ def test_bad_options_are_refused_before_the_device(no_device):
 
 
 def test_shapes_beyond_the_limits_are_refused_before_the_device(no_device, monkeypatch):
-    monkeypatch.setattr(align, "_check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
-    monkeypatch.setattr(partdist, "_check_disjoint", lambda b: None)
+    monkeypatch.setattr(_clusters, "check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
+    monkeypatch.setattr(_clusters, "check_disjoint", lambda b: None)
     with pytest.raises(ValueError, match="capacity=1048577 out of range"):
         partdist.distances([_wide((1 << 20) + 1, 1, 1)])
     with pytest.raises(ValueError, match=r"takes \d+ bytes on the device, the limit is 17179869184"):

@@ -8,7 +8,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from sbayes_amd import align, partdist, partsearch
+from sbayes_amd import _clusters, partdist, partsearch
 from tests import _abi_header as abi
 
 REPO = Path(__file__).resolve().parent.parent
@@ -43,7 +43,7 @@ def test_limits_agree_with_the_header():
         assert lib.sbe_partsearch_scratch_bytes(*shape) == 0, shape
     for shape in [(0, 1, 1), (9, 1, 1), (1, 0, 1), (1, 16385, 1), (1, 1, 0), (1, 1, (1 << 16) + 1)]:
         with pytest.raises(ValueError):
-            partsearch._check_shape(*shape)
+            partsearch.LIMITS.check_shape(*shape)
 
 
 def test_every_array_handed_to_the_library_is_bound_to_a_name():
@@ -122,8 +122,8 @@ def test_bad_options_are_refused_before_the_device(no_device, monkeypatch):
         partsearch.evaluate(runs, _overlap()[1])
     with pytest.raises(ValueError, match=r"the estimate must be one sample \[2, 5\], got 3"):
         partsearch.credible_ball(runs, _z(3, 2, 5))
-    monkeypatch.setattr(align, "_check_samples", lambda r, shape=None: r)    # (no copy of the large shape below)
-    monkeypatch.setattr(partdist, "_check_disjoint", lambda b: None)
+    monkeypatch.setattr(_clusters, "check_samples", lambda r, shape=None: r)    # (no copy of the large shape below)
+    monkeypatch.setattr(_clusters, "check_disjoint", lambda b: None)
     wide = np.broadcast_to(_z(1, 1, 1), ((1 << 16) + 1, 1, 2))
     for call in (lambda: partsearch.search([wide]), lambda: partsearch.evaluate([wide], _z(1, 2))):
         with pytest.raises(ValueError, match=r"the selection holds 65537 samples, the limit for the sums is 65536"):

@@ -8,7 +8,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from sbayes_amd import align, simerr
+from sbayes_amd import _clusters, simerr
 from tests import _abi_header as abi
 from tests import _simerr_oracle as orc
 
@@ -107,7 +107,7 @@ def test_run_agreement_asks_two_batches_of_every_run_and_checks_its_thresholds(n
 
 
 def test_shapes_beyond_the_limits_are_refused_before_the_device(no_device, monkeypatch):
-    monkeypatch.setattr(align, "_check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
+    monkeypatch.setattr(_clusters, "check_samples", lambda r, shape=None: r)    # (no copy of the large shapes below)
     with pytest.raises(ValueError, match="capacity=1048577 out of range"):
         simerr.similarity_error([_wide((1 << 20) + 1, 1, 1)])
     # T K = 2^24 + K: three runs of 2^20, 2^20 and 1 samples of K = 8 in batches of one sample
