@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function"
 mkdir -p build/obj
-units="sbe_engine_steps sbe_engine sbe_engine_resident sbe_engine_stateless sbe_mixture sbe_mixture_tuple sbe_mixture_rows sbe_mixture_mfma sbe_elpd sbe_em sbe_assoc sbe_geo sbe_wgibbs sbe_diag sbe_align sbe_summary sbe_consensus sbe_compare sbe_predict sbe_ppc sbe_partdist sbe_contrib sbe_pairppc sbe_loopred sbe_partsearch sbe_psens sbe_spatial sbe_simerr sbe_objpair"
+units="sbe_engine_steps sbe_engine sbe_engine_resident sbe_engine_stateless sbe_mixture sbe_mixture_tuple sbe_mixture_rows sbe_mixture_mfma sbe_elpd sbe_em sbe_assoc sbe_geo sbe_wgibbs sbe_diag sbe_align sbe_summary sbe_consensus sbe_compare sbe_predict sbe_ppc sbe_partdist sbe_contrib sbe_pairppc sbe_loopred sbe_partsearch sbe_psens sbe_spatial sbe_simerr sbe_objpair sbe_objloo"
 pids=""
 objects=""
 for unit in $units; do

@@ -1,12 +1,14 @@
 #pragma once
 // sbe_predict_row.hip.h -- the mixture row of a cell, m_t[n,f,.], written once for the units that put the logged samples back
 // on the data: the posterior predictive (sbe_predict.hip), the posterior predictive check (sbe_ppc.hip), the per-cluster
-// evidence (sbe_contrib.hip) and the leave-one-out predictive (sbe_loopred.hip).  All take the data
+// evidence (sbe_contrib.hip), the leave-one-out predictive (sbe_loopred.hip) and the leave-one-object-out ELPD
+// (sbe_objloo.hip).  All take the data
 // and a sample of include/sbe_predict.h word for word, so they share what reads them.  Device side: the
 // ids kernel, the validation kernel with the offender's key, the staging of a sample's slice
 // into one of two LDS buffers and the w~ / m arithmetic of a cell.  A unit's kernel
 // calls, per workgroup, tile_cell and cell_group once and, per sample, stage_slice, cell_weights and cell_state
-// (sbe_contrib.hip: cell_weights_in_and_out, cell_state and cell_state_in, the object placed in every cluster and in none).
+// (sbe_contrib.hip and sbe_objloo.hip: cell_weights_in_and_out, cell_state and cell_state_in, the object placed in every cluster
+// and in none).
 // Host side: the checks of the data's arguments, the plan of the feature tile, the messages of the offender's key, and the
 // sample store, which a unit's handle derives from: the data and the samples of the call in flight on the device, the whole of
 // <prefix>_set_feature_tile, the device part of <prefix>_set_data (upload), the opening of a compute call up to the offender's
@@ -35,7 +37,8 @@ constexpr int kDefaultTile = 16;                     // features per tile, where
 constexpr size_t kSmallSlices = (size_t)40 << 10;    // the default plan keeps the two slices under this: four workgroups per CU
 static_assert(kMaxTile <= kBlock, "a tile of Ft features gives every thread of a row of Ft a feature");
 
-// kinds of offender, in the order the headers list them (kUniform: sbe_ppc.h alone)
+// kinds of offender, in the order the headers list them (the seventh is the unit's to word: sbe_ppc.h's uniforms, kUniform, and
+// sbe_objloo.h's prior rows, which take the same slot)
 enum : int { kOverlap = 0, kWeightEntry = 1, kWeightSum = 2, kTableEntry = 3, kTableRowEmpty = 4, kTableSum = 5, kUniform = 6 };
 
 __host__ __device__ inline unsigned long long error_key(int64_t sample, int kind, int64_t at) {

@@ -5,9 +5,9 @@
 // kernels and the host side.  The numerical contract is tests/_psens_oracle.py; DESIGN.md section 28 has the layout, the
 // stated order of the prefix sum, the error bound and the limits.
 //
-// psens_block_sort: the bitonic network of sbe_summary.hip (every comparator points the same way, so slots >= N act as +inf
-// without storage) over keys of 12 bytes, a float64 value and an int32 sample index, held as two arrays; the order is
-// lexicographic, so it is unique and equals a stable argsort of the values.  Both kernels keep the keys in LDS when
+// psens_block_sort: sbe_psis_ratio.hip.h's bitonic network over keys of 12 bytes, a float64 value and an int32 sample index,
+// held as two arrays; the order is lexicographic, so it is unique and equals a stable argsort of the values (the header has
+// the PSIS steps too, which the leave-one-object-out unit shares).  Both kernels keep the keys in LDS when
 // N <= sbe_psens_lds_max_draws(), else in their slice of a global scratch: the same code, the same comparisons.
 //
 // k_psens_weights, one 256-thread workgroup per weight vector: ratios (alpha - 1) x of the component's column, their maximum
@@ -24,63 +24,26 @@
 #include <climits>
 
 #include "sbe_diag_column.hip.h"
+#include "sbe_psis_ratio.hip.h"
 #include "../../include/sbe_psens.h"
 
 namespace {
 
 constexpr size_t kPsensStaticLds = 8192;             // headroom for the kernels' static LDS (the scan's totals, the fit, reductions)
-constexpr int kPsensKeyBytes = (int)(sizeof(double) + sizeof(int32_t));
+constexpr int kPsensKeyBytes = kRatioKeyBytes;
 constexpr int64_t kPsensLdsMaxDraws = (int64_t)((kLdsBudget - kPsensStaticLds) / kPsensKeyBytes);
 constexpr size_t kPsensScratchBytes = (size_t)256 << 20;   // the sort keys of one launch on the global path
-constexpr int kPsensMaxTail = 3072;                  // the tail count ceil(min(0.2 N, 3 sqrt N)) at N = 2^20
-constexpr int kPsensMaxM = 96;                       // _gpdfit candidates: 30 + sqrt(tail) <= 85
+constexpr int kPsensMaxTail = kRatioMaxTail;
 constexpr int kPsensOutputs = 6;                     // js, bound, js_neg, bound_neg, wmean, wsd
 constexpr int kStartAt = SBE_DIAG_MAX_CHAINS;        // plan[kStartAt + m]: chain m's first place in the stack; [kStartAt + M] = N
 constexpr int kPlanLength = 2 * SBE_DIAG_MAX_CHAINS + 1;
 constexpr double kHalfInvLn2 = 0.7213475204444817;   // 0.5 / ln 2
-constexpr double kLogDblMin = -708.3964185322641;    // log(DBL_MIN)
-constexpr double kDblEps = 2.220446049250313e-16;
+static_assert(kDiagBlock == kRatioBlock, "the shared PSIS steps run in the unit's workgroup");
 constexpr int64_t kMaxProbe = (int64_t)1 << 24;
 
-struct PsensKeys {
-    double* val;
-    int32_t* idx;
-};
+using PsensKeys = RatioKeys;                         // (value, sample) keys and their sort: sbe_psis_ratio.hip.h
 
-__device__ inline void psens_compare_exchange(PsensKeys s, int lo, int hi) {
-    const double a = s.val[lo], b = s.val[hi];
-    const int32_t ia = s.idx[lo], ib = s.idx[hi];
-    if (b < a || (b == a && ib < ia)) {
-        s.val[lo] = b;
-        s.idx[lo] = ib;
-        s.val[hi] = a;
-        s.idx[hi] = ia;
-    }
-}
-
-// keys [0 .. N) ascending by (value, sample), by the whole block; ends with a barrier.  Slots N .. pad - 1 are never touched.
-__device__ inline void psens_block_sort(PsensKeys s, int N) {
-    const int tid = threadIdx.x;
-    int pad = 2;
-    while (pad < N) pad <<= 1;                               // (at most 2^20)
-    const int pairs = pad >> 1;                              // (< N)
-    for (int k = 2; k <= pad; k <<= 1) {
-        const int half = k >> 1;
-        for (int t = tid; t < pairs; t += kDiagBlock) {      // the merge's first step: slot o of a block with slot k - 1 - o
-            const int o = t & (half - 1), base = (t - o) << 1;
-            const int hi = base + k - 1 - o;
-            if (hi < N) psens_compare_exchange(s, base + o, hi);
-        }
-        __syncthreads();
-        for (int j = half >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < pairs; t += kDiagBlock) {
-                const int o = t & (j - 1), lo = ((t - o) << 1) | o;
-                if (lo + j < N) psens_compare_exchange(s, lo, lo + j);
-            }
-            __syncthreads();
-        }
-    }
-}
+__device__ inline void psens_block_sort(PsensKeys s, int N) { ratio_block_sort(s, N); }
 
 template <bool kLds>
 __device__ inline PsensKeys psens_keys(unsigned char* dyn, double* work_val, int32_t* work_idx, int N) {
@@ -119,9 +82,7 @@ struct WeightArgs {
 template <bool kLds>
 __global__ __launch_bounds__(kDiagBlock) void k_psens_weights(WeightArgs a) {
     extern __shared__ __align__(16) unsigned char dyn[];
-    __shared__ double red[kDiagWaves];
-    __shared__ int ired[kDiagWaves];
-    __shared__ double fit_b[kPsensMaxM], fit_k[kPsensMaxM], fit_ls[kPsensMaxM], fit_w[kPsensMaxM], fit_post;
+    __shared__ RatioScratch sc;
     const int v = blockIdx.x, tid = threadIdx.x, N = a.N;
     const PsensKeys s = psens_keys<kLds>(dyn, a.work_val, a.work_idx, N);
     const double* col = a.x + a.column[v] * a.cap;
@@ -138,13 +99,13 @@ __global__ __launch_bounds__(kDiagBlock) void k_psens_weights(WeightArgs a) {
         hi = fmax(hi, r);
         nlo = fmax(nlo, -r);
     });
-    bad = unit_block_reduce<kDiagWaves>(bad, ired, unit_or{});
+    bad = unit_block_reduce<kDiagWaves>(bad, sc.ired, unit_or{});
     if (bad) {                                               // (uniform over the block)
         if (tid == 0) a.bad[v] = 1;
         return;
     }
-    hi = unit_block_reduce<kDiagWaves>(hi, red, unit_max{});
-    nlo = unit_block_reduce<kDiagWaves>(nlo, red, unit_max{});
+    hi = unit_block_reduce<kDiagWaves>(hi, sc.red, unit_max{});
+    nlo = unit_block_reduce<kDiagWaves>(nlo, sc.red, unit_max{});
     if (hi + nlo == 0.0) {                                   // max - min == 0: uniform weights
         const double u = 1.0 / (double)N;
         for (int i = tid; i < N; i += kDiagBlock) w[i] = u;
@@ -165,93 +126,17 @@ __global__ __launch_bounds__(kDiagBlock) void k_psens_weights(WeightArgs a) {
     __syncthreads();
     psens_block_sort(s, N);
 
-    // 3. the cutoff and the tail: the values strictly above it, a suffix of the sort within its last tail_n places
-    const double xcutoff = fmax(s.val[N - a.tail_n - 1], kLogDblMin);
-    const double expxcutoff = exp(xcutoff);
-    int above = 0;
-    for (int p = N - a.tail_n + tid; p < N; p += kDiagBlock) above += s.val[p] > xcutoff;
-    const int n = unit_block_reduce<kDiagWaves>(above, ired, unit_sum{});
-    const int t0 = N - n;
-
-    // 4. _gpdfit on the exceedances exp(x) - exp(cutoff), ascending (sbe_psis_column.hip.h, step 5)
-    double k_hat = INFINITY, sigma = 0.0;
-    if (n > 4) {
-        for (int i = tid; i < n; i += kDiagBlock) ary[i] = exp(s.val[t0 + i]) - expxcutoff;
-        __syncthreads();
-        const int m = 30 + (int)sqrt((double)n);
-        const double q = 3 * ary[(int)(n / 4.0 + 0.5) - 1], inv_last = 1 / ary[n - 1];
-        const int lane = tid & 63, wave = tid >> 6;
-        for (int c = wave; c < m; c += kDiagWaves) {          // k_ary[c] = mean(log1p(-b[c] * ary)): one wave per candidate
-            double b = 1 - sqrt(m / ((double)(c + 1) - 0.5));
-            b /= q;
-            b += inv_last;
-            double acc = 0.0;
-            for (int i = lane; i < n; i += 64) acc += log1p(-b * ary[i]);
-            acc = unit_wave_reduce(acc, unit_sum{});
-            if (lane == 0) { fit_b[c] = b; fit_k[c] = acc / n; }
-        }
-        __syncthreads();
-        if (tid < m) fit_ls[tid] = n * (log(-(fit_b[tid] / fit_k[tid])) - fit_k[tid] - 1);
-        __syncthreads();
-        if (tid < m) {
-            double z = 0.0;
-            for (int c = 0; c < m; ++c) z += exp(fit_ls[c] - fit_ls[tid]);
-            fit_w[tid] = 1 / z;
-        }
-        __syncthreads();
-        if (tid == 0) {                                       // prune negligible weights (NaN included), normalise, posterior b
-            double wsum = 0.0;
-            for (int c = 0; c < m; ++c) if (fit_w[c] >= 10 * kDblEps) wsum += fit_w[c];
-            double b_post = 0.0;
-            for (int c = 0; c < m; ++c) if (fit_w[c] >= 10 * kDblEps) b_post += fit_b[c] * (fit_w[c] / wsum);
-            fit_post = b_post;
-        }
-        __syncthreads();
-        const double b_post = fit_post;
-        double acc = 0.0;
-        for (int i = tid; i < n; i += kDiagBlock) acc += log1p(-b_post * ary[i]);
-        const double k_post = unit_block_reduce<kDiagWaves>(acc, red, unit_sum{}) / n;
-        sigma = -k_post / b_post;
-        k_hat = (n * k_post + 10 * 0.5) / (n + 10);
-    }
-
-    // 5. the smoothed tail (_gpinv; NaN when sigma <= 0, not repaired), truncated at 0
-    if (n > 4 && isfinite(k_hat)) {
-        for (int i = tid; i < n; i += kDiagBlock) {
-            const double p = (0.5 + i) / n;
-            double gq = NAN;
-            if (!(sigma <= 0)) {
-                gq = fabs(k_hat) < kDblEps ? -log1p(-p) : expm1(-k_hat * log1p(-p)) / k_hat;
-                gq *= sigma;
-            }
-            double x = log(gq + expxcutoff);
-            if (x > 0) x = 0;
-            s.val[t0 + i] = x;
-        }
-        __syncthreads();
-    }
-
-    // 6. logsumexp, the weights to their samples, ess (a NaN in the tail makes every weight NaN, as the checker's does)
-    double top = -INFINITY;
-    int nan = 0;
-    for (int p = tid; p < N; p += kDiagBlock) {
-        top = fmax(top, s.val[p]);
-        nan |= isnan(s.val[p]);
-    }
-    top = unit_block_reduce<kDiagWaves>(top, red, unit_max{});
-    nan = unit_block_reduce<kDiagWaves>(nan, ired, unit_or{});
-    if (nan) top = NAN;
-    double sum = 0.0;
-    for (int p = tid; p < N; p += kDiagBlock) sum += exp(s.val[p] - top);
-    sum = unit_block_reduce<kDiagWaves>(sum, red, unit_sum{});
-    const double lse = log(sum) + top;
+    // 3 - 5. the cutoff, the tail, _gpdfit, _gpinv and the truncation at 0; 6. logsumexp, the weights to their samples, ess
+    // (a NaN in the tail makes every weight NaN, as the checker's does): sbe_psis_ratio.hip.h
+    const double k_hat = ratio_smooth_tail(s, N, a.tail_n, ary, sc);
+    const double lse = ratio_logsumexp(s, N, sc);
     double sumsq = 0.0;
     for (int p = tid; p < N; p += kDiagBlock) {
         const double wp = exp(s.val[p] - lse);
         w[s.idx[p]] = wp;
         sumsq += wp * wp;
     }
-    sumsq = unit_block_reduce<kDiagWaves>(sumsq, red, unit_sum{});
+    sumsq = unit_block_reduce<kDiagWaves>(sumsq, sc.red, unit_sum{});
     if (tid == 0) {
         a.bad[v] = 0;
         a.k_out[v] = k_hat;
